@@ -14,11 +14,19 @@ Per-GPU work is fixed as N grows (weak scaling, batch-sharded DP; the model's gr
 all-reduced over RCCL in 8 MB buckets issued from inside backward -- netscripts/gradreduce.py --
 the render/warp kernels need no collective).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the outputs of one reproducible
+run of the step if --dump-outputs DIR is given (see there), and prints the line: the contract fields, `hot_path_ms` / `roofline` / `cpu_baseline` null.
+With --full the line also carries
+  "hot_path_ms":  the render + warp hot path alone, forward + backward (hipGraph replay),
   "roofline":     algorithmic bytes / live HIP-event duration of the dominant hot-path kernel,
   "kernels":      the same for every hot-path kernel group (render fwd, render bwd, pair loss...),
   "cpu_baseline": the CPU oracle (oracle/, kind "port") timed on this box's host cores on a
-                  bounded sample of the same hot path (N=1 only).
+                  bounded sample of the same hot path (N=1 only),
+and the run with the stock trunk modules; the complete record goes to the details file (--details-out).
+
+MIOpen's solver search and TunableOp's GEMM tuning start from the results recorded in bench_tuning/ (see its README):
+a shape recorded there is not searched again, any other shape is searched at its first call as before.
+HOC_TUNING_DIR=none searches everything afresh.
 
 Profiling switches (environment, scripts/ only; none of them is set in a measured run): HOC_KERNEL_GROUPS (group names
 of --kernels-only, separated by ';'), HOC_FWD_DBG / HOC_BWD_FLAGS / HOC_FLOW_BWD_DBG (the kernels' own `flags >> 8` switches),
@@ -28,6 +36,7 @@ HOC_TORCH_DDP / HOC_FORCE_DDP (A/B of the data-parallel path on one rank), HOC_T
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -45,11 +54,33 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 
 
+def _positive(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, got {n}")
+    return n
+
+
+def _non_negative(text):
+    n = int(text)
+    if n < 0:
+        raise argparse.ArgumentTypeError(f"must not be negative, got {n}")
+    return n
+
+
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--steps", type=_positive, default=20, help="timed optimiser steps")
+    p.add_argument("--warmup", type=_non_negative, default=5, help="untimed optimiser steps before them")
+    p.add_argument("--full", action="store_true",
+                   help="also the legs beyond the headline figure: hot path alone, stock trunk, per-kernel bench + roofline "
+                        "(PMC / in-step kernel-trace passes), CPU baseline, details file")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, run the timed path's step once more, reproducibly (from the run's starting "
+                        "state, on the last timed step's batches, deterministic convolutions), and write what it computed "
+                        "as DIR/<name>.npy (float32): the loss, the logged loss terms, and a fixed sample of the updated "
+                        "parameters and of their gradients")
     p.add_argument("--batch", type=int, default=64, help="per-GPU batch size (frames / frame pairs)")
     p.add_argument("--image-size", type=int, default=256, help="frame width (= side of the square raster)")
     p.add_argument("--image-height", type=int, default=None, help="frame height if not square (BASELINE config 3: 480 x 270)")
@@ -852,7 +883,102 @@ def self_launch(args):
     sys.stderr.flush()
     # one OpenMP thread per rank unless the caller says otherwise (what torchrun itself would set, without its warning)
     os.environ.setdefault("OMP_NUM_THREADS", "1")
-    os.execv(sys.executable, cmd)
+    # (a child process, not an exec: this process may already have opened the GPU runtime to count the devices)
+    sys.exit(subprocess.call(cmd))
+
+
+TUNING_DIR = os.path.join(ROOT, "bench_tuning")
+
+
+def use_recorded_tuning():
+    """Start MIOpen's solver search and TunableOp's GEMM tuning from the results recorded in bench_tuning/ (MIOpen user
+    find-db / perf-db files, TunableOp results file), so that a fresh process does not spend its warm-up steps searching
+    again what an earlier run on an MI355X has measured.  A shape without a record (another MIOpen / hipBLASLt version,
+    another workload) is searched at its first call, as without this.  The working copies live in a temporary directory
+    that goes away at exit; HOC_TUNING_OUT=DIR keeps them in DIR instead and writes TunableOp's results there at exit
+    (how bench_tuning/ is recorded).  HOC_TUNING_DIR=none starts from nothing.  Returns the TunableOp results file."""
+    import atexit
+    import glob
+    import shutil
+    import tempfile
+
+    src = os.environ.get("HOC_TUNING_DIR", TUNING_DIR)
+    out = os.environ.get("HOC_TUNING_OUT")
+    if out:
+        os.makedirs(out, exist_ok=True)
+    else:
+        out = tempfile.mkdtemp(prefix="hoc_tuning_")
+
+        def drop():  # (TunableOp rewrites its file at exit when it tuned new shapes: not this copy, which goes away)
+            if torch.cuda.is_initialized() and torch.cuda.tunable.is_enabled():
+                torch.cuda.tunable.tuning_enable(False)
+            shutil.rmtree(out, ignore_errors=True)
+
+        atexit.register(drop)
+    recorded = [] if src.lower() == "none" else glob.glob(os.path.join(src, "miopen", "*.txt"))
+    # (a database the caller points MIOpen at stays theirs; child processes of this run inherit the working copy)
+    if "MIOPEN_USER_DB_PATH" not in os.environ:
+        for f in recorded:
+            if not os.path.exists(os.path.join(out, os.path.basename(f))):
+                shutil.copy(f, out)
+        os.environ["MIOPEN_USER_DB_PATH"] = out
+    tunable = os.path.join(out, "tunableop_results.csv")
+    if src.lower() != "none" and os.path.exists(os.path.join(src, "tunableop_results.csv")) and not os.path.exists(tunable):
+        shutil.copy(os.path.join(src, "tunableop_results.csv"), tunable)
+    return tunable
+
+
+def recorded_solver_choices(args, device_index):
+    """True when bench_tuning/ holds the measured solver search of this run's workload (bench_tuning/workloads.json) and
+    MIOpen's user database holds its find-db file for this device and MIOpen version (<arch><CUs in hex>.HIP.<version>_*,
+    the name MIOpen reads).  Then the step's convolutions can be asked for without exhaustive search: MIOpen's Find (default
+    hybrid find mode) answers each from its find-db record -- the solution the search measured fastest, compiled alone --
+    instead of searching, benchmarking and compiling every candidate again, which an exhaustive Find does in a fresh
+    process even with the record present (~30 s of a fresh box's warm-up)."""
+    import glob
+
+    src = os.environ.get("HOC_TUNING_DIR", TUNING_DIR)
+    try:
+        with open(os.path.join(src, "workloads.json")) as fh:
+            workloads = json.load(fh)
+    except (OSError, ValueError):
+        return False
+    mine = {"batch": args.batch, "image_size": args.image_size, "image_height": args.image_height or args.image_size,
+            "encoder_dtype": args.encoder_dtype}
+    if mine not in workloads:
+        return False
+    props = torch.cuda.get_device_properties(device_index)
+    v = torch.backends.cudnn.version() or 0
+    prefix = "%s%x.HIP.%d_%d_%d_" % (props.gcnArchName.split(":")[0], props.multi_processor_count, v // 1000000,
+                                     v // 1000 % 1000, v % 1000)
+    db = os.environ.get("MIOPEN_USER_DB_PATH")
+    return bool(db) and bool(glob.glob(os.path.join(db, glob.escape(prefix) + "*.ufdb.txt")))
+
+
+def dump_outputs(path, loss, logs, params, sample=1 << 20):
+    """What a step handed its caller -- the loss and the logged loss terms -- and what it did to the model:
+    the updated parameters and the gradients it computed, as a fixed sample (seed 0) of `sample` positions in the
+    concatenation of all trainable parameters in model order.  float32 .npy files, about 8 MB in all."""
+    import re
+
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(path, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"), np.asarray(a, dtype=np.float32))
+
+    save("loss", loss.detach().float().cpu().numpy())
+    for k, v in sorted(logs.items()):
+        if torch.is_tensor(v):
+            save("log_" + k, v.detach().float().cpu().numpy())
+        elif isinstance(v, (int, float)):
+            save("log_" + k, np.float64(v))
+    flat_p = torch.cat([p_.detach().reshape(-1).float() for p_ in params])
+    flat_g = torch.cat([(p_.grad if p_.grad is not None else torch.zeros_like(p_)).detach().reshape(-1).float() for p_ in params])
+    n = flat_p.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, sample), replace=False))
+    idx_t = torch.from_numpy(idx).to(flat_p.device)
+    save("params_sample", flat_p[idx_t].cpu().numpy())
+    save("grads_sample", flat_g[idx_t].cpu().numpy())
 
 
 _T0 = time.perf_counter()
@@ -884,19 +1010,24 @@ def main():
     # ... and PyTorch's TunableOp for the fp32 GEMMs of the heads (rocBLAS' default pick for [192,512] x [512,256] is a
     # single-workgroup kernel: 91 us for 25 MFLOP, twice per step): every GEMM shape is timed over the rocBLAS / hipBLASLt
     # solutions at its first call, inside the warm-up steps; 26.8 instead of 27.2 ms per step.  HOC_TUNABLEOP=0 disables.
-    # Its results file goes to the temp directory, not the working tree.
+    # Both start from the results recorded in bench_tuning/ (use_recorded_tuning): on a fresh box the searches took ~90 s
+    # of warm-up.  Working copies go to the temp directory, not the working tree.
+    tunable_file = None if (args.kernels_only or args.roofline_only) else use_recorded_tuning()
     if os.environ.get("HOC_TUNABLEOP", "1") == "1" and not (args.kernels_only or args.roofline_only or args.hot_only):
-        import tempfile
         torch.cuda.tunable.enable(True)
         torch.cuda.tunable.tuning_enable(True)
         torch.cuda.tunable.set_max_tuning_duration(10)    # ms per candidate solution
         torch.cuda.tunable.set_max_tuning_iterations(20)
-        torch.cuda.tunable.set_filename(os.path.join(tempfile.gettempdir(), "hoc_tunableop_%d.csv" % os.getpid()))
+        torch.cuda.tunable.set_filename(tunable_file)
     # HOC_SHARE_GPU=1 (tests only): ranks beyond the device count share GPUs, with HOC_DIST_BACKEND=gloo -- RCCL
     # refuses two ranks on one device; this is how a world_size-2 job is exercised on the one-GPU test box
     dev_index = local_rank % torch.cuda.device_count() if os.environ.get("HOC_SHARE_GPU", "0") == "1" else local_rank
     torch.cuda.set_device(dev_index)
     dev = torch.device("cuda", dev_index)
+    if torch.backends.cudnn.benchmark and tunable_file is not None and recorded_solver_choices(args, dev_index):
+        # the measured search of this workload is recorded: a non-exhaustive Find answers from the record (same solutions)
+        torch.backends.cudnn.benchmark = False
+        _phase("convolutions: the solver choices recorded in bench_tuning/")
     dist = None
     # HOC_FORCE_DDP=1: take the multi-GPU code path (RCCL process group, bucketed gradient reducer, barriers, max-over-ranks
     # all-reduce) with a single rank too -- how the path is exercised on a one-GPU box (tests/test_gpu_bench.py)
@@ -960,6 +1091,8 @@ def main():
     # weight gradients now and then, and lives in scripts/graph_step_experiment.py since round 6 -- not in the product.)
     fused_adam = os.environ.get("HOC_FUSED_ADAM", "1") == "1"
     optimizer = torch.optim.Adam(params, lr=5e-5, fused=fused_adam)
+    # (--dump-outputs: the state the run starts from, for the reproducible step after the timed ones)
+    start_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if args.dump_outputs else None
     loader = SyntheticConsistLoader(B, is_, seed=rank, device=dev, pool=2, image_height=ih_)
 
     def barrier():
@@ -1015,6 +1148,7 @@ def main():
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
+    _phase("warm-up done; timed steps")
     t0 = time.perf_counter()
     loss = torch.zeros(1)
     for i in range(0 if args.hot_only else args.steps):
@@ -1048,9 +1182,35 @@ def main():
         allchk = [torch.zeros_like(chk) for _ in range(world)]
         dist.all_gather(allchk, chk)
         assert all(torch.equal(c_, allchk[0]) for c_ in allchk), f"replicas diverged: {[float(c_) for c_ in allchk]}"
+    if args.dump_outputs and not args.hot_only:
+        # What the timed path computes, reproducibly: its step function once more, from the state the run started from,
+        # on the last timed step's batches, with a fresh optimiser of the same settings.  Not the last timed step itself:
+        # the steps' float atomics (convolution split-K, gradient scatters) round differently from run to run, the
+        # rasteriser turns such differences into flipped pixels and Adam carries them on, so after a few steps two runs
+        # differ far beyond rounding (loss ~1e-3, gradients ~0.5 relative).  Here MIOpen is held to deterministic
+        # solvers (too slow for the timed steps) and everything enters from the same values: two runs agree to rounding
+        # where the solver choices are recorded (bench_tuning/workloads.json); elsewhere each run's own search picks them.
+        model.load_state_dict(start_state)
+        opt_d = torch.optim.Adam(params, lr=5e-5, fused=fused_adam)
+        premodel.step_count = 1000
+        saved_det, saved_tunable = torch.backends.cudnn.deterministic, torch.cuda.tunable.is_enabled()
+        torch.backends.cudnn.deterministic = True
+        torch.cuda.tunable.enable(False)  # (the BLAS libraries' own choice: not one a run's tuning timed)
+        try:
+            loss_d, logs_d = train_step(loader.step_batches(n_warm + args.steps - 1), premodel, opt_d, check_nan=check_nan,
+                                        reducer=reducer)
+            if check_nan:
+                raise_pending_nan(opt_d)
+            torch.cuda.synchronize()
+        finally:
+            torch.backends.cudnn.deterministic = saved_det
+            torch.cuda.tunable.enable(saved_tunable)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss_d, logs_d, params)
+            _phase(f"outputs written to {args.dump_outputs}")
 
     # hot path alone (2 renders, flows, occlusion, pair loss, backward to the vertices)
-    hot_ms = None
+    hot_ms, hot_eager_ms, hot_graph_ms = None, None, None
     if args.step_only:
         if rank == 0:
             os.write(real_stdout, (json.dumps({"ms_per_step": round(dt / args.steps * 1e3, 3), "steps": args.steps}) + "\n").encode())
@@ -1058,7 +1218,7 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    if rank == 0:
+    if rank == 0 and (args.full or args.hot_only):
         from handobjectconsist_amd.models import warpbranch
 
         consist = loader.step_batches(0)[1]
@@ -1108,10 +1268,10 @@ def main():
     # the module substitution; memory format (channels-last), MIOpen's measured solver search (cudnn.benchmark) and TunableOp
     # are stock PyTorch features and stay as `value` has them.  `--stock-trunk-nchw` adds the round-1..4 leg (NCHW, solver
     # search off) as stock_trunk_nchw.  Single GPU only.
-    _phase("hot path done; stock trunk")
     stock, stock_nchw = None, None
-    if rank == 0 and world == 1 and not use_dist and not args.hot_only and not args.no_stock_trunk \
+    if rank == 0 and world == 1 and not use_dist and args.full and not args.hot_only and not args.no_stock_trunk \
             and args.encoder_dtype == "f32":
+        _phase("hot path done; stock trunk")
         from handobjectconsist_amd.models import synthnet as _sn
 
         def stock_leg(channels_last, solver_search, what):
@@ -1151,7 +1311,7 @@ def main():
             stock_nchw = stock_leg(False, False, "stock modules, NCHW, cudnn.benchmark off (the stock_trunk leg of rounds 1-4)")
 
     kernels, roof, roof_fwd, cpu, warp_tiles, in_step_line = None, None, None, None, None, None
-    if rank == 0 and not args.no_kernel_bench:
+    if rank == 0 and args.full and not args.no_kernel_bench:
         _phase("stock trunk done; kernel bench")
         # (N > 1: the other ranks sit in the final barrier meanwhile -- the roofline groups only, a few launches each)
         kernels = kernel_bench(dev, B, is_, args.kernel_iters) if world == 1 else \
@@ -1199,7 +1359,7 @@ def main():
         roof["hot_path_eager_ms_host_bound"] = None if hot_ms is None else round(hot_eager_ms, 3)
         roof["stock_trunk_it_s"] = None if stock is None else stock["value"]
         roof["stock_trunk_is"] = None if stock is None else "north-star-conformant step (stock BatchNorm2d / ReLU / MaxPool2d modules; everything else as `value`)"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         _phase("CPU baseline")
         ncpu = os.cpu_count() or 1
         try:
@@ -1229,7 +1389,8 @@ def main():
             # (what the scalar above is, so that lines of different rounds are not compared blindly: rounds 1-2 reported the
             # eager, host-bound figure under this key; roofline.frac is on the kernel's compulsory bytes since round 3,
             # SURVEY 8(d)'s algorithmic figure rides along as roofline.frac_algorithmic)
-            "hot_path_ms_is": "hot_path.device_ms_graph_replay" if hot_graph_ms is not None else "hot_path.eager_ms_host_bound",
+            "hot_path_ms_is": None if hot_ms is None else
+                              "hot_path.device_ms_graph_replay" if hot_graph_ms is not None else "hot_path.eager_ms_host_bound",
             "hot_path": None if hot_ms is None else {
                 "what": "render + warp hot path, forward + backward to the vertices (vertex stage, 2B-mesh flow render, occlusion + "
                         "epilogue, pair loss, their backward passes)",
@@ -1238,7 +1399,7 @@ def main():
             "ranks": ranks, "stock_trunk": stock, "stock_trunk_nchw": stock_nchw, "roofline": roof, "roofline_forward": roof_fwd, "warp_tiles": warp_tiles,
             "in_step_kernels_us": in_step_line, "kernels": kernels, "cpu_baseline": cpu,
         }
-        details = args.details_out or "bench_details.json"
+        details = args.details_out or ("bench_details.json" if args.full else "-")  # (a plain run writes no file)
         if details != "-":
             try:
                 with open(details, "w") as fh:

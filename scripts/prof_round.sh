@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profile: rocprofv3 --kernel-trace --stats of the DEFAULT bench command + per-(kernel, grid) split + one
+# Round profile: rocprofv3 --kernel-trace --stats of `bench.py --full` (all legs) + per-(kernel, grid) split + one
 # steady-state step + PMC passes over the per-kernel benchmark.  Usage: scripts/prof_round.sh <tag>   (GPU box)
 TAG=${1:-r02}
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_round
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_round -o p -- python $ROOT/bench.py --no-pmc > $OUT/bench_line_profiled.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_round -o p -- python $ROOT/bench.py --full --no-pmc > $OUT/bench_line_profiled.json 2> $OUT/bench.err
 f=$(find /tmp/prof_round -name "p_kernel_trace.csv" | head -1)
 st=$(find /tmp/prof_round -name "p_kernel_stats.csv" | head -1)
 cp "$st" $OUT/bench_kernel_stats.csv

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/evidence_$TAG
 mkdir -p $OUT
 cd $ROOT
-python3 bench.py --gpus 1 --steps 20 --warmup 5 --details-out $OUT/${TAG}_bench_details.json > $OUT/bench_stdout.txt 2> $OUT/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --details-out $OUT/${TAG}_bench_details.json > $OUT/bench_stdout.txt 2> $OUT/bench.err
 tail -1 $OUT/bench_stdout.txt > $OUT/${TAG}_bench_line.json   # (the driver's command; the contract line is the LAST stdout line)
 python bench.py --kernels-only --batch 8 --image-size 480 > $OUT/${TAG}_kernels_480.json 2>/dev/null
 python bench.py --kernels-only --batch 32 --image-size 640 > $OUT/${TAG}_kernels_640.json 2>/dev/null

@@ -35,7 +35,7 @@ def _json_line(out):
 @pytest.mark.gpu
 def test_bench_single_process_line(cuda, tmp_path):
     details = str(tmp_path / "details.json")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--details-out", details] + SMALL,
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--details-out", details] + SMALL,
                          capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = _json_line(res.stdout)
@@ -81,6 +81,40 @@ def test_bench_single_process_line(cuda, tmp_path):
     assert full["cpu_baseline"]["processes"] >= 1
     # the run of the same step with the stock trunk modules
     assert full["stock_trunk"]["value"] > 0 and full["stock_trunk"]["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_step_alone_and_dumps_its_outputs(cuda, tmp_path):
+    """A plain run (no --full): the contract line from the timed steps alone -- no hot-path, stock-trunk, kernel or CPU leg,
+    no details file -- and with --dump-outputs the step's loss, loss terms and parameter / gradient samples as float32
+    .npy files, within 64 MB, the same to rounding in a second run with the same arguments (the headline workload, whose
+    solver choices bench_tuning/ records)."""
+    import numpy as np
+
+    out, again = tmp_path / "outputs", tmp_path / "again"
+    for d in (out, again):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(d), "--steps", "2",
+                              "--warmup", "1"],
+                             capture_output=True, text=True, timeout=1800, cwd=str(tmp_path))
+        assert res.returncode == 0, res.stderr[-2000:]
+    line = _json_line(res.stdout)
+    for k in CONTRACT:
+        assert k in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] - 1e3 / line["value"]) <= 0.01 * line["ms_per_step"]
+    assert line["hot_path_ms"] is None and line["roofline"] is None and line["cpu_baseline"] is None
+    assert line["details"] is None and not (tmp_path / "bench_details.json").exists()
+    files = sorted(p.name for p in out.iterdir())
+    assert {"loss.npy", "params_sample.npy", "grads_sample.npy"} <= set(files) and any(f.startswith("log_") for f in files)
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    for p in out.iterdir():
+        a = np.load(p)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), p.name
+    assert np.abs(np.load(out / "grads_sample.npy")).sum() > 0
+    assert sorted(p.name for p in again.iterdir()) == files
+    for f in files:
+        a, b = np.load(out / f), np.load(again / f)
+        assert np.abs(a - b).max() <= 1e-5 * max(float(np.abs(a).max()), 1e-30), f
 
 
 @pytest.mark.gpu
@@ -246,8 +280,8 @@ def test_baseline_configs_3_and_5_full_steps(cuda, name, extra, dtype):
     cropped) and config 5 (640 x 480 frames, trunk under bf16 autocast, render / warp / heads in fp32) through bench.py:
     the line names the workload and the precision, the loss is finite (bench.py asserts it), and the line is kept as
     evidence (gpurun_out/evidence -> profiles/)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "2", "--no-kernel-bench",
-           "--no-cpu-baseline", "--no-stock-trunk"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "2", "--full",
+           "--no-kernel-bench", "--no-cpu-baseline", "--no-stock-trunk"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     line = _json_line(res.stdout)

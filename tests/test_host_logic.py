@@ -370,21 +370,24 @@ def test_general_flow_path_keeps_the_second_alpha_out_of_autograd(monkeypatch):
 
 
 def test_bench_plain_script_with_gpus_n_becomes_a_launcher(monkeypatch):
-    """`python bench.py --gpus N` without RANK / WORLD_SIZE re-executes itself under torch.distributed.run with N ranks on
-    127.0.0.1 and the original arguments; with fewer devices than N it exits with a one-line message (no traceback)."""
+    """`python bench.py --gpus N` without RANK / WORLD_SIZE runs itself under torch.distributed.run with N ranks on
+    127.0.0.1 and the original arguments, as a child process whose exit status becomes its own; with fewer devices
+    than N it exits with a one-line message (no traceback)."""
     import sys
 
     import bench
 
     launched = {}
-    monkeypatch.setattr(bench.os, "execv", lambda exe, cmd: launched.update(exe=exe, cmd=list(cmd)))
+    monkeypatch.setattr(bench.subprocess, "call", lambda cmd: launched.update(cmd=list(cmd)) or 3)
     monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 8)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "3", "--warmup", "1"])
     monkeypatch.delenv("HOC_SHARE_GPU", raising=False)
     args = bench.parse()
-    bench.self_launch(args)
+    with pytest.raises(SystemExit) as e:
+        bench.self_launch(args)
+    assert e.value.code == 3  # the launcher's exit status
     cmd = launched["cmd"]
-    assert launched["exe"] == sys.executable and cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
+    assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nnodes=1" in cmd and "--nproc-per-node=8" in cmd
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and 1024 < int(cmd[cmd.index("--master-port") + 1]) < 65536
     script = cmd.index(os.path.abspath(bench.__file__))
@@ -500,3 +503,128 @@ def test_cpu_baseline_reports_the_knee_of_its_sweep(monkeypatch):
     monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: (_ for _ in ()).throw(TimeoutError("nothing finished")))
     with pytest.raises(TimeoutError):
         bench.cpu_baseline_at_the_knee(256, 64, 256)
+
+
+def test_bench_options_full_dump_outputs_and_step_counts(monkeypatch):
+    """A plain command line runs the headline figure alone (--full off); --dump-outputs takes a directory; --steps is the
+    number of timed steps and must be at least 1, --warmup must not be negative."""
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "0"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 0 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def test_bench_dump_outputs_writes_float32_files_and_a_fixed_sample(tmp_path):
+    """dump_outputs: loss, loss terms and a seeded sample of the parameters / gradients, float32, same positions every time."""
+    import bench
+
+    torch.manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn(300, 200)), torch.nn.Parameter(torch.randn(50)), torch.nn.Parameter(torch.randn(7))]
+    for p in params[:2]:
+        p.grad = torch.randn_like(p)  # (the last one has no gradient: zeros)
+    logs = {"reg_loss": torch.tensor(0.5), "warp/consist": torch.tensor(0.25, dtype=torch.float64), "step": 3}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(1.5), logs, params, sample=1000)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grads_sample.npy", "log_reg_loss.npy", "log_step.npy", "log_warp_consist.npy", "loss.npy",
+                     "params_sample.npy"]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params]).numpy()
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+    ps = np.load(tmp_path / "a" / "params_sample.npy")
+    assert ps.shape == (1000,) and np.isin(ps, flat_p).all() and len(np.unique(ps)) == 1000
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 1.5 and float(np.load(tmp_path / "a" / "log_step.npy")) == 3.0
+
+
+def test_bench_starts_from_the_recorded_tuning(monkeypatch, tmp_path):
+    """use_recorded_tuning: MIOpen's user database and TunableOp's results file start as copies of the recorded ones in a
+    directory of the run's own; a database the caller names stays theirs; HOC_TUNING_DIR=none starts from nothing."""
+    import bench
+
+    rec = tmp_path / "rec"
+    (rec / "miopen").mkdir(parents=True)
+    (rec / "miopen" / "gfx950_256.HIP.ufdb.txt").write_text("key=solver:1.0\n")
+    (rec / "tunableop_results.csv").write_text("Validator,PT_VERSION,x\n")
+    out = tmp_path / "out"
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH", raising=False)
+    monkeypatch.setenv("HOC_TUNING_DIR", str(rec))
+    monkeypatch.setenv("HOC_TUNING_OUT", str(out))
+    f = bench.use_recorded_tuning()
+    assert f == str(out / "tunableop_results.csv") and os.environ["MIOPEN_USER_DB_PATH"] == str(out)
+    assert (out / "gfx950_256.HIP.ufdb.txt").read_text() == "key=solver:1.0\n"
+    assert (out / "tunableop_results.csv").read_text() == "Validator,PT_VERSION,x\n"
+    (out / "tunableop_results.csv").write_text("grown\n")  # a working copy is never overwritten by the recorded one
+    bench.use_recorded_tuning()
+    assert (out / "tunableop_results.csv").read_text() == "grown\n"
+    mine = tmp_path / "mine"
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", str(mine))
+    monkeypatch.setenv("HOC_TUNING_OUT", str(tmp_path / "out2"))
+    bench.use_recorded_tuning()
+    assert os.environ["MIOPEN_USER_DB_PATH"] == str(mine) and not mine.exists()
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH")
+    monkeypatch.setenv("HOC_TUNING_DIR", "none")
+    monkeypatch.setenv("HOC_TUNING_OUT", str(tmp_path / "out3"))
+    f = bench.use_recorded_tuning()
+    assert os.listdir(tmp_path / "out3") == [] and not os.path.exists(f)
+    # without HOC_TUNING_OUT: a temporary directory of its own, the committed records in it
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH")
+    monkeypatch.delenv("HOC_TUNING_OUT")
+    monkeypatch.delenv("HOC_TUNING_DIR")
+    f = bench.use_recorded_tuning()
+    work = os.environ["MIOPEN_USER_DB_PATH"]
+    assert os.path.dirname(f) == work and not work.startswith(bench.ROOT)
+    assert sorted(os.listdir(work)) == sorted(os.listdir(os.path.join(bench.TUNING_DIR, "miopen")) +
+                                              (["tunableop_results.csv"] if os.path.exists(f) else []))
+
+
+def test_bench_uses_the_recorded_solver_choices_only_where_they_apply(monkeypatch, tmp_path):
+    """recorded_solver_choices: only for a workload listed in workloads.json, and only when MIOpen's user database holds the
+    find-db file of this device (arch + CU count in hex) and MIOpen version -- otherwise the search runs as before."""
+    import sys
+    import types
+
+    import bench
+
+    rec = tmp_path / "rec"
+    rec.mkdir()
+    (rec / "workloads.json").write_text('[{"batch": 64, "image_size": 256, "image_height": 256, "encoder_dtype": "f32"}]')
+    db = tmp_path / "db"
+    db.mkdir()
+    (db / "gfx950100.HIP.3_5_0_abc.ufdb.txt").write_text("")
+    monkeypatch.setenv("HOC_TUNING_DIR", str(rec))
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", str(db))
+    props = types.SimpleNamespace(gcnArchName="gfx950:sramecc+:xnack-", multi_processor_count=256)
+    monkeypatch.setattr(bench.torch.cuda, "get_device_properties", lambda i: props)
+    monkeypatch.setattr(bench.torch.backends.cudnn, "version", lambda: 3005000)
+
+    def args(*extra):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + list(extra))
+        return bench.parse()
+
+    assert bench.recorded_solver_choices(args(), 0) is True  # the headline workload (defaults)
+    assert bench.recorded_solver_choices(args("--batch", "32"), 0) is False
+    assert bench.recorded_solver_choices(args("--image-height", "200"), 0) is False
+    assert bench.recorded_solver_choices(args("--encoder-dtype", "bf16"), 0) is False
+    props.multi_processor_count = 304  # another device
+    assert bench.recorded_solver_choices(args(), 0) is False
+    props.multi_processor_count = 256
+    monkeypatch.setattr(bench.torch.backends.cudnn, "version", lambda: 3006000)  # another MIOpen
+    assert bench.recorded_solver_choices(args(), 0) is False
+    monkeypatch.setattr(bench.torch.backends.cudnn, "version", lambda: 3005000)
+    monkeypatch.setenv("HOC_TUNING_DIR", "none")
+    assert bench.recorded_solver_choices(args(), 0) is False
+    # the committed records cover the headline workload on an MI355X
+    monkeypatch.delenv("HOC_TUNING_DIR")
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", os.path.join(bench.TUNING_DIR, "miopen"))
+    assert bench.recorded_solver_choices(args(), 0) is True
