@@ -11,12 +11,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (HOC_LIB_PATH: another build of the same ABI -- scripts/build_variant.py makes A / B libraries for one-box kernel comparisons)
 LIB_PATH = os.environ.get("HOC_LIB_PATH") or os.path.join(_HERE, "libmeshraster_hip.so")
-ABI_VERSION = 8  # MR_ABI_VERSION of include/meshraster_hip.h
+ABI_VERSION = 9  # MR_ABI_VERSION of include/meshraster_hip.h
 FLAG_REFERENCE_ALGO = 1
 FLAG_SPARSE_TILES = 2
 FLAG_OUTPUT_ZEROED = 4
 FLAG_TILE_PER_WORKGROUP = 8
 FLAG_TILE_LIST_CLEARED = 16
+CRITERION_L1 = 0  # MR_CRITERION_L1: the pair loss's per-channel term |res|
+CRITERION_L2 = 1  # MR_CRITERION_L2: res * res
 
 _c = ctypes
 _P, _I, _F, _L = _c.c_void_p, _c.c_int, _c.c_float, _c.c_int64
@@ -74,6 +76,14 @@ SIGNATURES = {
     "mr_flow_pair_forward_grad_tiles": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _P, _P, _P, _P]),
     "mr_flow_pair_backward_unit_tiles": (_I, [_P] * 9 + [_I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P]),
     "mr_flow_pair_scatter_work_bytes": (_L, [_I, _I]),
+    # ABI 9: the entry points that form the pair loss or its gradient with a trailing criterion (MR_CRITERION_*)
+    "mr_pair_consist_forward_crit": (_I, [_P] * 6 + [_I, _P, _L] + [_P] * 11 + [_I, _I, _I, _F, _P, _P, _I, _P, _I]),
+    "mr_pair_consist_backward_crit": (_I, [_P] * 6 + [_I] + [_P] * 5 + [_I, _I, _I, _F, _P, _P, _I, _P, _P, _I]),
+    "mr_pair_consist_forward_tiles_crit": (_I, [_P] * 6 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _F, _P, _P, _I, _P, _P, _L, _L, _P, _I]),
+    "mr_pair_consist_backward_tiles_crit": (_I, [_P] * 6 + [_I] + [_P] * 5 + [_I, _I, _I, _F, _P, _P, _I, _P, _P, _P, _L, _L, _P, _I]),
+    "mr_flow_pair_forward_tiles_crit": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _I]),
+    "mr_flow_pair_backward_tiles_crit": (_I, [_P] * 9 + [_I] + [_P] * 8 + [_I, _I, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _P, _I]),
+    "mr_flow_pair_forward_grad_tiles_crit": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _P, _P, _P, _P, _I]),
     "mr_pair_step_struct_bytes": (_L, []),
     "mr_pair_step_field_offsets": (_I, [_P, _I]),
     "mr_pair_step_sizes": (_I, [_P, _P, _P, _P]),
@@ -162,6 +172,14 @@ def call(name, *args):
         kind = {-1: "bad argument", -2: "not implemented"}.get(rc, f"hipError_t {rc}")
         raise RuntimeError(f"{name} failed: {kind}")
     return rc
+
+
+def crit_call(name, criterion, *args):
+    """``call`` of a pair-loss entry point for the criterion ``criterion`` (MR_CRITERION_*): the entry point itself for l1
+    (what every l1 caller has always called), its ``_crit`` form with the criterion appended otherwise."""
+    if criterion == CRITERION_L1:
+        return call(name, *args)
+    return call(name + "_crit", *args, int(criterion))
 
 
 def tile_list(workspace, batch_size, num_faces, image_size):

@@ -1,7 +1,7 @@
 // pair_step.hip -- the frame-pair step of the training path behind ONE argument block (ABI 8; include/meshraster_hip.h).
 //
 // What /root/reference/meshreg/models/warpbranch.py:59-88 runs per frame pair -- get_opticalflow (opticalflow.py:51-156) with
-// detach_textures=False, detach_renders=True, pair_consist (imgflowarp.py:58-115) with PyramidCriterion("l1")
+// detach_textures=False, detach_renders=True, pair_consist (imgflowarp.py:58-115) with PyramidCriterion("l1" or "l2": MrPairStep.criterion)
 // (pyramidloss.py:56-62, lossutils.py:1-8) and the mean over the batch -- is five launches forward and two backward in this
 // library.  Round 5's caller issued them through five C calls that marshalled 30 - 60 scalars each, allocated a dozen buffers
 // and kept two autograd nodes: 0.47 - 0.55 ms of host time per pass for 0.17 ms of device work.  Here the caller fills one
@@ -32,7 +32,7 @@ int mr_flow_pair_forward_grad_tiles_ex(const float* mask_flow1, const float* mas
                                        int width, float distance_thresh, float warp_thresh, float pair_thresh, const void* list_header,
                                        const void* list_entries, int64_t list_capacity, int64_t tile_bound, float* unit_grad,
                                        float* unit_grad_max, float* loss_sum, void* scatter_work, float* mean_out, int mean_of,
-                                       int reset_list, const void* records, mr_stream_t stream);
+                                       int reset_list, const void* records, mr_stream_t stream, int criterion);
 
 int mr_render_flow_forward_pair(const float* verts, const int32_t* faces_idx, const float* vcolors, const float* background,
                                 int bg_stride, const float* keep_lut, int n_lut, float alpha_thresh, float* rgb_img, float* alpha_img,
@@ -60,7 +60,8 @@ struct PairStepLayout {
 static int pair_step_layout(const MrPairStep& a, PairStepLayout& L) {
     if (a.batch_size < 0 || a.num_verts_a < 0 || a.num_verts_b <= 0 || a.num_hand_faces < 0 || a.num_obj_faces < 0 ||
         a.image_size <= 0 || a.height <= 0 || a.width < 2 || a.height > a.image_size || a.width > a.image_size ||
-        (a.jitter_channels != 1 && a.jitter_channels != 3) || a.batch_size > (1 << 20))
+        (a.jitter_channels != 1 && a.jitter_channels != 3) || a.batch_size > (1 << 20) ||
+        (a.criterion != MR_CRITERION_L1 && a.criterion != MR_CRITERION_L2))
         return MR_ERR_BADARG;
     const int64_t B2 = 2LL * a.batch_size, V = (int64_t)a.num_verts_a + a.num_verts_b;
     const int64_t F0 = (int64_t)a.num_hand_faces + a.num_obj_faces, F = a.fill_back ? 2 * F0 : F0;
@@ -103,7 +104,7 @@ extern "C" int mr_pair_step_field_offsets(int64_t* offsets, int capacity) {
 #define MR_PS_FIELDS(X)                                                                                                        \
     X(batch_size) X(num_verts_a) X(num_verts_b) X(num_hand_faces) X(num_obj_faces) X(hand_faces_batched) X(fill_back)          \
     X(image_size) X(height) X(width) X(jitter_channels) X(cam_batched) X(n_lut) X(bg_stride) X(texel_layout) X(want_grad)     \
-    X(mean_of) X(flags) X(orig_size) X(near_) X(far_) X(eps) X(alpha_thresh) X(distance_thresh) X(warp_thresh) X(pair_thresh) \
+    X(mean_of) X(flags) X(criterion) X(reserved) X(orig_size) X(near_) X(far_) X(eps) X(alpha_thresh) X(distance_thresh) X(warp_thresh) X(pair_thresh) \
     X(verts1a) X(verts1b) X(verts2a) X(verts2b) X(K1) X(K2) X(R) X(t) X(dist_coeffs) X(hand_faces) X(obj_faces) X(keep_lut)    \
     X(background) X(image_ref) X(image) X(jitter_ref) X(jitter) X(scratch) X(saved) X(scratch_bytes) X(saved_bytes) X(flows)   \
     X(losses) X(tile_count_out) X(tile_bound) X(grad_loss_fwd) X(grad_loss_bwd) X(grad_loss_sum) X(grad_mean) X(grad_verts1a) \
@@ -210,7 +211,7 @@ extern "C" int mr_pair_step_forward(const MrPairStep* step, mr_stream_t stream) 
                                          // (the finalize launch's last workgroup leaves the mean in losses[3 B]; the B words
                                          // behind it -- the caller's buffer has 4 B + 1 -- carry the samples' values to it)
                                          // (reset_list: the finalize launch leaves the list header's counters zero for the next step)
-                                         a.losses + 3 * (int64_t)B, a.mean_of, 1, records, stream);
+                                         a.losses + 3 * (int64_t)B, a.mean_of, 1, records, stream, a.criterion);
     return rc;
 }
 

@@ -860,7 +860,7 @@ __device__ unsigned long long mr_dbg_st[4096 * 8];  // profiling builds: phase s
 #define MR_ST_STAMP(k) do { } while (0)
 #endif
 
-template <bool FLOWGRAD, bool REC, bool PAIR, bool UNIT = false, bool WORK = false>
+template <bool FLOWGRAD, bool REC, bool PAIR, bool UNIT = false, bool WORK = false, PairCrit CRIT = PairCrit::L1>
 __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp) {
     MR_ST_STAMP(0);
     extern __shared__ long long vtab[];  // [V * NCH] rounded up to an even count
@@ -1065,7 +1065,7 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
                     pin(q);
                     const DirRaw r = unpack(q, tp.a);
                     const DirOut e = pair_eval(tp, r, sp.H, sp.W, sp.pair_thresh, false);
-                    const float2 gp = pair_grad(tp, r, e, sp.H, sp.W, coef);
+                    const float2 gp = pair_grad<CRIT>(tp, r, e, sp.H, sp.W, coef);
                     gq = make_float2((gp.x * post) * a, (gp.y * post) * a);
                 }
             }
@@ -1277,6 +1277,11 @@ __global__ void __launch_bounds__(ST_WAVES * MR_WAVE) scatter_tiles_kernel(Scatt
 __global__ void __launch_bounds__(ST_WAVES * MR_WAVE) __attribute__((amdgpu_waves_per_eu(8, 8)))
 pair_scatter_tiles_kernel(ScatterTilesParams sp) {
     scatter_tiles_body<true, true, true>(sp);
+}
+// ... for the l2 criterion (MR_CRITERION_L2: res * res per channel, gradient 2 res)
+__global__ void __launch_bounds__(ST_WAVES * MR_WAVE) __attribute__((amdgpu_waves_per_eu(8, 8)))
+pair_scatter_tiles_l2_kernel(ScatterTilesParams sp) {
+    scatter_tiles_body<true, true, true, false, false, PairCrit::L2>(sp);
 }
 
 // ... and with the pair loss's gradient already formed by the forward launch (mr_flow_pair_backward_unit_tiles): the
@@ -2681,15 +2686,16 @@ extern "C" int mr_render_flow_backward(const float* verts, const int32_t* faces_
     return MR_OK;
 }
 
-extern "C" int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
-                                           const int32_t* vertex_id_map, const float* flows, const float* image_ref,
-                                           const float* image, const float* jitter_ref, const float* jitter,
-                                           int jitter_channels, const float* sums, const float* grad_loss_fwd,
-                                           const float* grad_loss_bwd, const float* mask_pre, const float* mask_x_lo,
-                                           const float* mask_x_hi, const float* occl, float* grad_flow_scratch, int height,
-                                           int width, float* grad_vcolors, int batch_size, int num_verts, int num_faces,
-                                           int fill_back, int image_size, float eps, float pair_thresh, int flags,
-                                           int texel_layout, mr_stream_t stream) {
+extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
+                                                const int32_t* vertex_id_map, const float* flows, const float* image_ref,
+                                                const float* image, const float* jitter_ref, const float* jitter,
+                                                int jitter_channels, const float* sums, const float* grad_loss_fwd,
+                                                const float* grad_loss_bwd, const float* mask_pre, const float* mask_x_lo,
+                                                const float* mask_x_hi, const float* occl, float* grad_flow_scratch, int height,
+                                                int width, float* grad_vcolors, int batch_size, int num_verts, int num_faces,
+                                                int fill_back, int image_size, float eps, float pair_thresh, int flags,
+                                                int texel_layout, mr_stream_t stream, int criterion) {
+    if (criterion != MR_CRITERION_L1 && criterion != MR_CRITERION_L2) return MR_ERR_BADARG;
     if (batch_size < 0 || (batch_size & 1) || num_faces < 0 || num_verts < 0 || image_size <= 0 || !texel_layout_ok(texel_layout))
         return MR_ERR_BADARG;
     if (!grad_vcolors && (int64_t)batch_size * num_verts > 0) return MR_ERR_BADARG;
@@ -2729,9 +2735,26 @@ extern "C" int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const 
     sp.pair_thresh = pair_thresh;
     const int64_t blocks = (int64_t)batch_size * sp.groups;
     if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-    hipLaunchKernelGGL(pair_scatter_tiles_kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
+    hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_scatter_tiles_l2_kernel : pair_scatter_tiles_kernel,
+                       dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
     MR_CHECK_LAUNCH();
     return MR_OK;
+}
+
+extern "C" int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
+                                           const int32_t* vertex_id_map, const float* flows, const float* image_ref,
+                                           const float* image, const float* jitter_ref, const float* jitter,
+                                           int jitter_channels, const float* sums, const float* grad_loss_fwd,
+                                           const float* grad_loss_bwd, const float* mask_pre, const float* mask_x_lo,
+                                           const float* mask_x_hi, const float* occl, float* grad_flow_scratch, int height,
+                                           int width, float* grad_vcolors, int batch_size, int num_verts, int num_faces,
+                                           int fill_back, int image_size, float eps, float pair_thresh, int flags,
+                                           int texel_layout, mr_stream_t stream) {
+    return mr_flow_pair_backward_tiles_crit(face_index_map, tile_hit, weight_map, vertex_id_map, flows, image_ref, image, jitter_ref,
+                                            jitter, jitter_channels, sums, grad_loss_fwd, grad_loss_bwd, mask_pre, mask_x_lo,
+                                            mask_x_hi, occl, grad_flow_scratch, height, width, grad_vcolors, batch_size, num_verts,
+                                            num_faces, fill_back, image_size, eps, pair_thresh, flags, texel_layout, stream,
+                                            MR_CRITERION_L1);
 }
 
 // mr_flow_pair_backward_unit_tiles with the two extra incoming gradients of mr_pair_step_backward (pair_step.hip): of

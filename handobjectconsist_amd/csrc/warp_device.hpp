@@ -523,6 +523,23 @@ __device__ __forceinline__ DirOut pair_eval(const DirTaps& d, const DirRaw& r, i
     return o;
 }
 
+// The photometric criterion of the pair loss (PyramidCriterion, pyramidloss.py:56-62): the per-channel term of a residual
+// res = warped - target and its derivative.  A compile-time parameter of every kernel that forms the loss or its gradient:
+// the host picks the instantiation (MR_CRITERION_*), nothing branches on it inside the loops.
+enum class PairCrit { L1, L2 };
+
+template <PairCrit CRIT>
+__device__ __forceinline__ float pair_term(float res) {
+    if constexpr (CRIT == PairCrit::L2) return res * res;  // torch.nn.MSELoss(reduction="none")
+    else return fabsf(res);                                // torch.nn.L1Loss(reduction="none")
+}
+template <PairCrit CRIT>
+__device__ __forceinline__ float pair_dterm(float res) {
+    if constexpr (CRIT == PairCrit::L2) return 2.0f * res;
+    else return (res > 0.0f) ? 1.0f : ((res < 0.0f) ? -1.0f : 0.0f);
+}
+
+template <PairCrit CRIT = PairCrit::L1>
 __device__ __forceinline__ float2 pair_grad(const DirTaps& d, const DirRaw& r, const DirOut& o, int H, int W,
                                              float coef) {
     float gu = 0.0f, gv = 0.0f;
@@ -532,7 +549,7 @@ __device__ __forceinline__ float2 pair_grad(const DirTaps& d, const DirRaw& r, c
             float gix, giy;
             bilin_grad_q(r.src[c], d.t, d.a, gix, giy);
             const float res = o.s[c] - r.tgt[c];
-            const float sg = (res > 0.0f) ? 1.0f : ((res < 0.0f) ? -1.0f : 0.0f);
+            const float sg = pair_dterm<CRIT>(res);
             const float g = sg * coef * o.m;
             gu += g * gix;
             gv += g * giy;

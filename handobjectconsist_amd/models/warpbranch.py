@@ -65,10 +65,12 @@ def _frame_parts(samples, all_results, gt_refs, first_only):
     return frames
 
 
-def _fused_pairs(samples, all_results, hand_face, gt_refs, first_only, renderer, image_size, hand_ignore_faces, use_backward):
+def _fused_pairs(samples, all_results, hand_face, gt_refs, first_only, renderer, image_size, hand_ignore_faces, use_backward,
+                 crit):
     """The "loss" mode of ``forward`` with every (frame 0, frame k) pair as ONE fused node (opticalflow.flow_pair_loss:
     render, then occlusion + epilogue + pair loss in one pass, one backward launch; hand and object go in as separate
-    tensors, concatenated by index inside the kernels); None when the node does not apply."""
+    tensors, concatenated by index inside the kernels); None when the node does not apply.  ``crit``: MR_CRITERION_* of the
+    pair loss (imgflowarp._fused_criterion)."""
     cams = [_q(sample, "camintr").cuda() for sample in samples]
     ref_image, ref_jitter = _q(samples[0], "image").cuda(), _q(samples[0], "jittermask").cuda()
     parts = _frame_parts(samples, all_results, gt_refs, first_only)
@@ -78,7 +80,7 @@ def _fused_pairs(samples, all_results, hand_face, gt_refs, first_only, renderer,
         res = opticalflow.flow_pair_loss([parts[0], parts[k]], faces, [cams[0], cams[k]], renderer, image_size,
                                          ref_image, _q(samples[k], "image").cuda(), ref_jitter,
                                          _q(samples[k], "jittermask").cuda(), ignore_face_idxs=hand_ignore_faces, with_sum=True,
-                                         with_mean="sum" if use_backward else "fwd")
+                                         with_mean="sum" if use_backward else "fwd", criterion=crit)
         if res is None:
             return None if k == 1 else _raise_mixed()
         loss_fwd, loss_bwd, pair_flows, loss_sum, mean = res
@@ -124,9 +126,10 @@ def forward(
     Returns:
         (mean pair loss, {"masks", "warps", "recons_flows", "diffs", "diff_losses"})
     """
-    if pair_outputs == "loss" and imgflowarp._is_fused_l1(criterion):
+    crit = imgflowarp._fused_criterion(criterion)  # (l1 / l2: the fused pair kernels; None: anything else)
+    if pair_outputs == "loss" and crit is not None:
         fused = _fused_pairs(samples, all_results, hand_face, gt_refs, first_only, renderer, image_size, hand_ignore_faces,
-                             use_backward)
+                             use_backward, crit)
         if fused is not None:
             return fused
     verts_world, all_faces = _frame_meshes(samples, all_results, hand_face, gt_refs, first_only)
@@ -140,8 +143,9 @@ def forward(
         detach_renders=True,
         ignore_face_idxs=hand_ignore_faces,
         # "loss": nobody but pair_consist looks at the flows -- they (and the gradient that comes back for them) are then
-        # computed and stored under the renders' covered tiles only
-        sparse_flows=(pair_outputs == "loss"),
+        # computed and stored under the renders' covered tiles only.  Only where pair_consist reads them with the fused
+        # kernels (a criterion they compute): the composed path samples the flows over the whole image.
+        sparse_flows=(pair_outputs == "loss" and crit is not None),
     )
     ref_image, ref_jitter = _q(samples[0], "image").cuda(), _q(samples[0], "jittermask").cuda()
     per_pair = [

@@ -1,11 +1,14 @@
 """Photometric criterion -- drop-in for meshreg/optim/pyramidloss.py.
 
-Only the configuration the reference ever enables is on the hot path:
-``PyramidCriterion('l1')`` with ``level_nb=1`` (warpreg.py:34, trainmeshwarp.py
-``--consist_criterion l1``); ``imgflowarp.pair_consist`` recognises it and runs the fused HIP
-kernel.  ``l2`` works through the composed path.  ``ssim`` and ``level_nb > 1`` need kornia's
-SSIM / ScalePyramid (third-party, never enabled by any reference script): out of scope, they
-raise NotImplementedError instead of silently computing something else."""
+The two criteria the reference's trainer offers with ``level_nb=1`` are on the hot path:
+``PyramidCriterion('l1')`` (warpreg.py:34, trainmeshwarp.py ``--consist_criterion l1``, the
+default) and ``PyramidCriterion('l2')`` (``--consist_criterion l2``).  ``imgflowarp.pair_consist``,
+``opticalflow.flow_pair_loss`` and ``warpbranch.forward`` recognise them
+(``imgflowarp._fused_criterion``) and run the fused HIP kernels with the matching
+MR_CRITERION_* instantiation (|res| or res * res per channel, then the same per-sample masked
+mean); ``compute`` below is what the composed path runs.  ``ssim`` and ``level_nb > 1`` need
+kornia's SSIM / ScalePyramid (third-party, never enabled by any reference script): out of scope,
+they raise NotImplementedError instead of silently computing something else."""
 import torch
 
 from handobjectconsist_amd.optim import lossutils

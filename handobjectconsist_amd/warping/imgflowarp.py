@@ -7,10 +7,11 @@ warp, ~15 element-wise passes per pair) are replaced by the HIP kernels of csrc/
 
 * ``warp``               -> mr_warp_forward / mr_warp_backward (sample + validity in one pass)
 * ``get_occlusion_mask`` -> mr_occlusion_mask (4 chained nearest warps fused, no intermediates)
-* ``pair_consist``       -> mr_pair_consist_forward / _backward when the criterion is the
-                            reference's default ``PyramidCriterion('l1')`` with ``level_nb=1``;
-                            any other criterion goes through the composed ``warp`` path with
-                            the reference's exact control flow.
+* ``pair_consist``       -> mr_pair_consist_forward / _backward (_crit) when the criterion is
+                            ``PyramidCriterion('l1')`` (the reference's default) or
+                            ``PyramidCriterion('l2')`` with ``level_nb=1``; any other criterion
+                            goes through the composed ``warp`` path with the reference's exact
+                            control flow.
 
 Semantics preserved on purpose: Q5 (flow validity looks at the x
 component only), Q6 (jitter masks warped with the opposite flow, compared ``== 1``), Q7
@@ -108,12 +109,12 @@ DEBUG_POISON_SPARSE_GRADS = False
 
 
 class _PairConsistFunction(torch.autograd.Function):
-    """Fused both-direction masked-L1 photometric loss.  Differentiable w.r.t. the two
-    flows only (the images / jitter masks are data on the training path)."""
+    """Fused both-direction masked-L1 / masked-L2 photometric loss (``crit``: MR_CRITERION_*).  Differentiable w.r.t. the
+    two flows only (the images / jitter masks are data on the training path)."""
 
     @staticmethod
     def forward(ctx, flow12, flow21, image_ref, image, jitter_ref, jitter, thresh, want_debug, coverage=None, coverage_size=0,
-                tiles=None):
+                tiles=None, crit=_lib.CRITERION_L1):
         _lib.check_cuda(flow12, flow21, image_ref, image, jitter_ref, jitter)
         im_ref, im = _lib.contig(image_ref), _lib.contig(image)
         ctx.stacked = flow21 is None  # flow12 = [2B,H,W,2]: both flows in one tensor (get_opticalflow's fused path)
@@ -143,6 +144,7 @@ class _PairConsistFunction(torch.autograd.Function):
                 raise ValueError("coverage must be the [2B, tiles_y, tiles_x, 4] byte array of a raster of coverage_size")
             hit12, hit21 = coverage[:B], coverage[B:]
         ctx.coverage = (hit12, hit21, int(coverage_size))
+        ctx.crit = int(crit)
         lib = _lib.load()
         sums = torch.empty((B, 4), dtype=torch.float32, device=dev)
         loss_fwd = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -154,7 +156,7 @@ class _PairConsistFunction(torch.autograd.Function):
         if listed:
             wbytes = int(lib.mr_pair_consist_tiles_workspace_bytes(B, int(coverage_size)))
             work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-            _lib.call("mr_pair_consist_forward_tiles", _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
+            _lib.crit_call("mr_pair_consist_forward_tiles", ctx.crit, _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
                       _lib.ptr(jm_ref), _lib.ptr(jm), Cj, _lib.ptr(work), wbytes, _lib.ptr(sums), _lib.ptr(loss_fwd),
                       _lib.ptr(loss_bwd), B, H, W, float(thresh), _lib.ptr(hit12), _lib.ptr(hit21), int(coverage_size),
                       tiles[0], tiles[1], tiles[2], tiles[3], _lib.stream_ptr(dev))
@@ -169,7 +171,7 @@ class _PairConsistFunction(torch.autograd.Function):
             fm1 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
             fm2 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
             dbg = [fm1, fm2] + [torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) for _ in range(6)]
-        _lib.call("mr_pair_consist_forward", _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
+        _lib.crit_call("mr_pair_consist_forward", ctx.crit, _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
                   _lib.ptr(jm_ref), _lib.ptr(jm), Cj, _lib.ptr(work), wbytes, _lib.ptr(sums),
                   _lib.ptr(loss_fwd), _lib.ptr(loss_bwd), *[_lib.ptr(t) for t in dbg], B, H, W, float(thresh),
                   _lib.ptr(hit12), _lib.ptr(hit21), int(coverage_size) if hit12 is not None else 0, _lib.stream_ptr(dev))
@@ -187,7 +189,7 @@ class _PairConsistFunction(torch.autograd.Function):
         f12, f21, im_ref, im, jm_ref, jm, sums = ctx.saved_tensors
         B, _, H, W = im.shape
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) or (g_fwd is None and g_bwd is None):
-            return (None,) * 11
+            return (None,) * 12
         hit12, hit21, cov_size = ctx.coverage
         dev = im.device
         if g_fwd is None:
@@ -201,13 +203,13 @@ class _PairConsistFunction(torch.autograd.Function):
             grad_both = (torch.full((2 * B, H, W, 2), float("nan"), dtype=torch.float32, device=dev) if DEBUG_POISON_SPARSE_GRADS
                          else torch.empty((2 * B, H, W, 2), dtype=torch.float32, device=dev))
             gmax = torch.zeros((2 * B,), dtype=torch.float32, device=dev) if PASS_GRADIENT_BOUND else None
-            _lib.call("mr_pair_consist_backward_tiles", _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
+            _lib.crit_call("mr_pair_consist_backward_tiles", ctx.crit, _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
                       _lib.ptr(jm_ref), _lib.ptr(jm), int(jm.shape[1]), _lib.ptr(sums), _lib.ptr(g_fwd), _lib.ptr(g_bwd),
                       _lib.ptr(grad_both[:B]), _lib.ptr(grad_both[B:]), B, H, W, ctx.thresh, _lib.ptr(hit12), _lib.ptr(hit21),
                       cov_size, _lib.ptr(gmax), tiles[0], tiles[1], tiles[2], tiles[3], _lib.stream_ptr(dev))
             if gmax is not None:
                 grad_both._hoc_grad_bound = (gmax, grad_both._version)
-            return (grad_both,) + (None,) * 10
+            return (grad_both,) + (None,) * 11
         if ctx.stacked:  # one gradient tensor for the stacked flows: no slice / cat nodes in autograd
             grad_both = torch.empty((2 * B, H, W, 2), dtype=torch.float32, device=dev)
             grad12, grad21 = grad_both[:B], grad_both[B:]
@@ -218,15 +220,15 @@ class _PairConsistFunction(torch.autograd.Function):
         else:
             grad12 = torch.empty_like(f12)
             grad21 = torch.empty_like(f21)
-        _lib.call("mr_pair_consist_backward", _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
+        _lib.crit_call("mr_pair_consist_backward", ctx.crit, _lib.ptr(f12), _lib.ptr(f21), _lib.ptr(im_ref), _lib.ptr(im),
                   _lib.ptr(jm_ref), _lib.ptr(jm), int(jm.shape[1]), _lib.ptr(sums), _lib.ptr(g_fwd),
                   _lib.ptr(g_bwd), _lib.ptr(grad12), _lib.ptr(grad21), B, H, W, ctx.thresh, _lib.ptr(hit12), _lib.ptr(hit21),
                   cov_size if hit12 is not None else 0, _lib.ptr(gmax), _lib.stream_ptr(dev))
         if ctx.stacked:
             if gmax is not None:  # (rides on the gradient tensor, tied to its version like the coverage bytes of the flows)
                 grad_both._hoc_grad_bound = (gmax, grad_both._version)
-            return (grad_both,) + (None,) * 10
-        return (grad12, grad21) + (None,) * 9
+            return (grad_both,) + (None,) * 11
+        return (grad12, grad21) + (None,) * 10
 
 
 def _stacked_base(flow12, flow21):
@@ -242,13 +244,20 @@ def _stacked_base(flow12, flow21):
     return base
 
 
-def _is_fused_l1(criterion):
-    """True for the reference's default criterion: PyramidCriterion('l1'), level_nb == 1."""
-    return (
-        getattr(criterion, "level_nb", None) == 1
-        and isinstance(getattr(criterion, "criterion", None), torch.nn.L1Loss)
-        and getattr(criterion.criterion, "reduction", None) == "none"
-    )
+def _fused_criterion(criterion):
+    """The MR_CRITERION_* code of a criterion the fused pair kernels compute -- ``PyramidCriterion('l1')`` (the reference's
+    default) -> ``_lib.CRITERION_L1``, ``PyramidCriterion('l2')`` -> ``_lib.CRITERION_L2``, both with level_nb == 1 and
+    reduction "none" -- or None for anything else (those take the composed path, and get dense flows)."""
+    if getattr(criterion, "level_nb", None) != 1:
+        return None
+    loss = getattr(criterion, "criterion", None)
+    if getattr(loss, "reduction", None) != "none":
+        return None
+    if isinstance(loss, torch.nn.L1Loss):
+        return _lib.CRITERION_L1
+    if isinstance(loss, torch.nn.MSELoss):
+        return _lib.CRITERION_L2
+    return None
 
 
 # pair_consist(..., outputs=...): "full" returns masks / warps / diffs like the reference;
@@ -305,7 +314,8 @@ def pair_consist(
     image_ref, image = image_ref.cuda(), image.cuda()
     jitter_mask_ref, jitter_mask = jitter_mask_ref.cuda(), jitter_mask.cuda()
     # (the fused kernels fetch the two taps of a row with one 8-byte load: images at least 2 wide)
-    if _is_fused_l1(criterion) and image.shape[1] == 3 and jitter_mask.shape[1] in (1, 3) and image.shape[-1] >= 2:
+    crit = _fused_criterion(criterion)
+    if crit is not None and image.shape[1] == 3 and jitter_mask.shape[1] in (1, 3) and image.shape[-1] >= 2:
         want_debug = outputs == "full"
         stacked = _stacked_base(recons_flow[0], recons_flow[1])
         coverage, coverage_size = _coverage_of(stacked)
@@ -315,7 +325,8 @@ def pair_consist(
                              'only: pair_consist reads them with outputs="loss" (the tile-list kernels)')
         res = _PairConsistFunction.apply(stacked if stacked is not None else recons_flow[0],
                                          None if stacked is not None else recons_flow[1], image_ref, image,
-                                         jitter_mask_ref, jitter_mask, 0.99999, want_debug, coverage, coverage_size, tiles)
+                                         jitter_mask_ref, jitter_mask, 0.99999, want_debug, coverage, coverage_size, tiles,
+                                         crit)
         losses_fwd, losses_bwd = res[0], res[1]
         warp_loss = losses_bwd + losses_fwd if use_backward else losses_fwd
         if not want_debug:

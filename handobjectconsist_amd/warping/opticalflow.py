@@ -560,11 +560,11 @@ class _FlowPairLossFunction(torch.autograd.Function):
     (loss_fwd[B], loss_bwd[B], loss_bwd + loss_fwd, flows[2B,H,W,2], tile_hit): opticalflow.py:98-154 + imgflowarp.py:58-115 +
     pyramidloss.py:56-62 + lossutils.py:1-8 for one frame pair.  Differentiable w.r.t. ``cols`` only (the training
     setting: detach_renders=True, images are data).  ``flows`` are defined under the covered tiles only; the render's tile
-    list goes back to the caller in ``tile_out`` (a list the caller owns)."""
+    list goes back to the caller in ``tile_out`` (a list the caller owns).  ``crit``: the pair loss's criterion (MR_CRITERION_*)."""
 
     @staticmethod
     def forward(ctx, ndc, faces2, cols, lut, fill_back, image_size, near, far, eps, background_color, height, width,
-                image_ref, image, jitter_ref, jitter, thresh, cleared_work=None, tile_out=None):
+                image_ref, image, jitter_ref, jitter, thresh, cleared_work=None, tile_out=None, crit=_lib.CRITERION_L1):
         ctx.set_materialize_grads(False)
         _lib.check_cuda(image_ref, image, jitter_ref, jitter)
         r = _render_stacked_flow(ndc, faces2, cols, lut, fill_back, image_size, near, far, eps, background_color,
@@ -595,16 +595,16 @@ class _FlowPairLossFunction(torch.autograd.Function):
             # the images' covered-tile lists: the finalize launch writes them, the backward hands out its workgroups over them
             scatter_work = (torch.empty((int(_lib.load().mr_flow_pair_scatter_work_bytes(B, is_)),), dtype=torch.uint8, device=dev)
                             if USE_SCATTER_WORK else None)
-            _lib.call("mr_flow_pair_forward_grad_tiles", *args, _lib.ptr(unit_grad), _lib.ptr(unit_max), _lib.ptr(loss_sum),
-                      _lib.ptr(scatter_work), st)
+            _lib.crit_call("mr_flow_pair_forward_grad_tiles", int(crit), *args, _lib.ptr(unit_grad), _lib.ptr(unit_max),
+                           _lib.ptr(loss_sum), _lib.ptr(scatter_work), st)
         else:
-            _lib.call("mr_flow_pair_forward_tiles", *args, st)
+            _lib.crit_call("mr_flow_pair_forward_tiles", int(crit), *args, st)
             loss_sum = loss_bwd + loss_fwd
         # (the flows are defined under the covered tiles only: the list rides along with them, as for get_opticalflow(sparse_flows=True))
         if tile_out is not None:
             tile_out.append((where[0], where[1], where[2], int(r["bound"]), r["work"]))
         ctx.cfg = (is_, float(eps), bool(fill_back), height, width, float(thresh), int(r["F0"]), int(r["V"]))
-        ctx.unit = unit
+        ctx.unit, ctx.crit = unit, int(crit)
         if unit:
             ctx.save_for_backward(r["fim"], tile_hit, r["wmap"], r["vid"], unit_grad, unit_max, sums, scatter_work)
         else:
@@ -620,7 +620,7 @@ class _FlowPairLossFunction(torch.autograd.Function):
             g_fwd = g_sum if g_fwd is None else g_fwd + g_sum
             g_bwd = g_sum if g_bwd is None else g_bwd + g_sum
         if not ctx.needs_input_grad[2] or (g_fwd is None and g_bwd is None):
-            return (None,) * 19
+            return (None,) * 20
         fim = ctx.saved_tensors[0]
         B2 = fim.shape[0]
         B, dev = B2 // 2, fim.device
@@ -637,17 +637,17 @@ class _FlowPairLossFunction(torch.autograd.Function):
                       _lib.ptr(unit_grad), _lib.ptr(unit_max), _lib.ptr(sums), _lib.ptr(g_fwd), _lib.ptr(g_bwd), height, width,
                       _lib.ptr(grad_cols), B2, V, F0, int(fill_back), is_, eps, _lib.FLAG_OUTPUT_ZEROED if zeroed else 0,
                       textutils.texel_layout_code(), _lib.ptr(scatter_work), _lib.stream_ptr(dev))
-            return (None, None, grad_cols) + (None,) * 16
+            return (None, None, grad_cols) + (None,) * 17
         fim, tile_hit, wmap, vid, mask, alpha, occl, flow, im_ref, im, jm_ref, jm, sums = ctx.saved_tensors
         # scratch of the launch: the masked flow gradient of a workgroup's tiles between its two passes
         scratch = (torch.full((B2, height, width, 2), float("nan"), dtype=torch.float32, device=dev) if DEBUG_POISON_RENDER_OUTPUTS
                    else torch.empty((B2, height, width, 2), dtype=torch.float32, device=dev))
-        _lib.call("mr_flow_pair_backward_tiles", _lib.ptr(fim), _lib.ptr(tile_hit), _lib.ptr(wmap), _lib.ptr(vid), _lib.ptr(flow),
+        _lib.crit_call("mr_flow_pair_backward_tiles", ctx.crit, _lib.ptr(fim), _lib.ptr(tile_hit), _lib.ptr(wmap), _lib.ptr(vid), _lib.ptr(flow),
                   _lib.ptr(im_ref), _lib.ptr(im), _lib.ptr(jm_ref), _lib.ptr(jm), int(jm.shape[1]), _lib.ptr(sums), _lib.ptr(g_fwd),
                   _lib.ptr(g_bwd), _lib.ptr(mask), _lib.ptr(mask[:B]), _lib.ptr(alpha[B:]), _lib.ptr(occl), _lib.ptr(scratch),
                   height, width, _lib.ptr(grad_cols), B2, V, F0, int(fill_back), is_, eps, thresh,
                   _lib.FLAG_OUTPUT_ZEROED if zeroed else 0, textutils.texel_layout_code(), _lib.stream_ptr(dev))
-        return (None, None, grad_cols) + (None,) * 16
+        return (None, None, grad_cols) + (None,) * 17
 
 
 def dense_flows(pair_flows):
@@ -672,7 +672,7 @@ def dense_flows(pair_flows):
 
 
 def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image_ref, image, jitter_mask_ref, jitter_mask,
-                   ignore_face_idxs=None, with_sum=False, with_mean=None):
+                   ignore_face_idxs=None, with_sum=False, with_mean=None, criterion=_lib.CRITERION_L1):
     """``get_opticalflow(verts_cam, ..., detach_textures=False, detach_renders=True)`` followed by
     ``pair_consist(flows, image_ref, image, jitter_mask_ref, jitter_mask, PyramidCriterion("l1"))`` for ONE frame pair, as a
     single fused node (no counterpart function in the reference: opticalflow.py:51-156 + imgflowarp.py:58-115 composed).
@@ -688,7 +688,11 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
     element-wise launch less each way for callers that want the sum).  ``with_mean`` ("sum" or "fwd"): one more element, the
     mean over the batch of ``loss_bwd + loss_fwd`` / of ``loss_fwd`` (warpbranch.py:87-88 for one pair) -- the node's own
     output where the pair goes through ``pairstep`` (ABI 8: (hand, object) parts whose vertices want a gradient), a
-    ``torch.mean`` otherwise."""
+    ``torch.mean`` otherwise.  ``criterion``: the photometric criterion as its MR_CRITERION_* code -- ``_lib.CRITERION_L1``
+    (``PyramidCriterion("l1")``, the default) or ``_lib.CRITERION_L2`` (``PyramidCriterion("l2")``;
+    ``imgflowarp._fused_criterion`` maps a criterion object to its code)."""
+    if criterion not in (_lib.CRITERION_L1, _lib.CRITERION_L2):
+        raise ValueError(f"criterion must be an MR_CRITERION_* code (0: l1, 1: l2), got {criterion!r}")
     parts = isinstance(verts_cam[0], (tuple, list))  # (hand, object) vertex tensors per frame + (hand, object) faces
     if parts:
         (h1, o1), (h2, o2) = verts_cam
@@ -722,7 +726,7 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
         lut = _keep_lut(ignore_face_idxs, dev) if ignore_face_idxs is not None else None
         res = pairstep.pair_step((h1, o1), (h2, o2), hand_face, obj_faces, camintrs[0].to(dev), camintrs[1].to(dev), neurenderer,
                                  is_, H, W, image_ref, image, jitter_mask_ref, jitter_mask, lut, mean_of_fwd_only=(with_mean == "fwd"),
-                                 poison=DEBUG_POISON_RENDER_OUTPUTS, flags=_FWD_DBG_FLAGS | _PAIR_STEP_FLAGS)
+                                 poison=DEBUG_POISON_RENDER_OUTPUTS, flags=_FWD_DBG_FLAGS | _PAIR_STEP_FLAGS, criterion=criterion)
         if res is not None:
             mean, loss_sum, loss_fwd, loss_bwd, flows, tile_hit = res
             # (the render's tile list lives in the plan's scratch, which the next call reuses: the note carries the coverage only)
@@ -759,7 +763,7 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
     loss_fwd, loss_bwd, loss_sum, flows, tile_hit = _FlowPairLossFunction.apply(
         ndc, faces2, cols, lut, neurenderer.fill_back, is_, neurenderer.near, neurenderer.far,
         neurenderer.rasterizer_eps, neurenderer.background_color, H, W, image_ref, image, jitter_mask_ref, jitter_mask, 0.99999,
-        cleared_work, tile_out := [])
+        cleared_work, tile_out := [], criterion)
     tiles = tile_out[0]
     flows._hoc_coverage = (tile_hit, is_, flows._version, tiles)
     out = [loss_fwd, loss_bwd, [flows[:B], flows[B:]]]

@@ -81,8 +81,10 @@ typedef void* mr_stream_t;
  *    binning pass's workgroups, several per image since round 5); mr_flow_pair_prologue_parts takes clear_bytes;
  * 7: scatter_work of mr_flow_pair_forward_grad_tiles / mr_flow_pair_backward_unit_tiles (the covered-tile lists the
  *    backward's workgroups are handed out over), mr_flow_pair_scatter_work_bytes;
- * 8: mr_pair_step_* (the frame-pair step behind one argument struct), mr_pixel_map_terms. */
-#define MR_ABI_VERSION 8
+ * 8: mr_pair_step_* (the frame-pair step behind one argument struct), mr_pixel_map_terms;
+ * 9: the pair loss's photometric criterion (MR_CRITERION_*): *_crit forms of the seven entry points that form the loss or
+ *    its gradient, MrPairStep.criterion. */
+#define MR_ABI_VERSION 9
 MR_API int mr_abi_version(void);
 /* 1 if the calling thread's CURRENT HIP device is a gfx950, else 0.
  * Device contract of every entry point below: kernels are launched on the calling thread's current HIP
@@ -477,6 +479,14 @@ MR_API int mr_flow_finalize_backward(const float* grad_flow, const float* mask_p
                                      int batch_size, int image_size, int height, int width,
                                      mr_stream_t stream);
 
+/* The photometric criterion of the pair loss (PyramidCriterion of pyramidloss.py:56-62 with level_nb 1): the per-channel
+ * term of a residual res = warped - target is |res| (L1, torch.nn.L1Loss) or res * res (L2, torch.nn.MSELoss), both with
+ * reduction "none" followed by the same per-sample masked mean (lossutils.py:1-8); its derivative sign(res) or 2 res.
+ * Every entry point below that forms the pair loss or its gradient has a *_crit form with a trailing `int criterion`;
+ * the form without the suffix is that call with MR_CRITERION_L1.  Any other value: MR_ERR_BADARG. */
+#define MR_CRITERION_L1 0
+#define MR_CRITERION_L2 1
+
 /* Bytes of device workspace mr_pair_consist_forward needs (per-block partial sums). */
 MR_API int64_t mr_pair_consist_workspace_bytes(int batch_size, int height, int width);
 
@@ -519,6 +529,25 @@ MR_API int mr_pair_consist_backward(const float* flow12, const float* flow21, co
                              float* grad_flow12, float* grad_flow21, int batch_size,
                              int height, int width, float thresh, const uint8_t* tile_hit12,
                              const uint8_t* tile_hit21, int hit_image_size, float* grad_max, mr_stream_t stream);
+/* ... for the criterion `criterion` (MR_CRITERION_*): debug output diff1 / diff2 holds the per-channel term (|res| or
+ * res * res), sums[0] / sums[2] the masked sums of the term. */
+MR_API int mr_pair_consist_forward_crit(const float* flow12, const float* flow21, const float* image_ref,
+                                        const float* image, const float* jitter_ref, const float* jitter,
+                                        int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                        float* sums, float* loss_fwd, float* loss_bwd, uint8_t* full_mask1,
+                                        uint8_t* full_mask2, float* warp_mask1, float* warp_mask2,
+                                        float* warp1, float* warp2, float* diff1, float* diff2,
+                                        int batch_size, int height, int width, float thresh,
+                                        const uint8_t* tile_hit12, const uint8_t* tile_hit21, int hit_image_size,
+                                        mr_stream_t stream, int criterion);
+MR_API int mr_pair_consist_backward_crit(const float* flow12, const float* flow21, const float* image_ref,
+                                         const float* image, const float* jitter_ref, const float* jitter,
+                                         int jitter_channels, const float* sums,
+                                         const float* grad_loss_fwd, const float* grad_loss_bwd,
+                                         float* grad_flow12, float* grad_flow21, int batch_size,
+                                         int height, int width, float thresh, const uint8_t* tile_hit12,
+                                         const uint8_t* tile_hit21, int hit_image_size, float* grad_max, mr_stream_t stream,
+                                         int criterion);
 
 /* ---- the warp half of the training path over the render's tile list (the SPARSE contract) -----------------------
  * The stacked render of a frame pair (mr_render_flow_forward over 2B images: frame 1 of every pair, then frame 2; called
@@ -568,6 +597,22 @@ MR_API int mr_pair_consist_backward_tiles(const float* flow12, const float* flow
                                           const uint8_t* tile_hit12, const uint8_t* tile_hit21, int hit_image_size,
                                           float* grad_max, const void* list_header, const void* list_entries,
                                           int64_t list_capacity, int64_t tile_bound, mr_stream_t stream);
+/* ... for the criterion `criterion` (MR_CRITERION_*). */
+MR_API int mr_pair_consist_forward_tiles_crit(const float* flow12, const float* flow21, const float* image_ref,
+                                              const float* image, const float* jitter_ref, const float* jitter,
+                                              int jitter_channels, void* workspace, int64_t workspace_bytes, float* sums,
+                                              float* loss_fwd, float* loss_bwd, int batch_size, int height, int width,
+                                              float thresh, const uint8_t* tile_hit12, const uint8_t* tile_hit21,
+                                              int hit_image_size, const void* list_header, const void* list_entries,
+                                              int64_t list_capacity, int64_t tile_bound, mr_stream_t stream, int criterion);
+MR_API int mr_pair_consist_backward_tiles_crit(const float* flow12, const float* flow21, const float* image_ref,
+                                               const float* image, const float* jitter_ref, const float* jitter,
+                                               int jitter_channels, const float* sums, const float* grad_loss_fwd,
+                                               const float* grad_loss_bwd, float* grad_flow12, float* grad_flow21,
+                                               int batch_size, int height, int width, float thresh,
+                                               const uint8_t* tile_hit12, const uint8_t* tile_hit21, int hit_image_size,
+                                               float* grad_max, const void* list_header, const void* list_entries,
+                                               int64_t list_capacity, int64_t tile_bound, mr_stream_t stream, int criterion);
 
 /* The consistency term of a frame pair in two launches (+ the render).
  * mr_flow_pair_forward_tiles = mr_occlusion_flow_tiles + mr_pair_consist_forward_tiles in ONE pass over the tile list: the
@@ -601,6 +646,26 @@ MR_API int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const uint
                                        int width, float* grad_vcolors, int batch_size, int num_verts, int num_faces,
                                        int fill_back, int image_size, float eps, float pair_thresh, int flags,
                                        int texel_layout, mr_stream_t stream);
+/* ... for the criterion `criterion` (MR_CRITERION_*). */
+MR_API int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                           const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                           const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                           float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                           const float* image_ref, const float* image, const float* jitter_ref,
+                                           const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                           float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
+                                           int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
+                                           const void* list_header, const void* list_entries, int64_t list_capacity,
+                                           int64_t tile_bound, mr_stream_t stream, int criterion);
+MR_API int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
+                                            const int32_t* vertex_id_map, const float* flows, const float* image_ref,
+                                            const float* image, const float* jitter_ref, const float* jitter,
+                                            int jitter_channels, const float* sums, const float* grad_loss_fwd,
+                                            const float* grad_loss_bwd, const float* mask_pre, const float* mask_x_lo,
+                                            const float* mask_x_hi, const float* occl, float* grad_flow_scratch, int height,
+                                            int width, float* grad_vcolors, int batch_size, int num_verts, int num_faces,
+                                            int fill_back, int image_size, float eps, float pair_thresh, int flags,
+                                            int texel_layout, mr_stream_t stream, int criterion);
 
 /* The same pair with the pair loss's gradient formed where its inputs already sit in registers -- in the FORWARD launch
  * (round 4, ABI 5): the training path of opticalflow.flow_pair_loss when the vertices want a gradient.
@@ -637,6 +702,21 @@ MR_API int mr_flow_pair_forward_grad_tiles(const float* mask_flow1, const float*
                                            const void* list_header, const void* list_entries, int64_t list_capacity,
                                            int64_t tile_bound, float* unit_grad, float* unit_grad_max, float* loss_sum,
                                            void* scatter_work, mr_stream_t stream);
+/* ... for the criterion `criterion` (MR_CRITERION_*): unit_grad is the derivative of the sum of the criterion's terms.  The
+ * backward (mr_flow_pair_backward_unit_tiles) takes it as it is: its fixed-point scale comes from unit_grad_max, whatever
+ * the criterion. */
+MR_API int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                                const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                                const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                                float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                                const float* image_ref, const float* image, const float* jitter_ref,
+                                                const float* jitter, int jitter_channels, void* workspace,
+                                                int64_t workspace_bytes, float* sums, float* loss_fwd, float* loss_bwd,
+                                                int batch_size, int image_size, int height, int width, float distance_thresh,
+                                                float warp_thresh, float pair_thresh, const void* list_header,
+                                                const void* list_entries, int64_t list_capacity, int64_t tile_bound,
+                                                float* unit_grad, float* unit_grad_max, float* loss_sum,
+                                                void* scatter_work, mr_stream_t stream, int criterion);
 MR_API int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
                                             const int32_t* vertex_id_map, const float* unit_grad, const float* unit_grad_max,
                                             const float* sums, const float* grad_loss_fwd, const float* grad_loss_bwd,
@@ -667,7 +747,9 @@ MR_API int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, const
  *     grad_verts* nullable (not wanted); all four NULL: nothing to do.  The vertex-colour gradient buffer inside `saved` is
  *     cleared by the FORWARD call (want_grad != 0) and consumed by the first backward call; a caller that differentiates the
  *     same forward call again sets MR_PAIR_STEP_GRAD_BUFFER_USED in `flags` for the later calls (the buffer is then cleared
- *     first).  flags bits 8 and up: profiling switches of the render (forward call only). */
+ *     first).  flags bits 8 and up: profiling switches of the render (forward call only).
+ *   criterion (ABI 9): MR_CRITERION_L1 or MR_CRITERION_L2, the pair loss's criterion (forward call; the backward's scatter
+ *     does not depend on it); reserved: zero. */
 #define MR_PAIR_STEP_GRAD_BUFFER_USED 1
 /* flags bit 1 (forward call): every stage as a launch of its own, as in ABI 8's first form -- the vertex stage + stacked faces
  * (mr_flow_pair_prologue_parts, which also clears the list header) otherwise run inside the render's binning pass.  Same
@@ -682,6 +764,7 @@ typedef struct MrPairStep {
     int32_t batch_size, num_verts_a, num_verts_b, num_hand_faces, num_obj_faces, hand_faces_batched;
     int32_t fill_back, image_size, height, width, jitter_channels, cam_batched;
     int32_t n_lut, bg_stride, texel_layout, want_grad, mean_of, flags;
+    int32_t criterion, reserved;
     float orig_size, near_, far_, eps, alpha_thresh, distance_thresh, warp_thresh, pair_thresh;
     const float *verts1a, *verts1b, *verts2a, *verts2b, *K1, *K2, *R, *t, *dist_coeffs;
     const int64_t *hand_faces, *obj_faces;

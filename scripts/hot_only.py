@@ -1,8 +1,8 @@
 """The render + warp hot path alone (warpbranch.forward + backward to the vertices, "loss" mode), N passes eager and N as a
 hipGraph replay -- the workload of bench.py's hot_path leg without the trainer around it (no MIOpen solver search: starts in
 seconds).  For rocprofv3 --kernel-trace (scripts/hot_kernels.sh) and quick A / B runs:
-    python scripts/hot_only.py [--batch 64] [--image-size 256] [--image-height H] [--passes 30]
-prints {"eager_ms": host-bound wall time per pass, "graph_ms": device time per pass}."""
+    python scripts/hot_only.py [--batch 64] [--image-size 256] [--image-height H] [--passes 30] [--criterion l1|l2]
+prints {"eager_ms": host-bound wall time per pass, "graph_ms": device time per pass, "criterion"}."""
 import argparse
 import json
 import os
@@ -23,11 +23,12 @@ ap.add_argument("--image-size", type=int, default=256)
 ap.add_argument("--image-height", type=int, default=0)
 ap.add_argument("--passes", type=int, default=30)
 ap.add_argument("--no-graph", action="store_true")
+ap.add_argument("--criterion", choices=("l1", "l2"), default="l1")  # (the pair loss's photometric criterion)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 W, H = a.image_size, (a.image_height or a.image_size)
 model = SynthMeshRegNet().to(dev).eval()
-pre = WarpRegNet((W, H), model, lambda_consist=0.001, lambda_data=0.999, criterion="l1", gt_refs=True, progressive_steps=1000,
+pre = WarpRegNet((W, H), model, lambda_consist=0.001, lambda_data=0.999, criterion=a.criterion, gt_refs=True, progressive_steps=1000,
                  use_backward=True, mano_faces=model.mano_layer.th_faces, pair_outputs="loss").to(dev)
 loader = SyntheticConsistLoader(a.batch, W, seed=0, device=dev, pool=1, image_height=H) if a.image_height else \
     SyntheticConsistLoader(a.batch, W, seed=0, device=dev, pool=1)
@@ -50,7 +51,7 @@ t0 = time.perf_counter()
 for _ in range(a.passes):
     hot()
 torch.cuda.synchronize()
-out = {"eager_ms": round((time.perf_counter() - t0) / a.passes * 1e3, 4)}
+out = {"eager_ms": round((time.perf_counter() - t0) / a.passes * 1e3, 4), "criterion": a.criterion}
 if not a.no_graph:
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
