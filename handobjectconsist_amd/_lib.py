@@ -17,6 +17,12 @@ FLAG_SPARSE_TILES = 2
 FLAG_OUTPUT_ZEROED = 4
 FLAG_TILE_PER_WORKGROUP = 8
 FLAG_TILE_LIST_CLEARED = 16
+FLAG_FORCE_PARTS = 1 << 24  # binning pass: several workgroups per image also where one is the default (tests)
+FLAG_ONE_WORKGROUP_PER_IMAGE = 32 << 24  # binning pass: one workgroup per image (the reference of the parts' tests)
+FLAG_PARTS_IN_ONE_LAUNCH = 64 << 24  # binning pass: the last-arriver exchange also where two launches are the default
+FLAG_PLAIN_DIVISIONS = 4096 << 8  # forward renders: plain divisions everywhere (the shared-reciprocal path's reference)
+FLAG_FORCE_GATHER = 32 << 8  # mr_render_vc_backward: the per-face gather also where the scatter's table fits LDS
+FLAG_COUNT_PIXEL_MAP_TERMS = 1024 << 8  # mr_render_backward: count the terms mr_pixel_map_terms reads back
 CRITERION_L1 = 0  # MR_CRITERION_L1: the pair loss's per-channel term |res|
 CRITERION_L2 = 1  # MR_CRITERION_L2: res * res
 

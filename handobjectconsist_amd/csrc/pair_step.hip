@@ -194,7 +194,7 @@ extern "C" int mr_pair_step_forward(const MrPairStep* step, mr_stream_t stream) 
     rc = mr_render_flow_forward_pair(ndc, faces2, cols, a.background, a.bg_stride, a.keep_lut, a.n_lut, a.alpha_thresh,
                                      records ? nullptr : rgb, records ? nullptr : alpha, records ? nullptr : mask,
                                      nullptr, wmap, fim, tile_hit, rwork, L.render_work_bytes, B2, V, L.F0, a.fill_back, is, a.near_, a.far_,
-                                     a.eps, MR_FLAG_SPARSE_TILES | MR_FLAG_TILE_LIST_CLEARED | (a.flags & ~0xff), vid,  // (flags >> 8: the render's profiling switches)
+                                     a.eps, MR_FLAG_SPARSE_TILES | MR_FLAG_TILE_LIST_CLEARED, vid,
                                      (int)(bound > 0x7fffffffLL ? 0x7fffffffLL : bound), a.tile_count_out, grad_buf,
                                      grad_buf ? (int64_t)B2 * V * 3 : 0, a.texel_layout, stream, separate ? nullptr : &pro, records);
     if (rc != MR_OK) return rc;

@@ -60,7 +60,6 @@ struct GatherParams {
     // others were zeroed when the list was built
     const uint32_t* owners;
     const unsigned* n_owners;
-    int dbg_rows;             // profiling: 1 = the row-walking form of the small-face path
 };
 
 template <bool IMG, bool TEX, bool DEPTH>
@@ -110,18 +109,12 @@ __device__ __forceinline__ void gather_pixel(const GatherParams& p, const Face& 
 // the partial sums are combined with shuffles inside the lane group (fixed order: deterministic).  Faces whose bbox
 // exceeds GATHER_BIG pixels are walked by the whole wave instead.
 constexpr int GLPF = 4;
-#ifndef MR_GGL
-#define MR_GGL 8
-#endif
-constexpr int GGL = MR_GGL;   // lanes per face of the generic gather (E: 74 -> 64 us, E + F: 105 -> 93 us against 4; 16: 70 / 101)
+constexpr int GGL = 8;       // lanes per face of the generic gather (E: 74 -> 64 us, E + F: 105 -> 93 us against 4; 16: 70 / 101)
 constexpr int GATHER_BIG = 128;          // vertex-colour gather: bbox area above which the whole wave probes
 // (256 until round 5: the 114 faces of the bench scene with boxes of 256-500 pixels then took the whole-wave path ONE BEHIND THE
 // OTHER inside the wave that holds them -- consecutive wrist faces -- while as ordinary lane groups they advance side by side: E
 // alone 93.7 -> 90.4 us at 256 x 256, 263 -> 230 at 640 x 640; 8192: no further gain at 256, slower at 640)
-#ifndef MR_GATHER_BIG
-#define MR_GATHER_BIG 1024
-#endif
-constexpr int GATHER_BIG_GENERIC = MR_GATHER_BIG;  // generic gather (direct accumulation on the wave-cooperative path)
+constexpr int GATHER_BIG_GENERIC = 1024;  // generic gather (direct accumulation on the wave-cooperative path)
 
 template <bool TEX, bool DEPTH>
 __device__ __forceinline__ void gather_store(const GatherParams& p, int64_t i, const float* gt, const float* gf) {
@@ -146,11 +139,6 @@ __device__ __forceinline__ void gather_store(const GatherParams& p, int64_t i, c
     }
 }
 
-#ifdef MR_GATHER_WPE
-#define MR_GATHER_ATTR __attribute__((amdgpu_waves_per_eu(MR_GATHER_WPE, MR_GATHER_WPE)))
-#else
-#define MR_GATHER_ATTR
-#endif
 // (`vbid` of `vgrid`: the workgroup's place in the gather's own grid -- blockIdx.x of gridDim.x when it is launched alone,
 // a virtual index when its workgroups are interleaved with kernel D's strips in one launch, strip_gather_kernel)
 template <bool IMG, bool TEX, bool DEPTH>
@@ -190,7 +178,7 @@ __device__ __forceinline__ void gather_body(const GatherParams& p, const unsigne
 
     // very large faces first: the whole wave walks the bbox, lane per pixel, butterfly-reduce,
     // the owner lane stores the result straight away
-    unsigned long long m_big = (p.dbg_rows & 2) ? 0ull : __ballot(big && sub == 0);  // (profiling: 2 = big faces skipped)
+    unsigned long long m_big = __ballot(big && sub == 0);
     while (m_big) {
         const int src = __ffsll((long long)m_big) - 1;
         m_big &= m_big - 1;
@@ -239,43 +227,31 @@ __device__ __forceinline__ void gather_body(const GatherParams& p, const unsigne
         Face f;
         load_face(p.faces + i * 9, f, is);
         const int32_t* fim_b = p.fim + (int64_t)b * is * is;
-        if (p.dbg_rows) {  // (profiling: the round-4 form -- every lane evaluates the pixels of its own rows)
-            for (int yi = bx.y0 + sub; yi <= bx.y1; yi += GGL)
-                for (int xi = bx.x0; xi <= bx.x1; xi += 4) {
-                    int hit[4];  // four probes in flight
+        // Round 5.  The face's box goes by chunks of GGL rows x 4 columns: lane `sub` probes row `sub` of the chunk (four
+        // probes in flight), the group ORs its lanes' results into one 32-bit mask, and the pixels the face WON are then
+        // dealt out over the group's lanes by rank -- the few-pixel faces of a dense mesh win 4.6 of the 14 pixels of
+        // their box, so one trip through the ~250 instructions of a pixel serves a whole face at more than half of the
+        // lanes, where "every lane walks its own row" ran four trips (one per column) at a sixth of them.
+        for (int yc = bx.y0; yc <= bx.y1; yc += GGL)
+            for (int xc = bx.x0; xc <= bx.x1; xc += 4) {
+                const int yi = yc + sub;
+                const int yl = min(yi, (int)bx.y1);
+                int hit[4];
 #pragma unroll
-                    for (int u = 0; u < 4; u++) hit[u] = fim_b[yi * is + min(xi + u, (int)bx.x1)];
+                for (int u = 0; u < 4; u++) hit[u] = fim_b[yl * is + min(xc + u, (int)bx.x1)];
+                unsigned gm = 0u;
 #pragma unroll
-                    for (int u = 0; u < 4; u++)
-                        if (xi + u <= bx.x1 && hit[u] == fn) gather_pixel<IMG, TEX, DEPTH>(p, f, b, xi + u, yi, gt, gf);
+                for (int u = 0; u < 4; u++) gm |= (yi <= bx.y1 && xc + u <= bx.x1 && hit[u] == fn) ? (1u << (sub * 4 + u)) : 0u;
+#pragma unroll
+                for (int off = 1; off < GGL; off <<= 1) gm |= (unsigned)__shfl_xor((int)gm, off);
+                const int won = __popc(gm);
+                for (int r = sub; r < won; r += GGL) {
+                    unsigned m = gm;
+                    for (int k = 0; k < r; k++) m &= m - 1u;  // drop the r lowest set bits
+                    const int pos = __ffs((int)m) - 1;
+                    gather_pixel<IMG, TEX, DEPTH>(p, f, b, xc + (pos & 3), yc + (pos >> 2), gt, gf);
                 }
-        } else {
-            // Round 5.  The face's box goes by chunks of GGL rows x 4 columns: lane `sub` probes row `sub` of the chunk (four
-            // probes in flight), the group ORs its lanes' results into one 32-bit mask, and the pixels the face WON are then
-            // dealt out over the group's lanes by rank -- the few-pixel faces of a dense mesh win 4.6 of the 14 pixels of
-            // their box, so one trip through the ~250 instructions of a pixel serves a whole face at more than half of the
-            // lanes, where "every lane walks its own row" ran four trips (one per column) at a sixth of them.
-            for (int yc = bx.y0; yc <= bx.y1; yc += GGL)
-                for (int xc = bx.x0; xc <= bx.x1; xc += 4) {
-                    const int yi = yc + sub;
-                    const int yl = min(yi, (int)bx.y1);
-                    int hit[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) hit[u] = fim_b[yl * is + min(xc + u, (int)bx.x1)];
-                    unsigned gm = 0u;
-#pragma unroll
-                    for (int u = 0; u < 4; u++) gm |= (yi <= bx.y1 && xc + u <= bx.x1 && hit[u] == fn) ? (1u << (sub * 4 + u)) : 0u;
-#pragma unroll
-                    for (int off = 1; off < GGL; off <<= 1) gm |= (unsigned)__shfl_xor((int)gm, off);
-                    const int won = __popc(gm);
-                    for (int r = sub; r < won; r += GGL) {
-                        unsigned m = gm;
-                        for (int k = 0; k < r; k++) m &= m - 1u;  // drop the r lowest set bits
-                        const int pos = __ffs((int)m) - 1;
-                        gather_pixel<IMG, TEX, DEPTH>(p, f, b, xc + (pos & 3), yc + (pos >> 2), gt, gf);
-                    }
-                }
-        }
+            }
     }
     // quad reduction: afterwards every lane of the quad holds the face's sums
 #pragma unroll
@@ -290,7 +266,7 @@ __device__ __forceinline__ void gather_body(const GatherParams& p, const unsigne
     if (valid && sub == 0 && !big) gather_store<TEX, DEPTH>(p, i, gt, gf);
 }
 template <bool IMG, bool TEX, bool DEPTH>
-__global__ void __launch_bounds__(256) MR_GATHER_ATTR gather_kernel(GatherParams p) {
+__global__ void __launch_bounds__(256) gather_kernel(GatherParams p) {
     gather_body<IMG, TEX, DEPTH>(p, blockIdx.x, gridDim.x);
 }
 
@@ -305,7 +281,6 @@ struct GatherVCParams {
     float* grad_vcolors;    // [B,V,3], pre-zeroed, accumulated with fp32 atomics
     int B, V, F0, fill_back, is;
     float eps;
-    int dbg;    // profiling experiments (flags >> 8)
     int texel;  // texel layout code of the vertex-colour texture (mr_common.hpp: texel_vertex)
 };
 
@@ -382,15 +357,10 @@ __global__ void __launch_bounds__(256) gather_vc_kernel(GatherVCParams p) {
 #pragma unroll
         for (int c = 0; c < 3; c++) acc[k][c] = 0.0f;
     const int32_t* fim_b = p.fim + (int64_t)b * is * is;
-    if (p.dbg & 8) {
-        if (valid && v[0] == 12345.0f) p.grad_vcolors[0] = v[1] + v[5];
-        return;
-    }
-
     // P3: one lane per fragment
     int qhead = 0, qn = 0;
     auto shade = [&](int n) {
-        if (lane < n && !(p.dbg & 2)) {
+        if (lane < n) {
             const unsigned fr = fq[(qhead + lane) & (GV_FQ - 1)];
             const int slot = (int)(fr >> 26);
             const float* c = fc + slot * GV_FCS;
@@ -447,10 +417,6 @@ __global__ void __launch_bounds__(256) gather_vc_kernel(GatherVCParams p) {
         const bool big = nonempty && bw * bh > GATHER_BIG;
         const int fn = o ? f0 + p.F0 : f0;
         if (__ballot(nonempty) == 0ull) continue;  // wave-uniform
-        if (p.dbg & 16) {
-            if (nonempty && bw == 12345) p.grad_vcolors[0] = 1.0f;
-            continue;
-        }
 
         // P1: park the orientation's face in the cache, clear its accumulators
         if (sub == 0) {
@@ -468,7 +434,7 @@ __global__ void __launch_bounds__(256) gather_vc_kernel(GatherVCParams p) {
 
         // P2 (large faces): the whole wave probes the bbox, lane per column, rows in groups of 8;
         // won pixels join the same fragment ring
-        unsigned long long m_big = (p.dbg & 4) ? 0ull : __ballot(big && sub == 0);
+        unsigned long long m_big = __ballot(big && sub == 0);
         while (m_big) {
             const int src = __ffsll((long long)m_big) - 1;
             m_big &= m_big - 1;
@@ -504,7 +470,7 @@ __global__ void __launch_bounds__(256) gather_vc_kernel(GatherVCParams p) {
         }
 
         // P2: GLPF lanes per face (rows sub, sub + GLPF, ...), 8 probes per iteration, lock step
-        bool act = nonempty && !big && !(p.dbg & 4);
+        bool act = nonempty && !big;
         int px = bx.x0, py = bx.y0 + sub;
         act = act && py <= bx.y1;
         while (__ballot(act) != 0ull) {
@@ -552,7 +518,7 @@ __global__ void __launch_bounds__(256) gather_vc_kernel(GatherVCParams p) {
             }
         __builtin_amdgcn_wave_barrier();
     }
-    if (valid && sub == 0 && !(p.dbg & 1)) {
+    if (valid && sub == 0) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             float* o = p.grad_vcolors + ((int64_t)b * p.V + vid[k]) * 3;
@@ -619,7 +585,7 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
     bool cov = false;
 #pragma unroll
     for (int r = 0; r < SV_RPW; r++) cov = cov || fnv[r] >= 0;
-    if (!__syncthreads_or(cov) || (p.dbg & 8)) return;  // block-uniform
+    if (!__syncthreads_or(cov)) return;  // block-uniform
 
     const float* verts_b = p.verts + (int64_t)b * p.V * 3;
     const int32_t* fidx_b = p.fidx + (int64_t)b * p.F0 * 3;
@@ -665,10 +631,6 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
     if (lane == 0) wmax[wave] = mx;
     const int n2 = (p.V * 3 + 1) >> 1;
     for (int k = threadIdx.x; k < n2; k += blockDim.x) reinterpret_cast<int4*>(vtab)[k] = make_int4(0, 0, 0, 0);
-    if (p.dbg & 16) {
-        if (f[0].v[2] + f[SV_RPW - 1].v[8] == 12345.0f) p.grad_vcolors[0] = 1.0f;
-        return;
-    }
     __syncthreads();  // table zeroed, maxima visible
 
     unsigned bm = 0u;
@@ -681,7 +643,7 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
 
 #pragma unroll
     for (int r = 0; r < SV_RPW; r++) {
-        if (fnv[r] >= 0 && !(p.dbg & 2)) {
+        if (fnv[r] >= 0) {
             float tif[3];
             if (!STORED) {
                 face_inverse(f[r].v, f[r].inv, is);
@@ -719,9 +681,7 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
                 sl = sl >= 9 ? sl - 9 : sl;
                 const int k = (sl >= 3) + (sl >= 6), ch = sl - 3 * k;
                 const int cell = sel3(vid[r][0], vid[r][1], vid[r][2], texel_vertex(p.texel, k, rev_r[r])) * 3 + ch;
-                if (p.dbg & 4) {
-                    if (val[j] == 12345.0f) vtab[0] = 1;
-                } else if (finite) {
+                if (finite) {
                     const long long q = (long long)ldexp((double)val[j], shift);
                     atomicAdd(reinterpret_cast<unsigned long long*>(&vtab[cell]), (unsigned long long)q);
                 } else if (val[j] != 0.0f) {
@@ -730,7 +690,7 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
             }
         }
     }
-    if (!finite || (p.dbg & 1)) return;  // block-uniform
+    if (!finite) return;  // block-uniform
     __syncthreads();
     for (int k = threadIdx.x; k < p.V * 3; k += blockDim.x) {
         const long long t = vtab[k];
@@ -758,11 +718,11 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
 // colour-space gradient is never materialised.
 // Launch shape.  The [V, channels] fixed-point table is what limits residency (42.7 KB for a hand + object mesh with
 // three channels: 3 workgroups per compute unit, 768 for 2048 launched, i.e. three rounds of ~9 us each -- workgroup
-// timeline, scripts/bwd_timeline.py).  The flow-space gradient has two channels (the third colour plane's gradient is
+// timeline, profiles/r05_bwd_timeline_before.txt).  The flow-space gradient has two channels (the third colour plane's gradient is
 // identically zero): its table is a third smaller; and eight workgroups of EIGHT waves per image instead of sixteen of
 // four keep the 64 waves per image while halving the per-image fixed work (covered-tile list, table zeroing, flush):
 // 4 x 8 waves fit a compute unit, so all 1024 workgroups of a 128-image launch are resident at once.
-constexpr int ST_G = 8;       // workgroups per image (sp.groups; profiling: flags >> 8 bits 4-6 select 2 / 4 / 16 / 32)
+constexpr int ST_G = 8;       // workgroups per image (sp.groups)
 constexpr int ST_WAVES = 8;   // waves per workgroup
 constexpr int ST_TW = 32, ST_TH = 8;  // the forward's tile
 constexpr int ST_MAX_TILES = 4096;    // tiles per image the covered-tile list in LDS can hold (1024 x 1024 pixels)
@@ -853,16 +813,8 @@ __device__ __forceinline__ void st_load_grad(const ScatterTilesParams& sp, int b
     }
 }
 
-#ifdef MR_WG_TIMELINE
-__device__ unsigned long long mr_dbg_st[4096 * 8];  // profiling builds: phase stamps of the first 4096 workgroups
-#define MR_ST_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) mr_dbg_st[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define MR_ST_STAMP(k) do { } while (0)
-#endif
-
 template <bool FLOWGRAD, bool REC, bool PAIR, bool UNIT = false, bool WORK = false, PairCrit CRIT = PairCrit::L1>
 __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp) {
-    MR_ST_STAMP(0);
     extern __shared__ long long vtab[];  // [V * NCH] rounded up to an even count
     constexpr int NCH = FLOWGRAD ? 2 : 3;  // (the flow-space gradient has no third channel)
     __shared__ unsigned wmax[ST_WAVES];
@@ -1007,7 +959,6 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
         __syncthreads();
     }
 
-    MR_ST_STAMP(1);
     if (part * ST_WAVES >= n_hits) return;  // fewer covered tiles than waves before this workgroup: nothing to do
     const int n2 = (p.V * NCH + 1) >> 1;
     for (int k = threadIdx.x; k < n2 && !WORK; k += blockDim.x) reinterpret_cast<int4*>(vtab)[k] = make_int4(0, 0, 0, 0);
@@ -1089,14 +1040,12 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     // (WORK: the barrier behind the table zeroing waits in front of the first LDS atomic of pass 2, behind the tile's loads)
     if constexpr (UNIT) {
         if (!WORK) __syncthreads();  // table zeroed
-        MR_ST_STAMP(2);
         bm = mx;          // (the image's bound: the same in every lane of the workgroup, nothing to reduce)
     } else {
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off));
         if (lane == 0) wmax[wave] = mx;
         __syncthreads();  // table zeroed, maxima visible
-        MR_ST_STAMP(2);
 #pragma unroll
         for (int k = 0; k < ST_WAVES; k++) bm = max(bm, wmax[k]);
     }
@@ -1160,23 +1109,24 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
                 // atomics of step k below all hit the same table cell -- 65 % of this kernel's LDS-active cycles were such
                 // collisions (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r05_pmc_summary.txt), the LDS pipe the
                 // longest phase of a workgroup.  Rotated, neighbouring rows add to DIFFERENT vertices of the face in the same
-                // step (the sum does not care about the order).  SQ_LDS_BANK_CONFLICT 1.59 -> 1.27 M per launch.  dbg & 4: off.
-                if (!(p.dbg & 4)) {
-                    // (by row AND column: horizontally adjacent lanes share a face where it straddles their four-pixel groups.
-                    // 640 x 640, B = 32, warm: 43.9 us unrotated, 36.7 by row, 33.1 by row + column; at 256 x 256, one tile per
-                    // wave, the launch is not bound by its LDS pipe and does not change.  dbg & 8: by row only)
-                    const int rot = (p.dbg & 8) ? r % 3 : (r + (lane & 7)) % 3;
+                // step (the sum does not care about the order).  SQ_LDS_BANK_CONFLICT 1.59 -> 1.27 M per launch.
+                // (by row AND column: horizontally adjacent lanes share a face where it straddles their four-pixel groups.
+                // 640 x 640, B = 32, warm: 43.9 us unrotated, 36.7 by row, 33.1 by row + column; at 256 x 256, one tile per
+                // wave, the launch is not bound by its LDS pipe and does not change)
+                // (the scheduling barrier keeps the rotation from being interleaved with the loads around it: without it
+                // the unit scatter and the colour-space form need ~80 VGPRs instead of ~62, six waves per SIMD instead of eight)
+                if constexpr (UNIT || !FLOWGRAD) __builtin_amdgcn_sched_barrier(0);
+                const int rot = (r + (lane & 7)) % 3;
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const int a0 = vid[j][0], a1 = vid[j][1], a2 = vid[j][2];
-                        const float b0 = w[j][0], b1 = w[j][1], b2 = w[j][2];
-                        vid[j][0] = rot == 0 ? a0 : (rot == 1 ? a1 : a2);
-                        vid[j][1] = rot == 0 ? a1 : (rot == 1 ? a2 : a0);
-                        vid[j][2] = rot == 0 ? a2 : (rot == 1 ? a0 : a1);
-                        w[j][0] = rot == 0 ? b0 : (rot == 1 ? b1 : b2);
-                        w[j][1] = rot == 0 ? b1 : (rot == 1 ? b2 : b0);
-                        w[j][2] = rot == 0 ? b2 : (rot == 1 ? b0 : b1);
-                    }
+                for (int j = 0; j < 4; j++) {
+                    const int a0 = vid[j][0], a1 = vid[j][1], a2 = vid[j][2];
+                    const float b0 = w[j][0], b1 = w[j][1], b2 = w[j][2];
+                    vid[j][0] = rot == 0 ? a0 : (rot == 1 ? a1 : a2);
+                    vid[j][1] = rot == 0 ? a1 : (rot == 1 ? a2 : a0);
+                    vid[j][2] = rot == 0 ? a2 : (rot == 1 ? a0 : a1);
+                    w[j][0] = rot == 0 ? b0 : (rot == 1 ? b1 : b2);
+                    w[j][1] = rot == 0 ? b1 : (rot == 1 ? b2 : b0);
+                    w[j][2] = rot == 0 ? b2 : (rot == 1 ? b0 : b1);
                 }
             } else {
                 const float4 d4 = *reinterpret_cast<const float4*>(sp.depth + ((int64_t)b * is + (is - 1 - yi)) * is + x);
@@ -1256,7 +1206,6 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     }
     if (!finite) return;  // block-uniform
     __syncthreads();
-    MR_ST_STAMP(3);
     for (int k = threadIdx.x; k < p.V * NCH; k += blockDim.x) {
         const long long tsum = (long long)((unsigned long long)vtab[k] << (64 - ST_SUM_BITS - 1)) >> (64 - ST_SUM_BITS - 1);
         if (tsum != 0) {
@@ -1264,7 +1213,6 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
             if (v != 0.0f) atomicAdd(&out[(k / NCH) * 3 + k % NCH], v);
         }
     }
-    MR_ST_STAMP(4);
 }
 
 template <bool FLOWGRAD, bool REC>
@@ -1393,7 +1341,7 @@ struct PixelMapParams {
     float eps;
     int return_rgb, return_alpha;
     int write_backfacing;  // fused path: also zero the rows of culled faces
-    int dbg;               // profiling experiments (flags >> 8)
+    int count_terms;       // MR_FLAG_COUNT_PIXEL_MAP_TERMS: count the walk's terms (mr_pixel_map_terms)
     float* zero_textures;  // nullable: [B*F, 24] texture-gradient rows, zeroed for the faces that own no pixel
     int zero_owner_rows;   // compact_owners_kernel: zero the grad_faces rows of the owning faces too (kernel D by strips adds into them)
 };
@@ -1638,10 +1586,7 @@ __device__ __forceinline__ float wave_max_last(float v) {
 // the owners of ONE image and reads nothing else of a face).
 // faces per thread: 1 -- seven workgroups per image of the bench meshes instead of two; most of this kernel's time is the zero
 // rows it writes (60 MB per launch at the metric config), which 128 workgroups do not stream at the chip's rate: 17.8 -> 13.8 us
-#ifndef MR_CO_PER
-#define MR_CO_PER 1
-#endif
-constexpr int CO_TPB = 1024, CO_PER = MR_CO_PER;
+constexpr int CO_TPB = 1024, CO_PER = 1;
 __global__ void __launch_bounds__(CO_TPB) compact_owners_kernel(PixelMapParams p, const uint8_t* __restrict__ owns,
                                                                 unsigned* __restrict__ counter, uint32_t* __restrict__ list,
                                                                 unsigned* __restrict__ img_count, float4* __restrict__ img_recs,
@@ -1782,16 +1727,7 @@ __global__ void __launch_bounds__(CO_TPB) compact_owners_kernel(PixelMapParams p
 //     for the texture / depth terms of this backward pass upstream; MR_FLAG_REFERENCE_ALGO keeps the ordered walk.
 // Measured (B = 64, 256 x 256, 3076 faces, MI355X): 310 us + 21 us (owner records) + 6 us (flags), against 425 us
 // + 95 us (pack) + 15 us of the packed per-face walk; ~70 % of it is VALU issue of the 1.5 x 10^8 terms (31
-// instructions a term), the rest the per-strip phases that wait on memory.  Profiling switches (flags >> 8): 1 no
-// chunk tasks, 2 no short "in" sweeps, 4 enumeration only, 8 tasks without their steps.
-#ifdef MR_WG_TIMELINE
-__device__ unsigned long long mr_dbg_ps[8192 * 16];  // profiling builds: phase stamps and counts of the first 8192 strips
-#define MR_PS_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) mr_dbg_ps[blockIdx.x * 16 + (k)] = wall_clock64(); } while (0)
-#define MR_PS_COUNT(k, n) do { if (lane == 0) atomicAdd(&s_dbg[k], (unsigned)(n)); } while (0)
-#else
-#define MR_PS_STAMP(k) do { } while (0)
-#define MR_PS_COUNT(k, n) do { } while (0)
-#endif
+// instructions a term), the rest the per-strip phases that wait on memory.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // sum over the channels of (value - reference) * gradient: v = (alpha, r, g, b), g = their gradients (channels a launch
 // does not render are staged as zeros); two packed subtractions, a packed multiply and a packed fma
@@ -1803,7 +1739,7 @@ __device__ __forceinline__ float ps_diff_grad(const float4 v, const float4 g, co
     return d.x + d.y;
 }
 __device__ __forceinline__ float ps_bound_k(float k) { return (k == k) ? fminf(fmaxf(k, -1e15f), 1e15f) : k; }
-// Terms of the walk (profiling switch flags >> 8 & 1024; read back by mr_pixel_map_terms): one term = one evaluation of upstream's
+// Terms of the walk (MR_FLAG_COUNT_PIXEL_MAP_TERMS; read back by mr_pixel_map_terms): one term = one evaluation of upstream's
 // sweep body (rasterize.py:269-281 -> backward_pixel_map: every position of an "out" sweep, every position of an "in" sweep whose
 // pixel belongs to the face) -- the unit bench.py's `d_e_f.frac_of_algorithmic_issue` prices at 10 lane-instructions.
 __device__ unsigned long long mr_pixel_map_terms_counter;
@@ -1834,7 +1770,7 @@ static int64_t strip_lds_bytes(int is, int L) {
 // strip kernel takes workgroup i = entry i / 8 of XCD i % 8: no workgroup for the 57 % of the strips outside their image's
 // line range (each used to hold one of the chip's 768 slots for a microsecond or two), and the strips through the middle
 // of the meshes (up to 100 us each) start first instead of wherever the image order put them (workgroup timeline,
-// scripts/dstrip_timeline.py: last start 265 us into a 315 us launch, 650-700 working strips resident of 768).
+// profiles/r03_kernel_d.txt: last start 265 us into a 315 us launch, 650-700 working strips resident of 768).
 constexpr int SL_T = 1024;
 __global__ void __launch_bounds__(SL_T) strip_list_kernel(const unsigned* __restrict__ strip_w, unsigned* __restrict__ lists,
                                                           unsigned* __restrict__ counts, int B, int S, int cap) {
@@ -1875,11 +1811,6 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                                            const unsigned* __restrict__ strip_counts, int list_cap, const unsigned vbid) {
     extern __shared__ float4 ps_lds[];
     __shared__ unsigned s_qn, s_next;
-#ifdef MR_WG_TIMELINE
-    __shared__ unsigned s_dbg[12];
-    if (threadIdx.x < 12) s_dbg[threadIdx.x] = 0u;
-#endif
-    MR_PS_STAMP(0);
     constexpr int ENT = MR_WAVE / L;  // entries per batch of a wave
     const int is = p.is, stride = is + 1;  // (+1: the L lines of a staging store fall into different banks)
     float4* recA = ps_lds;                 // [L][stride]  alpha, r, g, b
@@ -1948,7 +1879,6 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
             if (lane == 0) base = atomicAdd(&s_next, (unsigned)ENT);
             base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
             if (base >= qn) break;
-            MR_PS_COUNT(3, 1);
             const unsigned ei = base + (unsigned)(lane / L);
             const int loff = lane % L;
             const bool have = ei < qn;
@@ -1995,7 +1925,7 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
             const bool long_in = valid && (in_to - in_from) >= PM_LONG;
 
             float g0 = 0.0f, g1 = 0.0f;  // short "in" sweep: the lane walks its own item
-            if (valid && !long_in && !(p.dbg & 2)) {
+            if (valid && !long_in) {
                 for (int d1 = in_from; d1 <= in_to; d1++) {
                     if (fimL[line * stride + d1] != fn) continue;
                     const float dg = ps_diff_grad(recA[line * stride + d1], recB[line * stride + d1],
@@ -2005,7 +1935,7 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                     if (use1) g1 -= pm_term(dg, c1, (float)d1, d1_cross, two_over_is, p.eps);
                 }
             }
-            if (p.dbg & 1024) {  // (profiling: the terms of the short "in" sweeps)
+            if (p.count_terms) {  // (the terms of the short "in" sweeps)
                 int nt = 0;
                 if (valid && !long_in)
                     for (int d1 = in_from; d1 <= in_to; d1++) nt += fimL[line * stride + d1] == fn ? 1 : 0;
@@ -2030,7 +1960,7 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                 const int n = want ? span / CH + 1 : 0;
                 const int incl = (int)wave_sum_last((float)n);  // (inclusive scan; exact: at most 1024)
                 const int total = __builtin_amdgcn_readlane(incl, 63);
-                if (total == 0 || (p.dbg & 1)) continue;
+                if (total == 0) continue;
                 for (int c = 0; c < n; c++) tasks[incl - n + c] = (uint16_t)(lane | (c << 6));
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll 1
@@ -2053,9 +1983,7 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                     const int base = t_line * stride + from;
                     const int rot = (lane - base) & 15;
                     const int t_fn = __shfl(fn, src);
-                    MR_PS_COUNT(1, 1);
-                    MR_PS_COUNT(2, cnt);
-                    if (p.dbg & 1024) {  // (profiling: "out" sweeps count every position, long "in" sweeps the face's own pixels)
+                    if (p.count_terms) {  // ("out" sweeps count every position, long "in" sweeps the face's own pixels)
                         int nt = kind == 0 ? cnt : 0;
                         if (kind == 1)
                             for (int q_ = 0; q_ < cnt; q_++) nt += fimL[base + q_] == t_fn ? 1 : 0;
@@ -2107,7 +2035,7 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                         Quad x, y;
                         request(x, 0);
 #pragma unroll 1
-                        for (int it0 = 0; it0 < ((p.dbg & 8) ? 0 : CH); it0 += 2 * PG) {
+                        for (int it0 = 0; it0 < CH; it0 += 2 * PG) {
                             request(y, it0 + PG);
                             work(x);
                             request(x, it0 + 2 * PG);  // (behind the last step: positions wrap inside the chunk, the values are not used)
@@ -2134,7 +2062,7 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                         Quad x, y;
                         request(x, 0);
 #pragma unroll 1
-                        for (int it0 = 0; it0 < ((p.dbg & 8) ? 0 : CH); it0 += 2 * PG) {
+                        for (int it0 = 0; it0 < CH; it0 += 2 * PG) {
                             request(y, it0 + PG);
                             work(x);
                             request(x, it0 + 2 * PG);  // (behind the last step: positions wrap inside the chunk, the values are not used)
@@ -2147,30 +2075,23 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
                     // two LDS float atomics per round; ds_add_f32 costs ~12 cycles PER ACTIVE LANE on gfx950 -- 770 cycles for
                     // a full wave whatever the addresses, 30 x a ds_add_u64, profiles/r05_valu_rate_probe.txt -- i.e. as much
                     // as the sixteen terms of the chunks themselves.)
-                    if (p.dbg & 16) {
-                        if (mine) {
-                            if (t_use0 && ww.x != 0.0f) unsafeAtomicAdd(&acc[src].x, ww.x);
-                            if (t_use1 && ww.y != 0.0f) unsafeAtomicAdd(&acc[src].y, ww.y);
-                        }
-                    } else {
-                        float sx = (mine && t_use0) ? ww.x : 0.0f, sy = (mine && t_use1) ? ww.y : 0.0f;
-                        const int seg = mine ? src : -1 - lane;
+                    float sx = (mine && t_use0) ? ww.x : 0.0f, sy = (mine && t_use1) ? ww.y : 0.0f;
+                    const int seg = mine ? src : -1 - lane;
 #pragma unroll
-                        for (int off = 1; off < 16; off <<= 1) {
-                            // (every shuffle in full-wave control flow: a lane that is masked off hands out zeros)
-                            const float ox = __shfl_down(sx, off), oy = __shfl_down(sy, off);
-                            const int os = __shfl_down(seg, off);
-                            const bool same = lane + off < MR_WAVE && os == seg;
-                            sx += same ? ox : 0.0f;
-                            sy += same ? oy : 0.0f;
-                        }
-                        const int prev = __shfl_up(seg, 1);
-                        const bool head = mine && (lane == 0 || prev != seg);
-                        if (head && (sx != 0.0f || sy != 0.0f)) {
-                            float2 a = acc[src];
-                            a.x += sx; a.y += sy;
-                            acc[src] = a;
-                        }
+                    for (int off = 1; off < 16; off <<= 1) {
+                        // (every shuffle in full-wave control flow: a lane that is masked off hands out zeros)
+                        const float ox = __shfl_down(sx, off), oy = __shfl_down(sy, off);
+                        const int os = __shfl_down(seg, off);
+                        const bool same = lane + off < MR_WAVE && os == seg;
+                        sx += same ? ox : 0.0f;
+                        sy += same ? oy : 0.0f;
+                    }
+                    const int prev = __shfl_up(seg, 1);
+                    const bool head = mine && (lane == 0 || prev != seg);
+                    if (head && (sx != 0.0f || sy != 0.0f)) {
+                        float2 a = acc[src];
+                        a.x += sx; a.y += sy;
+                        acc[src] = a;
                     }
                 }
                 __builtin_amdgcn_wave_barrier();  // (the next kind / batch overwrites the task list)
@@ -2202,7 +2123,6 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
     }
     stage_strip();
     __syncthreads();
-    MR_PS_STAMP(1);
     for (unsigned k0 = 0, j = 0; k0 < n_own; k0 += PS_T, j++) {
         const unsigned k = k0 + tid;
         float4 v01, v2n;
@@ -2238,18 +2158,12 @@ __device__ __forceinline__ void strip_body(const PixelMapParams& p, const unsign
         __syncthreads();
         const unsigned qn = s_qn;
         if (qn + 3u * PS_T > (unsigned)PS_QCAP || k0 + PS_T >= n_own) {
-            MR_PS_STAMP(2);
-            MR_PS_COUNT(0, tid == 0 ? qn : 0);
-            if (qn && !(p.dbg & 4)) process(qn);
+            if (qn) process(qn);
             __syncthreads();
             if (tid == 0) { s_qn = 0u; s_next = 0u; }
             __syncthreads();
         }
     }
-    MR_PS_STAMP(3);
-#ifdef MR_WG_TIMELINE
-    if (tid < 12 && blockIdx.x < 8192) mr_dbg_ps[blockIdx.x * 16 + 4 + tid] = s_dbg[tid];
-#endif
 }
 
 template <bool IMG, int L>
@@ -2274,19 +2188,11 @@ __global__ void __launch_bounds__(PS_T) strip_gather_kernel(PixelMapParams p, co
                                                             const float4* __restrict__ img_recs, int strips_axis,
                                                             const unsigned* __restrict__ strip_lists,
                                                             const unsigned* __restrict__ strip_counts, int list_cap,
-                                                            GatherParams g, unsigned gather_groups, unsigned strip_groups) {
+                                                            GatherParams g, unsigned gather_groups) {
     const unsigned grp = blockIdx.x >> 3, r = blockIdx.x & 7u;
-    bool gather;
-    unsigned vg;
-    if (p.dbg & 256) {         // (profiling: the two grids alternate group by group while both last)
-        const unsigned pairs = min(gather_groups, strip_groups);
-        if (grp < 2u * pairs) { gather = (grp & 1u) != 0u; vg = grp >> 1; }
-        else { gather = gather_groups > strip_groups; vg = pairs + (grp - 2u * pairs); }
-    } else if (p.dbg & 512) {  // (profiling: the strips first)
-        gather = grp >= strip_groups; vg = gather ? grp - strip_groups : grp;
-    } else {                   // the gather's workgroups first: short, and its few long ones (faces with large boxes) start early
-        gather = grp < gather_groups; vg = gather ? grp : grp - gather_groups;
-    }
+    // the gather's workgroups first: short, and its few long ones (faces with large boxes) start early
+    const bool gather = grp < gather_groups;
+    const unsigned vg = gather ? grp : grp - gather_groups;
     if (gather) gather_body<IMG, TEX, DEPTH>(g, vg * 8u + r, gather_groups * 8u);
     else strip_body<IMG, L>(p, img_count, img_recs, strips_axis, strip_lists, strip_counts, list_cap, vg * 8u + r);
 }
@@ -2424,8 +2330,7 @@ static int launch_pixel_map(const PixelMapParams& p, void* workspace, int64_t wo
 #define MR_SG_LAUNCH(L_, T_, D_)                                                                                          \
             hipLaunchKernelGGL((strip_gather_kernel<IMG, L_, T_, D_>), dim3((unsigned)total), dim3(PS_T), lds, s, p,      \
                                (const unsigned*)ol0.img_count, (const float4*)ol0.img_recs, strips_axis,                  \
-                               (const unsigned*)sl.lists, (const unsigned*)sl.counts, sl.cap, g, (unsigned)ggroups,       \
-                               (unsigned)sl.cap)
+                               (const unsigned*)sl.lists, (const unsigned*)sl.counts, sl.cap, g, (unsigned)ggroups)
 #define MR_SG_PICK(L_)                                                                                                    \
             do {                                                                                                          \
                 if (fused->tex && fused->depth) MR_SG_LAUNCH(L_, true, true);                                             \
@@ -2558,7 +2463,6 @@ extern "C" int mr_render_backward(const float* faces, const float* textures,
     g.grad_textures = gather_tex ? grad_textures : nullptr;
     g.B = batch_size; g.F = num_faces; g.is = image_size; g.eps = eps;
     g.accumulate_faces = want_d ? 1 : 0;
-    g.dbg_rows = ((flags >> 8) & 32 ? 1 : 0) | ((flags >> 8) & 64 ? 2 : 0);
     if (use_list) {
         const OwnerList ol = owner_list(workspace, batch_size, num_faces);
         g.owners = ol.list; g.n_owners = ol.counter;
@@ -2574,12 +2478,12 @@ extern "C" int mr_render_backward(const float* faces, const float* textures,
     if (want_d) {
         const int rr = return_rgb && grad_rgb_img && rgb_img, ra = return_alpha && grad_alpha_img && alpha_img;
         PixelMapParams p{faces, face_index_map, rgb_img, alpha_img, grad_rgb_img, grad_alpha_img,
-                         grad_faces, batch_size, num_faces, image_size, eps, rr, ra, 1, flags >> 8};
+                         grad_faces, batch_size, num_faces, image_size, eps, rr, ra, 1, (flags & MR_FLAG_COUNT_PIXEL_MAP_TERMS) ? 1 : 0};
         p.zero_textures = (use_list && run_gather && gather_tex) ? grad_textures : nullptr;
         // Round 5: kernel D's walk and the E / F gather go out as ONE launch when both run over the owner lists
-        // (strip_gather_kernel; profiling switch flags >> 8 & 128: two launches, one behind the other, as before)
+        // (strip_gather_kernel)
         FusedGather fg{g, gather_tex, want_f, gather_threads};
-        const bool fuse = use_list && strips_d && run_gather && (gather_tex || want_f) && !((flags >> 8) & 128);
+        const bool fuse = use_list && strips_d && run_gather && (gather_tex || want_f);
         rc = launch_pixel_map<true>(p, workspace, workspace_bytes, flags, s, fuse ? &fg : nullptr, &gathered);
         if (rc != MR_OK) return rc;
     } else if (use_list && run_gather) {
@@ -2622,14 +2526,14 @@ extern "C" int mr_render_vc_backward(const float* verts, const int32_t* faces_id
     if (num_faces == 0) return MR_OK;
     if (!verts || !faces_idx || !face_index_map || !grad_rgb_img || !(eps >= 1e-6f)) return MR_ERR_BADARG;
     GatherVCParams g{verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces,
-                     fill_back, image_size, eps, flags >> 8, texel_layout};
-    // pixel-parallel scatter when the per-image colour table fits LDS (dbg bit 32 forces the gather)
+                     fill_back, image_size, eps, texel_layout};
+    // pixel-parallel scatter when the per-image colour table fits LDS (MR_FLAG_FORCE_GATHER: the gather)
     const int64_t table_bytes = (((int64_t)num_verts * 3 + 1) / 2) * 16;
-    if (table_bytes <= SV_MAX_TABLE_BYTES && !(g.dbg & 32)) {
+    if (table_bytes <= SV_MAX_TABLE_BYTES && !(flags & MR_FLAG_FORCE_GATHER)) {
         ScatterVCParams sp{g, weight_map, depth_img, (image_size + SV_W - 1) / SV_W, (image_size + SV_H - 1) / SV_H};
         const int64_t blocks = (int64_t)batch_size * sp.rx_n * sp.ry_n;
         if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-        const bool stored = weight_map && depth_img && !(g.dbg & 64);
+        const bool stored = weight_map && depth_img;
         hipLaunchKernelGGL(stored ? scatter_vc_kernel<true> : scatter_vc_kernel<false>, dim3((unsigned)blocks),
                            dim3(SV_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
         MR_CHECK_LAUNCH();
@@ -2669,14 +2573,13 @@ extern "C" int mr_render_flow_backward(const float* verts, const int32_t* faces_
         return MR_ERR_NOTIMPL;
     ScatterTilesParams sp{};
     sp.g = GatherVCParams{verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces,
-                          fill_back, image_size, eps, flags >> 8, texel_layout};
+                          fill_back, image_size, eps, texel_layout};
     sp.weight = weight_map; sp.depth = depth_img; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.grad_flow = grad_flow; sp.m_pre = mask_pre; sp.m_x_lo = mask_x_lo; sp.m_x_hi = mask_x_hi; sp.occl = occl;
     sp.split = split; sp.H = height; sp.W = width;
     sp.tiles_x = (image_size + ST_TW - 1) / ST_TW; sp.tiles_y = (image_size + ST_TH - 1) / ST_TH;
     sp.grad_bound = flowgrad ? grad_bound : nullptr;
     sp.groups = ST_G;
-    switch ((flags >> 12) & 7) { case 1: sp.groups = 2; break; case 2: sp.groups = 4; break; case 3: sp.groups = 16; break; case 4: sp.groups = 32; break; default: break; }
     const int64_t blocks = (int64_t)batch_size * sp.groups;
     if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
     auto kernel = vertex_id_map ? (flowgrad ? scatter_tiles_kernel<true, true> : scatter_tiles_kernel<false, true>)
@@ -2719,7 +2622,7 @@ extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, c
         return MR_ERR_NOTIMPL;
     ScatterTilesParams sp{};
     sp.g = GatherVCParams{nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces,
-                          fill_back, image_size, eps, flags >> 8, texel_layout};
+                          fill_back, image_size, eps, texel_layout};
     sp.weight = weight_map; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.m_pre = mask_pre; sp.m_x_lo = mask_x_lo; sp.m_x_hi = mask_x_hi; sp.occl = occl;
     sp.split = batch_size / 2; sp.H = height; sp.W = width;
@@ -2729,7 +2632,6 @@ extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, c
     // ~8 tiles each (a 480 x 480 pair at B = 8: 73 -> 46 us with 32 instead of 8)
     sp.groups = ST_G;
     while (sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
-    switch ((flags >> 12) & 7) { case 1: sp.groups = 2; break; case 2: sp.groups = 4; break; case 3: sp.groups = 16; break; case 4: sp.groups = 32; break; case 5: sp.groups = 8; break; default: break; }
     sp.stash = grad_flow_scratch; sp.flow = flows; sp.image_ref = image_ref; sp.image = image; sp.jitter_ref = jitter_ref;
     sp.jitter = jitter; sp.Cj = jitter_channels; sp.sums = sums; sp.gl_fwd = grad_loss_fwd; sp.gl_bwd = grad_loss_bwd;
     sp.pair_thresh = pair_thresh;
@@ -2787,7 +2689,7 @@ int mr_flow_pair_backward_unit_tiles_ex(const int32_t* face_index_map, const uin
         return MR_ERR_NOTIMPL;
     ScatterTilesParams sp{};
     sp.g = GatherVCParams{nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces,
-                          fill_back, image_size, eps, flags >> 8, texel_layout};
+                          fill_back, image_size, eps, texel_layout};
     sp.weight = weight_map; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.split = batch_size / 2; sp.H = height; sp.W = width;
     sp.tiles_x = (image_size + ST_TW - 1) / ST_TW; sp.tiles_y = (image_size + ST_TH - 1) / ST_TH;
@@ -2795,13 +2697,12 @@ int mr_flow_pair_backward_unit_tiles_ex(const int32_t* face_index_map, const uin
     // 256 / 900 / 1600 tiles): 8 / 32 / 32 -- a 480 x 480 pair at B = 8: 30 -> 19 us, 640 x 640 at B = 32: 86 -> 74 us cold
     sp.groups = ST_G;
     while (sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
-    switch ((flags >> 12) & 7) { case 1: sp.groups = 2; break; case 2: sp.groups = 4; break; case 3: sp.groups = 16; break; case 4: sp.groups = 32; break; case 5: sp.groups = 8; break; default: break; }
     sp.unit_grad = unit_grad; sp.unit_max = unit_grad_max; sp.sums = sums; sp.gl_fwd = grad_loss_fwd; sp.gl_bwd = grad_loss_bwd;
     sp.gl_sum = grad_loss_sum; sp.gl_mean = grad_mean; sp.mean_div = (float)(batch_size / 2); sp.mean_of = mean_of;
     const int64_t blocks = (int64_t)batch_size * sp.groups;
     if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-    // (the covered-tile lists need the workgroup split's head room: grid > images; profiling bit 15 of flags: the listing form)
-    if (scatter_work && sp.groups >= 2 && !(flags & (1 << 15))) {
+    // (the covered-tile lists need the workgroup split's head room: grid > images)
+    if (scatter_work && sp.groups >= 2) {
         sp.work = scatter_work_at(const_cast<void*>(scatter_work), batch_size);
         hipLaunchKernelGGL(unit_scatter_tiles_kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
     } else {
@@ -2840,12 +2741,3 @@ extern "C" int mr_pixel_map_terms(uint64_t* terms_host, int reset) {
     }
     return MR_OK;
 }
-
-#ifdef MR_WG_TIMELINE
-extern "C" __attribute__((visibility("default"))) int mr_debug_ps_times(void* dst, long n) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mr::mr_dbg_ps), n, 0, hipMemcpyDeviceToHost);
-}
-extern "C" __attribute__((visibility("default"))) int mr_debug_st_times(void* dst, long n) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mr::mr_dbg_st), n, 0, hipMemcpyDeviceToHost);
-}
-#endif

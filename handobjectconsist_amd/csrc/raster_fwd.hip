@@ -144,7 +144,6 @@ struct BinParams {
     int V, F0, F, fill_back, is;
     int nbx, nby, ysh;       // bins per row / column; a bin is TILE_W x (TILE_H << ysh) pixels
     int lds_boxes;           // bin_boxes_kernel keeps the image's boxes in LDS between its two passes
-    int dbg;                 // profiling experiments (scripts/fwd_vc_variants.py)
     // compacted list of the tiles with candidate records (sparse-tile launches; nullptr = none is built)
     TileList* tlist;         // counter, zeroed by face_records_kernel, bumped once per image by bin_boxes_kernel
     int64_t tile_cap;        // B * tiles: the list's heavy part starts at entry 0, its light part at entry tile_cap
@@ -209,7 +208,7 @@ __global__ void __launch_bounds__(256) face_records_kernel(BinParams p) {
         box_b[f0 + p.F0] = b1;
         live = live || b1.x0 <= b1.x1;
     }
-    if (VC && live && !(p.dbg & 16)) {
+    if (VC && live) {
         float4* rv = reinterpret_cast<float4*>(p.rverts + (int64_t)b * p.F0 + f0);
         rv[0] = make_float4(f[0], f[1], f[2], f[3]);
         rv[1] = make_float4(f[4], f[5], f[6], f[7]);
@@ -224,14 +223,7 @@ __global__ void __launch_bounds__(256) face_records_kernel(BinParams p) {
 // (Measured and dropped, each SLOWER than the plain per-lane LDS atomics below -- the kernel is bound by the
 // length of each wave's dependent instruction chain, not by LDS conflicts: combining the lanes that hit one bin
 // with a ballot loop, folding runs of equal neighbours into one atomic, prefetching 8 iterations of boxes.)
-#ifdef MR_WG_TIMELINE
-__device__ unsigned long long mr_dbg_bin[1024 * 8];  // profiling builds: phase stamps of the binning pass per image
-#define MR_BIN_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 1024) mr_dbg_bin[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define MR_BIN_STAMP(k) do { } while (0)
-#endif
-
-// Where its time goes (scripts/wg_timeline.py on a -DMR_WG_TIMELINE build, 7104 virtual faces, 1024 bins): 10 us inside the
+// Where its time goes (phase stamps of an instrumented build, profiles/: 7104 virtual faces, 1024 bins): 10 us inside the
 // kernel per image -- counting pass 4.1 (of which the boxes' load round trip ~1.5), scan + headers 1.6, fill pass 3.9
 // -- + ~3 us of launch and ~2 us between the first image's start and the last one's end.  Measured WITHOUT effect on
 // those numbers, and not kept: walking the faces in a strided order so that a wave's lanes land in different bins,
@@ -276,7 +268,6 @@ template <bool RECORDS, bool PROLOGUE, int PHASE = 0>
 __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPrologue& pro) {
     static_assert(RECORDS || !PROLOGUE, "the prologue feeds the per-face pass");
     static_assert(PHASE == 0 || !PROLOGUE || PHASE == 1, "the fill launch has no vertex stage");
-    MR_BIN_STAMP(0);
     extern __shared__ int bin_smem[];
     __shared__ int s_large, s_nlarge, s_lbase, s_hbase, s_bbase, s_everywhere, s_last;
     // listed launches: bit 30 of a bin's counter = "a face of the image's large list overlaps this bin" (counts stay far below)
@@ -312,7 +303,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
     for (int i = tid; i < nbins; i += BIN_TPB) cnt[i] = 0;
     if (tid == 0) { s_large = 0; s_nlarge = 0; s_everywhere = 0; s_last = 1; }
     __syncthreads();
-    MR_BIN_STAMP(1);
 
     if constexpr (RECORDS && PHASE != 2) {
         // the per-face pass (face_records_kernel<true>'s arithmetic): indices of REC_PF faces per thread requested together,
@@ -438,7 +428,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
         }
     }
     __syncthreads();
-    MR_BIN_STAMP(2);
 
     const int per = (nbins + BIN_TPB - 1) / BIN_TPB;
     const int i0 = min(tid * per, nbins), i1 = min(i0 + per, nbins);
@@ -516,7 +505,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
                                    __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        MR_BIN_STAMP(6);
         if (tid == 0) {
             unsigned* arr = p.arrive + (int64_t)b * ARRIVE_STRIDE;
             const unsigned old = __hip_atomic_fetch_add(arr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -525,7 +513,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
         }
         __syncthreads();
         if (!s_last) return;
-        MR_BIN_STAMP(7);
         const int* all = p.part_cnt + (int64_t)b * K * pstride;
         for (int i = i0; i < i1; i++) {
             int raw[MAX_PARTS_DEV];  // (all parts' counters of the bin in flight together)
@@ -587,7 +574,7 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
     int base = (int)(unsigned)(base64 & 0xffffffffull);
     // The image's places in the launch's tile list: three device-scope atomics whose results are needed only when the entries are
     // written -- BEHIND the fill pass (round 6: the ~2 us memory-side round trip used to sit between the scan and the fill, with
-    // the whole workgroup waiting at the barrier behind it; scripts/pair_bin_timeline.py).  The results stay in thread 0's
+    // the whole workgroup waiting at the barrier behind it; profiles/r06_pair_binning_timeline.txt).  The results stay in thread 0's
     // registers until then.
     int got_h = 0, got_l = 0, got_b = 0;
     if (p.tlist && lead && tid == 0) {
@@ -615,7 +602,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
         lgbits |= (lg ? 1u : 0u) << (i - i0);
     }
     __syncthreads();
-    MR_BIN_STAMP(3);
     auto write_tile_list = [&]() __attribute__((always_inline)) {
         if (!(p.tlist && lead)) return;  // (uniform)
         // the image's tiles with candidates go to the launch's tile list (a bin IS a tile here: ysh == 0), the
@@ -639,12 +625,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
             else hit32[i] = 0u;
         }
     };
-    MR_BIN_STAMP(4);
-    if (p.dbg & 2) {  // (profiling: the binning pass without its fill)
-        write_tile_list();
-        return;
-    }
-
     // pass 2: fill
     FaceRec* recs_b = p.recs + (int64_t)b * REC_CAP * p.F;
     FaceRec* large_b = recs_b + (int64_t)SMALL_MAX_BINS * p.F;
@@ -682,7 +662,7 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
     } else if (K > 1) {
         // the last arriver fills for the whole image, from the boxes all parts left in global memory (FILL_PF trips requested
         // together: a hand + object mesh's 7104 boxes in ONE memory-side round trip -- two of ~2 us each with four per thread,
-        // scripts/pair_bin_timeline.py)
+        // profiles/r06_pair_binning_timeline.txt)
         constexpr int FILL_PF = 8;
         for (int base = 0; base < p.F; base += FILL_PF * BIN_TPB) {
             FaceBox bxs[FILL_PF];
@@ -703,7 +683,6 @@ __device__ __forceinline__ void bin_boxes_body(const BinParams& p, const PairPro
     } else {
         for (int j = tid; j < nv; j += BIN_TPB) fill_face(fn_of(j), box_b[fn_of(j)]);
     }
-    MR_BIN_STAMP(5);
     write_tile_list();
     if (lead && tid == 0) {
         ImageHdr h;
@@ -770,7 +749,7 @@ struct FwdParams {
     float near_, far_, eps;
     int tiles_x, tiles_y;  // tiles per row / per column
     const unsigned long long* keys;  // validation only: precomputed z-buffer keys (skip the scan)
-    int dbg;                         // profiling experiments (flags >> 8)
+    int plain_div;                   // VC: plain divisions everywhere (MR_FLAG_PLAIN_DIVISIONS, the shared-reciprocal path's reference)
     // listed launches (sparse tiles): the binning pass's list of tiles with candidates
     const TileList* tlist;
     const uint4* tile_ids;           // heavy entries [0, n_heavy), light entries [tile_cap, tile_cap + n_light)
@@ -804,7 +783,7 @@ __device__ __forceinline__ bool load_face_coords(const FwdParams& p, const RecVe
         v[0] = rev ? v1.z : v0.x; v[1] = rev ? v1.w : v0.y; v[2] = rev ? v2.x : v0.z;
         v[3] = v0.w; v[4] = v1.x; v[5] = v1.y;
         v[6] = rev ? v0.x : v1.z; v[7] = rev ? v0.y : v1.w; v[8] = rev ? v0.z : v2.x;
-        return v2.y != 0.0f && !(p.dbg & 4096);  // division-safe (dbg 4096: plain divisions everywhere, for the A/B test)
+        return v2.y != 0.0f && !p.plain_div;  // division-safe
     }
 }
 
@@ -835,12 +814,6 @@ __device__ __forceinline__ void zbuf_min(unsigned long long* zb, int idx, float 
 
 // FUSED = true : write every pixel of every requested plane (fused epilogue).
 // FUSED = false: upstream-compatible forward_face_index_map: touch hit pixels only.
-#ifdef MR_WG_TIMELINE
-// profiling builds (scripts/wg_timeline.py): per tile with geometry, start / end of its S1-S3 phase on the 100 MHz
-// wall clock, candidate count, the compute unit it ran on and its workgroup
-__device__ unsigned long long mr_dbg_times[65536 * 4];
-#endif
-
 // A tile no face can touch is pure background: every requested plane streamed with 16-byte stores (full tiles of rasters
 // whose side is a multiple of 4; one 128-B row segment = 8 float4 of a scalar plane / 24 float4 of weight_map).
 __device__ __forceinline__ void stream_background_tile(const FwdParams& p, int b, int t, int tx0, int ty0) {
@@ -879,9 +852,6 @@ __device__ __forceinline__ void stream_background_tile(const FwdParams& p, int b
 // `ent` (listed launches): the tile's list entry {lid, record offset, record count, large-list length}; else nullptr
 template <bool FUSED, bool VC>
 __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsigned lid, const uint4* ent = nullptr) {
-#ifdef MR_WG_TIMELINE
-    const unsigned long long dbg_t0 = wall_clock64();
-#endif
     __shared__ unsigned long long zbuf[TILE_W * TILE_H];
     __shared__ float fcache[TPB / MR_WAVE][NB * FC_STRIDE];
     __shared__ unsigned short fragq[TPB / MR_WAVE][FQCAP];  // slot << 8 | row << 5 | x
@@ -916,8 +886,6 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
             n_rec = n_bin + p.hdrs[b].n_large;
         }
         off_large = (int64_t)SMALL_MAX_BINS * p.F - n_bin;  // so that record i >= n_bin sits at off_large + i
-        if (p.dbg & 1) n_rec = 0;
-        if (n_rec == 0 && (p.dbg & 256)) return;
         if (FUSED && n_rec == 0 && p.sparse_tiles) {
             if (tid == 0) reinterpret_cast<uint32_t*>(p.tile_hit)[(int64_t)b * tiles_per_img + t] = 0u;
             return;
@@ -928,16 +896,6 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
         }
     }
 
-#ifdef MR_WG_TIMELINE
-    if (threadIdx.x == 0 && lid < 65536u) {
-        unsigned hwid, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        mr_dbg_times[lid * 4 + 0] = dbg_t0;
-        mr_dbg_times[lid * 4 + 2] = ((unsigned long long)n_rec << 32) | (xcc << 24) | (hwid & 0xffffffu);
-        mr_dbg_times[lid * 4 + 3] = blockIdx.x;
-    }
-#endif
     zbuf[tid] = ~0ull;
     // NDC coordinates of the tile's pixel centres (upstream: (2 * i + 1 - is) / is)
     if (tid < TILE_W) xp_tab[tid] = (float)(2 * (tx0 + tid) + 1 - is) / fis;
@@ -955,7 +913,7 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
     // S3: one lane per fragment -- barycentrics, near/far, depth test
     int fqh = 0, fqn = 0;  // fragment ring (wave-uniform)
     auto shade = [&](int n) {
-        if (lane < n && !(p.dbg & 16)) {
+        if (lane < n) {
             const unsigned fr = fq[(fqh + lane) & (FQCAP - 1)];
             const float* c = fc + (fr >> 8) * FC_STRIDE;
             const int lx = (int)(fr & 31u), ly = (int)((fr >> 5) & 7u);
@@ -978,7 +936,7 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
     auto process_batch = [&](int first, int count) {
         // S1: one lane per record
         int nrows = 0, row0 = 0;  // rows of the face's bbox inside this tile, the first of them
-        if (lane < count && !(p.dbg & 4)) {
+        if (lane < count) {
             const FaceRec r = *rec_at(first + lane);
             const int fn = (int)r.z;
             Face f;
@@ -1008,7 +966,6 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
         for (int r_ = 0; r_ < nrows; r_++) itab[incl - nrows + r_] = (unsigned char)(lane | ((row0 + r_) << 5));
         const int n_items = __builtin_amdgcn_readlane(incl, NB - 1);
         __builtin_amdgcn_wave_barrier();
-        if (p.dbg & (4 | 8)) return;
         // S2: one lane per (face, bbox row) item, 64 items per pass.  Along a row each edge test
         //   reject_k(x) = ey_k < (xp[x] - a_k) * dy_k
         // is monotone in x even in floating point (xp[x] increases with x; IEEE subtraction and
@@ -1064,7 +1021,7 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
                 open_any = open_any || (t0 ? (t1 && c + 1 < lx1) : c > lx0);
                 cc[k] = c; tt[k] = (t0 ? 1 : 0) | (t1 ? 2 : 0);
             }
-            if (!(p.dbg & 32) && __ballot(act && open_any) != 0ull) {
+            if (__ballot(act && open_any) != 0ull) {
 #pragma unroll
                 for (int k = 0; k < 3; k++) {
                     const bool t0 = tt[k] & 1, t1 = tt[k] & 2;
@@ -1091,7 +1048,7 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
             for (int k = 0; k < 3; k++) {
                 if (dec[k]) lo = max(lo, l[k] + 1); else hi = min(hi, l[k]);
             }
-            int len = (act && !(p.dbg & 64)) ? max(hi - lo + 1, 0) : 0;
+            int len = act ? max(hi - lo + 1, 0) : 0;
             int x = lo;
             // emit the spans as fragments, at most EMIT pixels per lane per round: a wave prefix sum gives every
             // lane its place in the ring
@@ -1130,10 +1087,6 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
     if (p.keys && tx0 + lxr < is && ty0 + ly < is) zbuf[tid] = p.keys[((int64_t)b * is + ty0 + ly) * is + tx0 + lxr];
     __syncthreads();
 
-#ifdef MR_WG_TIMELINE
-    if (threadIdx.x == 0 && lid < 65536u) mr_dbg_times[lid * 4 + 1] = wall_clock64();
-#endif
-    if (p.dbg & 2) return;
     // resolve: one pixel per thread (x = tid % 32, y = tid / 32)
     {
         const unsigned long long key = zbuf[tid];
@@ -1173,27 +1126,21 @@ __device__ __forceinline__ void raster_one_tile(const FwdParams& p, const unsign
         // compacted before the expensive part -- the winner's set-up, barycentrics and sampling, ~180 instructions --
         // so that it runs in ceil(covered / 64) waves instead of in every wave that owns a covered pixel.  The list
         // lives in the (now idle) fragment ring of wave 0, the per-wave counts in its row-offset table.
-        int q = tid;
-        bool active = hitpx;
-        if (!(p.dbg & 8192)) {
-            unsigned short* hlist = fragq[0];
-            int* hcnt = hitcnt;
-            const unsigned long long m = __ballot(hitpx);
-            if (lane == 0) hcnt[wave] = __popcll(m);
-            __syncthreads();
-            int hbase = 0, htotal = 0;
+        unsigned short* hlist = fragq[0];
+        const unsigned long long m = __ballot(hitpx);
+        if (lane == 0) hitcnt[wave] = __popcll(m);
+        __syncthreads();
+        int hbase = 0, htotal = 0;
 #pragma unroll
-            for (int w = 0; w < TPB / MR_WAVE; w++) {
-                const int c = hcnt[w];
-                hbase += w < wave ? c : 0;
-                htotal += c;
-            }
-            if (hitpx) hlist[hbase + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)tid;
-            __syncthreads();
-            active = tid < htotal;
-            q = active ? (int)hlist[tid] : tid;
+        for (int w = 0; w < TPB / MR_WAVE; w++) {
+            const int c = hitcnt[w];
+            hbase += w < wave ? c : 0;
+            htotal += c;
         }
-        if (!active) return;
+        if (hitpx) hlist[hbase + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)tid;
+        __syncthreads();
+        if (tid >= htotal) return;
+        const int q = (int)hlist[tid];
         const unsigned long long wkey = zbuf[q];
         const int px = tx0 + (q & (TILE_W - 1)), py = ty0 + (q >> 5);
         const int64_t ri = ((int64_t)b * is + py) * is + px;            // raster orientation
@@ -1477,7 +1424,7 @@ struct WorkLayout {
 
 // Workgroups per image of the binning pass: the largest power of two (<= 16) that keeps B x parts within the device's
 // compute units -- every workgroup of the launch resident at once, which the parts' barrier relies on -- and leaves a part
-// at least 256 faces.  Phase stamps (scripts/wg_timeline.py, profiles/r05_binning_parts.txt): the exchange costs a part
+// at least 256 faces.  Phase stamps (profiles/r05_binning_parts.txt): the exchange costs a part
 // ~2.5 us (publish 0.4, barrier 0.8, the other parts' counters 1.4) once it stays inside the XCD's L2; 16 renders of 480 x 480
 // (config 3, the reference's default batch size) 19.5 -> 13.9 us per workgroup, 64 renders 19.6 -> 16.6, 128 renders 21.7 -> ~19.
 static int device_cus() {
@@ -1530,7 +1477,7 @@ static WorkLayout work_layout(int B, int F, int is) {
 // `pro` (pair steps): the frame pair's vertex stage, to run inside the binning pass where that pass takes its fused-records
 // form and the vertices fit its LDS (bin_boxes_kernel PROLOGUE) -- else as the launch of its own, in front, from here
 template <bool VC>
-static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int F, int is, hipStream_t s,
+static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int F, int is, hipStream_t s, int flags,
                        uint8_t* tile_hit = nullptr, bool dense_list = false, bool list_cleared = false,
                        const PairPrologue* pro = nullptr) {
     const WorkLayout w = work_layout(B, F, is);
@@ -1555,21 +1502,19 @@ static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int 
     bp.rverts = (RecVerts*)(base + w.off_rverts);
     bp.F = F; bp.is = is; bp.nbx = w.nbx; bp.nby = w.nby; bp.ysh = w.ysh;
     const int nbins = w.nbx * w.nby;
-    // parts per image (bin_boxes_kernel, PARTS): B x parts workgroups, all resident at once; dbg 32: one workgroup per image
-    // (at most one workgroup per compute unit: two per compute unit -- dbg 64 -- were measured at 2B = 128: 37.7 us against
-    // 28.9 with two parts and 28.5 with one; config 3's 16 renders: 16 parts 23.1 us, one part 26.0)
-    int parts = (bp.dbg & 32) ? 1 : bin_parts(B, F, std::min(device_cus(), MAX_PART_CUS), 1);
-    if (bp.dbg & 4) parts = std::max(1, parts / 2);  // (profiling: half / a quarter / an eighth of the parts)
-    if (bp.dbg & 8) parts = std::max(1, parts / 4);
+    // parts per image (bin_boxes_kernel, PARTS): B x parts workgroups, all resident at once; MR_FLAG_ONE_WORKGROUP_PER_IMAGE: one
+    // (at most one workgroup per compute unit: two per compute unit were measured at 2B = 128: 37.7 us against 28.9 with two
+    // parts and 28.5 with one; config 3's 16 renders: 16 parts 23.1 us, one part 26.0)
+    int parts = (flags & MR_FLAG_ONE_WORKGROUP_PER_IMAGE) ? 1 : bin_parts(B, F, std::min(device_cus(), MAX_PART_CUS), 1);
     if (parts > w.parts) parts = w.parts;
     // (list_cleared: the caller cleared the tile list's header on this stream -- what the per-face pass's first thread does)
-    const bool fused_records = VC && list_cleared && bp.tlist && bp.F0 > 0 && !(bp.dbg & 16);
+    const bool fused_records = VC && list_cleared && bp.tlist && bp.F0 > 0;
     // The parts pay where they split the PER-FACE pass (fused_records: 64 renders of 256 x 256 22.1 us with 4 parts against 24.3
     // with one, 16 renders of 480 x 480 21.9 / 24.5, 64 of 640 x 640 31.1 / 35.5; 128 renders: 28.3 / 28.5).  With the boxes
     // already in memory a part only saves counting, and the exchange costs more than that unless the bins are many: 128 renders
     // of 256 x 256 19.6 us with two parts, 17.8 with one; 64 renders 16.9 / 15.6; 16 of 480 x 480 18.3 / 17.5; 64 of 640 x 640
-    // (1600 bins) 26.2 / 27.9 (round 6, rocprofv3 over `bench.py --kernels-only` / scripts/hot_only.py, HOC_FWD_DBG sweeps).
-    if (!fused_records && nbins <= 1024 && !(bp.dbg & 1)) parts = 1;
+    // (1600 bins) 26.2 / 27.9 (round 6, rocprofv3 over `bench.py --kernels-only` / scripts/hot_only.py).
+    if (!fused_records && nbins <= 1024 && !(flags & MR_FLAG_FORCE_PARTS)) parts = 1;
     bp.B = B; bp.parts = parts;
     bp.part_cnt = (int*)(base + w.off_part_cnt);
     bp.arrive = (unsigned*)(base + w.off_arrive);
@@ -1598,7 +1543,7 @@ static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int 
     bool pro_fused = false;
     if (pro) {
         const size_t v_lds = (size_t)bp.V * 3 * sizeof(float);
-        if (VC && fused_records_ok && (B & 1) == 0 && lds + v_lds <= 152 * 1024 && !(bp.dbg & 128)) {
+        if (VC && fused_records_ok && (B & 1) == 0 && lds + v_lds <= 152 * 1024) {
             pro_fused = true;
             lds += v_lds;
         } else {
@@ -1639,8 +1584,8 @@ static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int 
     // steps, device time per hot-path pass: 16 renders of 480 x 480 in 16 parts 27.7 us as one launch, 13.0 + 8.7 as two (0.097 ->
     // 0.092 ms); 32 renders in 8 parts and 64 in 4: no difference (0.0811 / 0.0818, 0.1109 / 0.1112); 128 renders of 256 x 256 in
     // 2 parts 33.4 against 22.4 + 13.1 -- with few parts the last arriver's serial share is small and the second launch's floor
-    // is not.  dbg 64: the last-arriver form whatever the parts)
-    const bool two_launches = parts >= 8 && !(bp.dbg & 64);
+    // is not.  MR_FLAG_PARTS_IN_ONE_LAUNCH: the last-arriver form whatever the parts)
+    const bool two_launches = parts >= 8 && !(flags & MR_FLAG_PARTS_IN_ONE_LAUNCH);
     if (two_launches) {
         if (pro_fused) hipLaunchKernelGGL(bin_count_prologue_kernel, dim3(grid), dim3(BIN_TPB), lds, s, bp, *pro);
         else if (fused_records_ok) hipLaunchKernelGGL(bin_count_kernel<true>, dim3(grid), dim3(BIN_TPB), lds, s, bp);
@@ -1768,7 +1713,7 @@ extern "C" int mr_forward_face_index_map(const float* faces, int32_t* face_index
     FwdParams p{};
     BinParams bp{};
     bp.faces = faces; bp.faces_inv = faces_inv; bp.F0 = num_faces;
-    int rc = launch_bins<false>(bp, p, work, batch_size, num_faces, image_size, s);
+    int rc = launch_bins<false>(bp, p, work, batch_size, num_faces, image_size, s, 0);
     if (rc == MR_OK) {
         p.faces = faces;
         p.depth = depth_map; p.fim = face_index_map;
@@ -1822,10 +1767,9 @@ extern "C" int mr_render_forward(const float* faces, const float* textures, cons
     FwdParams p{};
     BinParams bp{};
     bp.faces = faces; bp.F0 = num_faces;
-    bp.dbg = (flags >> 24) & 0xff;
     const bool dense_list = dense_list_ok(batch_size, num_faces, image_size, face_inv_map, flags);
     int rc = (flags & MR_FLAG_REFERENCE_ALGO) ? MR_OK
-                                              : launch_bins<false>(bp, p, workspace, batch_size, num_faces, image_size, s, nullptr, dense_list);
+                                              : launch_bins<false>(bp, p, workspace, batch_size, num_faces, image_size, s, flags, nullptr, dense_list);
     if (rc != MR_OK) return rc;
     p.faces = faces;
     p.textures = textures; p.background = background;
@@ -1837,7 +1781,7 @@ extern "C" int mr_render_forward(const float* faces, const float* textures, cons
     p.face_inv_map = face_inv_map;
     p.B = batch_size; p.F = num_faces; p.is = image_size; p.ts = return_rgb ? texture_size : 1;
     p.near_ = near_; p.far_ = far_; p.eps = eps;
-    p.dbg = flags >> 8;
+    p.plain_div = (flags & MR_FLAG_PLAIN_DIVISIONS) ? 1 : 0;
     if (flags & MR_FLAG_REFERENCE_ALGO) {
         const int64_t npx = (int64_t)batch_size * image_size * image_size;
         unsigned long long* keys = nullptr;
@@ -1889,10 +1833,9 @@ extern "C" int mr_render_vc_forward(const float* verts, const int32_t* faces_idx
     FwdParams p{};
     BinParams bp{};
     bp.verts = verts; bp.fidx = faces_idx; bp.V = num_verts; bp.F0 = num_faces; bp.fill_back = fill_back;
-    bp.dbg = (flags >> 24) & 0xff;
     if (batch_size > 65535) return MR_ERR_BADARG;
     const bool dense_list = dense_list_ok(batch_size, F, image_size, nullptr, flags);
-    const int rc = launch_bins<true>(bp, p, workspace, batch_size, F, image_size, s, nullptr, dense_list);
+    const int rc = launch_bins<true>(bp, p, workspace, batch_size, F, image_size, s, flags, nullptr, dense_list);
     if (rc != MR_OK) return rc;
     p.background = background; p.bg_stride = bg_stride;
     p.rgb = return_rgb ? rgb_img : nullptr;
@@ -1903,20 +1846,10 @@ extern "C" int mr_render_vc_forward(const float* verts, const int32_t* faces_idx
     p.near_ = near_; p.far_ = far_; p.eps = eps;
     p.verts = verts; p.fidx = faces_idx; p.vcolors = vcolors; p.V = num_verts; p.F0 = num_faces;
     p.texel = texel_layout;
-    p.dbg = (flags >> 8) & 0xffff;  // profiling experiments (scripts/fwd_vc_variants.py)
-    if (p.dbg & 128) return MR_OK;  // ... binning pass alone
+    p.plain_div = (flags & MR_FLAG_PLAIN_DIVISIONS) ? 1 : 0;
     if (p.tlist) return launch_dense_listed<true>(p, s);
     return launch_tiles<true, true>(p, s);
 }
-
-#ifdef MR_WG_TIMELINE
-extern "C" __attribute__((visibility("default"))) int mr_debug_times(void* dst, long n) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mr::mr_dbg_times), n, 0, hipMemcpyDeviceToHost);
-}
-extern "C" __attribute__((visibility("default"))) int mr_debug_bin_times(void* dst, long n) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mr::mr_dbg_bin), n, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 // mr_render_flow_forward of the 2B stacked meshes of a frame pair whose vertex stage has NOT run yet (mr_pair_step_forward,
 // pair_step.hip): `verts` (unused where the stage runs inside the binning pass), `faces_idx` and `vcolors` are the buffers that
@@ -1981,11 +1914,10 @@ int mr_render_flow_forward_pair(const float* verts, const int32_t* faces_idx, co
     FwdParams p{};
     BinParams bp{};
     bp.verts = verts; bp.fidx = faces_idx; bp.V = num_verts; bp.F0 = num_faces; bp.fill_back = fill_back;
-    bp.dbg = (flags >> 24) & 0xff;
     bp.zero_fill = zero_fill_count > 0 ? zero_fill : nullptr; bp.zero_count = zero_fill_count;
     if ((flags & MR_FLAG_SPARSE_TILES) && !tile_hit) return MR_ERR_BADARG;
     const bool listed = (flags & MR_FLAG_SPARSE_TILES) && tile_bound != 0;
-    const int rc = launch_bins<true>(bp, p, workspace, batch_size, F, image_size, s, listed ? tile_hit : nullptr, false,
+    const int rc = launch_bins<true>(bp, p, workspace, batch_size, F, image_size, s, flags, listed ? tile_hit : nullptr, false,
                                      (flags & MR_FLAG_TILE_LIST_CLEARED) != 0, pro);
     if (rc != MR_OK) return rc;
     p.tile_count_out = p.tlist ? tile_count_out : nullptr;
@@ -2002,7 +1934,6 @@ int mr_render_flow_forward_pair(const float* verts, const int32_t* faces_idx, co
     p.near_ = near_; p.far_ = far_; p.eps = eps;
     p.verts = verts; p.fidx = faces_idx; p.vcolors = vcolors; p.V = num_verts; p.F0 = num_faces;
     p.texel = texel_layout;
-    p.dbg = (flags >> 8) & 0xffff;
-    if (p.dbg & 128) return MR_OK;
+    p.plain_div = (flags & MR_FLAG_PLAIN_DIVISIONS) ? 1 : 0;
     return launch_tiles<true, true>(p, s, tile_bound);
 }

@@ -431,8 +431,7 @@ def _render_stacked_flow(ndc, faces2, cols, lut, fill_back, image_size, near, fa
     work = cleared_work if cleared_work is not None else torch.empty((max(wbytes, 8),), dtype=torch.uint8, device=dev)
     st = _lib.stream_ptr(dev)
     bound, count_word = _tile_bound(dev, B2, is_) if (USE_SPARSE_TILES and USE_TILE_LIST) else (0, None)
-    render_flags = ((_lib.FLAG_SPARSE_TILES if USE_SPARSE_TILES else 0) | (_lib.FLAG_TILE_LIST_CLEARED if cleared_work is not None else 0)
-                    | _FWD_DBG_FLAGS)
+    render_flags = (_lib.FLAG_SPARSE_TILES if USE_SPARSE_TILES else 0) | (_lib.FLAG_TILE_LIST_CLEARED if cleared_work is not None else 0)
     # the backward's output buffer is cleared by the render's binning pass on its way (its own clearing would be a
     # launch on the backward pass's critical path); a second backward through this node clears its own
     grad_buf = torch.empty((B2, V, 3), **f32) if want_grad else None
@@ -543,8 +542,7 @@ USE_UNIT_GRADIENT = True
 # ... and with the backward's workgroups handed out over the covered-tile lists the forward's finalize launch compacts (ABI 7):
 # workgroups per image in proportion to its covered tiles.  False: a fixed number per image, each listing the image's tiles.
 USE_SCATTER_WORK = os.environ.get("HOC_SCATTER_WORK", "1") != "0"
-_FWD_DBG_FLAGS = int(os.environ.get("HOC_FWD_DBG", "0")) << 8  # profiling switches of the forward kernels (csrc/raster_fwd.hip: dbg)
-_PAIR_STEP_FLAGS = int(os.environ.get("HOC_PAIR_STEP_FLAGS", "0")) & 0xfe  # MrPairStep.flags, e.g. 2 = MR_PAIR_STEP_SEPARATE_LAUNCHES (A / B runs)
+_PAIR_STEP_FLAGS = 0  # MrPairStep.flags of the step's forward call (tests set pairstep.SEPARATE_LAUNCHES)
 # ... and with the render's per-face pass folded into its binning pass (the pair prologue clears the tile list's header, which
 # the per-face pass's first thread does otherwise): one launch and one dependent round trip less per pair.
 USE_FUSED_RECORDS = True
@@ -726,7 +724,7 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
         lut = _keep_lut(ignore_face_idxs, dev) if ignore_face_idxs is not None else None
         res = pairstep.pair_step((h1, o1), (h2, o2), hand_face, obj_faces, camintrs[0].to(dev), camintrs[1].to(dev), neurenderer,
                                  is_, H, W, image_ref, image, jitter_mask_ref, jitter_mask, lut, mean_of_fwd_only=(with_mean == "fwd"),
-                                 poison=DEBUG_POISON_RENDER_OUTPUTS, flags=_FWD_DBG_FLAGS | _PAIR_STEP_FLAGS, criterion=criterion)
+                                 poison=DEBUG_POISON_RENDER_OUTPUTS, flags=_PAIR_STEP_FLAGS, criterion=criterion)
         if res is not None:
             mean, loss_sum, loss_fwd, loss_bwd, flows, tile_hit = res
             # (the render's tile list lives in the plan's scratch, which the next call reuses: the note carries the coverage only)

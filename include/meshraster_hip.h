@@ -52,6 +52,24 @@ extern "C" {
  * (mr_render_tile_list's list_header, pure address arithmetic on the workspace pointer: the list counters and the arrival
  * counters of the binning pass) on the same stream before the call -- mr_flow_pair_prologue_parts does it on request.  The per-face pass, whose first thread clears it otherwise, then runs inside the binning pass (one launch less). */
 #define MR_FLAG_TILE_LIST_CLEARED 16
+/* mr_render_forward / mr_render_vc_forward / mr_render_flow_forward: the binning pass bins each image in parts (several
+ * workgroups) also where one workgroup per image is the default.  Same outputs; tests only. */
+#define MR_FLAG_FORCE_PARTS (1 << 24)
+/* ... the binning pass bins each image with one workgroup, whatever the default.  Same outputs; the reference of the
+ * parts' tests. */
+#define MR_FLAG_ONE_WORKGROUP_PER_IMAGE (32 << 24)
+/* ... the parts of an image exchange their counts through the last part to arrive, in one launch, also where two launches
+ * are the default (eight parts or more).  Same outputs; tests only. */
+#define MR_FLAG_PARTS_IN_ONE_LAUNCH (64 << 24)
+/* mr_render_forward / mr_render_vc_forward / mr_render_flow_forward: plain divisions everywhere instead of the shared
+ * reciprocals of division-safe faces (vertex-colour modes).  Same outputs; the reference of that path's tests. */
+#define MR_FLAG_PLAIN_DIVISIONS (4096 << 8)
+/* mr_render_vc_backward: the per-face gather also where the pixel-parallel scatter's colour table would fit LDS (the gather
+ * is the path of larger tables).  Same results up to the order of the fp32 additions; tests only. */
+#define MR_FLAG_FORCE_GATHER (32 << 8)
+/* mr_render_backward: count the terms of the pixel-map walk that mr_pixel_map_terms reads back.  Profiling only. */
+#define MR_FLAG_COUNT_PIXEL_MAP_TERMS (1024 << 8)
+/* Other bits of `flags` are ignored. */
 
 /* texel_layout argument of the vertex-colour entry points (mr_render_vc_*, mr_render_flow_*): which vertex's colour the
  * three non-zero texels of the 2x2x2 texture of libyana's batch_vertex_textures hold -- two bits per texel axis,
@@ -203,7 +221,7 @@ MR_API int mr_render_backward(const float* faces, const float* textures,
                        int return_rgb, int return_alpha, int return_depth, int flags,
                        mr_stream_t stream);
 
-/* Profiling aid of the pixel-map term (kernel D by strips): mr_render_backward launched with `flags | (1024 << 8)` adds the
+/* Profiling aid of the pixel-map term (kernel D by strips): mr_render_backward launched with MR_FLAG_COUNT_PIXEL_MAP_TERMS adds the
  * number of TERMS its walk evaluates -- one term = one evaluation of the sweep body of upstream's backward_pixel_map
  * (rasterize.py:269-281): every position of an "out" sweep, every position of an "in" sweep whose pixel belongs to the face
  * -- to a device-side counter.  This call synchronises the device, copies the counter to *terms_host (host memory) and, with
@@ -747,7 +765,7 @@ MR_API int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, const
  *     grad_verts* nullable (not wanted); all four NULL: nothing to do.  The vertex-colour gradient buffer inside `saved` is
  *     cleared by the FORWARD call (want_grad != 0) and consumed by the first backward call; a caller that differentiates the
  *     same forward call again sets MR_PAIR_STEP_GRAD_BUFFER_USED in `flags` for the later calls (the buffer is then cleared
- *     first).  flags bits 8 and up: profiling switches of the render (forward call only).
+ *     first).
  *   criterion (ABI 9): MR_CRITERION_L1 or MR_CRITERION_L2, the pair loss's criterion (forward call; the backward's scatter
  *     does not depend on it); reserved: zero. */
 #define MR_PAIR_STEP_GRAD_BUFFER_USED 1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel durations of the render + warp hot path (scripts/hot_only.py under rocprofv3 --kernel-trace), eager + replayed passes.
-# Usage: scripts/hot_kernels.sh <label> [hot_only.py arguments]   (environment, e.g. HOC_FWD_DBG=..., is inherited)
+# Usage: scripts/hot_kernels.sh <label> [hot_only.py arguments]   (the environment is inherited)
 LABEL=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out

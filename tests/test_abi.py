@@ -107,6 +107,38 @@ def test_pair_step_struct_layout_matches_the_binding():
     assert lib.mr_pair_step_forward(None, None) == -1 and lib.mr_pair_step_backward(None, None) == -1
 
 
+def _header_int(expr):
+    """value of a #define's integer expression: literals, parentheses, <<, | and unary minus"""
+    import ast
+
+    def ev(n):
+        if isinstance(n, ast.Constant) and isinstance(n.value, int):
+            return n.value
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, ast.USub):
+            return -ev(n.operand)
+        if isinstance(n, ast.BinOp) and isinstance(n.op, (ast.LShift, ast.BitOr)):
+            a, b = ev(n.left), ev(n.right)
+            return a << b if isinstance(n.op, ast.LShift) else a | b
+        raise ValueError(f"unsupported constant expression: {expr}")
+
+    return ev(ast.parse(expr.strip(), mode="eval").body)
+
+
+def test_header_constants_match_their_python_mirrors():
+    from handobjectconsist_amd import _lib
+    from handobjectconsist_amd.warping import pairstep
+
+    src = open(HEADER).read()
+    defs = re.findall(r"^#define\s+MR_(FLAG|PAIR_STEP|CRITERION)_([A-Z0-9_]+)\s+(.+?)\s*$", src, re.M)
+    kinds = {k for k, _, _ in defs}
+    assert kinds == {"FLAG", "PAIR_STEP", "CRITERION"}, kinds
+    for kind, name, expr in defs:
+        value = _header_int(expr)
+        mirror = (pairstep, name) if kind == "PAIR_STEP" else (_lib, f"{kind}_{name}")
+        assert hasattr(*mirror), f"MR_{kind}_{name} has no Python mirror ({mirror[0].__name__}.{mirror[1]})"
+        assert getattr(*mirror) == value, f"MR_{kind}_{name} = {value}, {mirror[0].__name__}.{mirror[1]} = {getattr(*mirror)}"
+
+
 def test_argument_validation_needs_no_device():
     from handobjectconsist_amd import _lib
 

@@ -567,7 +567,7 @@ def test_tile_kernel_divisions_shared_vs_plain(cuda, case):
     wbytes = int(_lib.load().mr_render_workspace_bytes(B, 2 * F0, is_))
     work = torch.empty((wbytes,), dtype=torch.uint8, device=cuda)
     outs = []
-    for dbg in (0, 4096):
+    for div_flags in (0, _lib.FLAG_PLAIN_DIVISIONS):
         for records in (True, False):
             rgb = torch.zeros((B, 3, is_, is_), **f32)
             alpha, mask, depth = torch.zeros((B, is_, is_), **f32), torch.zeros((B, is_, is_), **f32), torch.zeros((B, is_, is_), **f32)
@@ -577,7 +577,7 @@ def test_tile_kernel_divisions_shared_vs_plain(cuda, case):
             hit = torch.zeros((B, (is_ + 7) // 8, (is_ + 31) // 32, 4), dtype=torch.uint8, device=cuda)
             _lib.call("mr_render_flow_forward", P(v), P(fidx), P(cols), P(bg), 0, None, 0, 0.99999, P(rgb), P(alpha), P(mask),
                       None if records else P(depth), P(wmap), P(fim), P(hit), P(work), wbytes, B, V, F0, 1, is_, 0.1, 100.0, 1e-3,
-                      _lib.FLAG_SPARSE_TILES | (dbg << 8), P(vid) if records else None, -1, None, None, 0, 0, st)
+                      _lib.FLAG_SPARSE_TILES | div_flags, P(vid) if records else None, -1, None, None, 0, 0, st)
             outs.append([x.view(torch.int32) if x.dtype == torch.float32 else x for x in (rgb, alpha, mask, depth, wmap, fim, vid, hit)])
     assert int((outs[0][5] >= 0).sum()) > 200
     for fast, plain in ((outs[0], outs[2]), (outs[1], outs[3])):
@@ -778,7 +778,7 @@ def _vc_backward(d, g_rgb_img, mode):
     stored = mode == "stored"
     _lib.call("mr_render_vc_backward", P(d["v"]), P(d["fidx"]), P(d["fim"]), P(d["wmap"]) if stored else None,
               P(d["depth"]) if stored else None, P(g_rgb_img), P(out), d["B"], d["V"], d["F0"], 1, d["is_"], 1e-3,
-              (32 << 8) if mode == "gather" else 0, 0, _lib.stream_ptr(g_rgb_img.device))
+              _lib.FLAG_FORCE_GATHER if mode == "gather" else 0, 0, _lib.stream_ptr(g_rgb_img.device))
     return out.cpu().numpy()
 
 
@@ -1076,11 +1076,6 @@ def test_dense_forwards_over_the_tile_list_equal_one_workgroup_per_tile(cuda, B,
         assert int((new[3] >= 0).sum()) > 100
 
 
-FLAG_ONE_WORKGROUP_PER_IMAGE = 32 << 24  # (profiling / A-B bit of the binning pass: raster_fwd.hip, launch_bins)
-FLAG_FORCE_PARTS = 1 << 24  # (launch_bins: several workgroups per image also where one is the default)
-FLAG_PARTS_IN_ONE_LAUNCH = 64 << 24  # (launch_bins: the last-arriver form also where four or more parts take two launches, round 6)
-
-
 @pytest.mark.parametrize("B,is_", [(2, 256), (13, 96), (40, 64), (3, 480)])
 def test_binning_pass_in_parts_equals_one_workgroup_per_image(cuda, B, is_):
     """Round 5: an image is binned by several workgroups (a contiguous range of its faces each; they exchange their bin
@@ -1128,13 +1123,13 @@ def test_binning_pass_in_parts_equals_one_workgroup_per_image(cuda, B, is_):
         return outs, int(word[0])
 
     for kind in ("flow", "vc", "generic"):
-        one, n_one = run(kind, FLAG_ONE_WORKGROUP_PER_IMAGE)
+        one, n_one = run(kind, _lib.FLAG_ONE_WORKGROUP_PER_IMAGE)
         # (FLAG_FORCE_PARTS: since round 6 the standalone entry points bin rasters of up to 1024 tiles with one workgroup per
         # image -- the parts only pay where they split the per-face pass, i.e. on the training path's fused launch, which
         # tests/test_gpu_warp.py drives; the switch keeps this comparison on the parts)
         # (round 6: four or more parts exchange their counters across a kernel boundary -- count launch, fill launch; fewer, or
         # FLAG_PARTS_IN_ONE_LAUNCH, through the memory side with the last arriver finishing the image: both forms here)
-        for flags in (FLAG_FORCE_PARTS, FLAG_FORCE_PARTS, FLAG_FORCE_PARTS | FLAG_PARTS_IN_ONE_LAUNCH, 0):  # (twice: the second call finds the first one's counters in a REUSED allocation)
+        for flags in (_lib.FLAG_FORCE_PARTS, _lib.FLAG_FORCE_PARTS, _lib.FLAG_FORCE_PARTS | _lib.FLAG_PARTS_IN_ONE_LAUNCH, 0):  # (twice: the second call finds the first one's counters in a REUSED allocation)
             parts, n_parts = run(kind, flags)
             for a, b_, name in zip(one, parts, ("rgb", "alpha", "mask", "depth", "weights", "face_index_map", "vertex ids", "coverage")):
                 assert torch.equal(a, b_), f"{name} differs ({kind})"
