@@ -8,39 +8,11 @@
 // plain struct (sizes once per shape, pointers per call) and makes ONE call each way; the buffers the launches hand to one
 // another live in a scratch region the caller keeps from call to call.  No new device code except the batch mean, which the
 // finalize launch's last workgroup forms: every launch is the existing entry point's, so the results are the five calls' bit
-// for bit.
+// for bit.  The launchers underneath take named argument blocks (pair_launch.hpp), filled here from MrPairStep + PairStepLayout.
 #include <cstddef>
 #include <cstdint>
 
-#include "mr_common.hpp"
-#include "vertex_stage_device.hpp"
-
-int mr_flow_pair_backward_unit_tiles_ex(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
-                                        const int32_t* vertex_id_map, const float* unit_grad, const float* unit_grad_max,
-                                        const float* sums, const float* grad_loss_fwd, const float* grad_loss_bwd,
-                                        const float* grad_loss_sum, const float* grad_mean, int mean_of, int height, int width,
-                                        float* grad_vcolors, int batch_size, int num_verts, int num_faces, int fill_back,
-                                        int image_size, float eps, int flags, int texel_layout, const void* scatter_work,
-                                        mr_stream_t stream);
-
-int mr_flow_pair_forward_grad_tiles_ex(const float* mask_flow1, const float* mask_flow2, const float* flow12, const float* flow21,
-                                       int64_t flow_bstride, const float* flow12_scale, const float* flow21_scale, float* occl1,
-                                       float* occl2, float* flow_out12, float* flow_out21, const uint8_t* tile_hit1,
-                                       const uint8_t* tile_hit2, const float* image_ref, const float* image, const float* jitter_ref,
-                                       const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
-                                       float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size, int height,
-                                       int width, float distance_thresh, float warp_thresh, float pair_thresh, const void* list_header,
-                                       const void* list_entries, int64_t list_capacity, int64_t tile_bound, float* unit_grad,
-                                       float* unit_grad_max, float* loss_sum, void* scatter_work, float* mean_out, int mean_of,
-                                       int reset_list, const void* records, mr_stream_t stream, int criterion);
-
-int mr_render_flow_forward_pair(const float* verts, const int32_t* faces_idx, const float* vcolors, const float* background,
-                                int bg_stride, const float* keep_lut, int n_lut, float alpha_thresh, float* rgb_img, float* alpha_img,
-                                float* mask_img, float* depth_img, float* weight_map, int32_t* face_index_map, uint8_t* tile_hit,
-                                void* workspace, int64_t workspace_bytes, int batch_size, int num_verts, int num_faces, int fill_back,
-                                int image_size, float near_, float far_, float eps, int flags, int32_t* vertex_id_map, int tile_bound,
-                                uint32_t* tile_count_out, float* zero_fill, int64_t zero_fill_count, int texel_layout,
-                                mr_stream_t stream, const mr::PairPrologue* pro, void* records);
+#include "pair_launch.hpp"
 
 namespace mr {
 
@@ -191,28 +163,39 @@ extern "C" int mr_pair_step_forward(const MrPairStep* step, mr_stream_t stream) 
     // (round 6: what the render hands to the fused warp forward is ONE 16-byte record per pixel {displacement x, y, alpha,
     // mask} instead of four planes; the first form keeps the planes)
     void* records = separate ? nullptr : (void*)(sc + L.rec);
-    rc = mr_render_flow_forward_pair(ndc, faces2, cols, a.background, a.bg_stride, a.keep_lut, a.n_lut, a.alpha_thresh,
-                                     records ? nullptr : rgb, records ? nullptr : alpha, records ? nullptr : mask,
-                                     nullptr, wmap, fim, tile_hit, rwork, L.render_work_bytes, B2, V, L.F0, a.fill_back, is, a.near_, a.far_,
-                                     a.eps, MR_FLAG_SPARSE_TILES | MR_FLAG_TILE_LIST_CLEARED, vid,
-                                     (int)(bound > 0x7fffffffLL ? 0x7fffffffLL : bound), a.tile_count_out, grad_buf,
-                                     grad_buf ? (int64_t)B2 * V * 3 : 0, a.texel_layout, stream, separate ? nullptr : &pro, records);
+    FlowRenderArgs r{};
+    r.verts = ndc; r.faces_idx = faces2; r.vcolors = cols; r.background = a.background; r.bg_stride = a.bg_stride;
+    r.keep_lut = a.keep_lut; r.n_lut = a.n_lut; r.alpha_thresh = a.alpha_thresh;
+    if (!records) { r.rgb_img = rgb; r.alpha_img = alpha; r.mask_img = mask; }
+    r.weight_map = wmap; r.face_index_map = fim; r.tile_hit = tile_hit; r.vertex_id_map = vid;
+    r.workspace = rwork; r.workspace_bytes = L.render_work_bytes;
+    r.batch_size = B2; r.num_verts = V; r.num_faces = L.F0; r.fill_back = a.fill_back; r.image_size = is;
+    r.near_ = a.near_; r.far_ = a.far_; r.eps = a.eps; r.flags = MR_FLAG_SPARSE_TILES | MR_FLAG_TILE_LIST_CLEARED;
+    r.tile_bound = (int)(bound > 0x7fffffffLL ? 0x7fffffffLL : bound); r.texel_layout = a.texel_layout;
+    r.tile_count_out = a.tile_count_out; r.zero_fill = grad_buf; r.zero_fill_count = grad_buf ? (int64_t)B2 * V * 3 : 0;
+    r.pro = separate ? nullptr : &pro; r.records = records;
+    rc = launch_flow_render(r, (hipStream_t)stream);
     if (rc != MR_OK) return rc;
     // 3. occlusion + flow epilogue + pair loss forward (+ its unit gradient) over the render's tile list; finalize
-    float *loss_fwd = a.losses, *loss_bwd = a.losses + B, *loss_sum = a.losses + 2 * (int64_t)B;
     const int64_t th_half = (int64_t)B * (((is + 7) / 8) * ((is + 31) / 32)) * 4;  // (bytes of frame 1's coverage words)
-    float* flow12 = a.flows;
-    float* flow21 = a.flows + (int64_t)B * a.height * a.width * 2;
-    rc = mr_flow_pair_forward_grad_tiles_ex(mask, alpha + (int64_t)B * px, rgb, rgb + (int64_t)B * 3 * px, 3 * px, mask,
-                                         mask + (int64_t)B * px, records ? nullptr : occl, records ? nullptr : occl + (int64_t)B * px, flow12, flow21, tile_hit,
-                                         tile_hit + th_half, a.image_ref, a.image, a.jitter_ref, a.jitter, a.jitter_channels, pwork,
-                                         L.pair_work_bytes, sums, loss_fwd, loss_bwd, B, is, a.height, a.width, a.distance_thresh,
-                                         a.warp_thresh, a.pair_thresh, hdr, ents, cap, bound, unit_grad, unit_max, loss_sum, swork,
-                                         // (the finalize launch's last workgroup leaves the mean in losses[3 B]; the B words
-                                         // behind it -- the caller's buffer has 4 B + 1 -- carry the samples' values to it)
-                                         // (reset_list: the finalize launch leaves the list header's counters zero for the next step)
-                                         a.losses + 3 * (int64_t)B, a.mean_of, 1, records, stream, a.criterion);
-    return rc;
+    FlowPairFwdArgs f{};
+    f.mask_flow1 = mask; f.mask_flow2 = alpha + (int64_t)B * px; f.flow12 = rgb; f.flow21 = rgb + (int64_t)B * 3 * px; f.flow_bstride = 3 * px;
+    f.flow12_scale = mask; f.flow21_scale = mask + (int64_t)B * px;
+    if (!records) { f.occl1 = occl; f.occl2 = occl + (int64_t)B * px; }
+    f.flow_out12 = a.flows; f.flow_out21 = a.flows + (int64_t)B * a.height * a.width * 2;
+    f.tile_hit1 = tile_hit; f.tile_hit2 = tile_hit + th_half;
+    f.image_ref = a.image_ref; f.image = a.image; f.jitter_ref = a.jitter_ref; f.jitter = a.jitter; f.jitter_channels = a.jitter_channels;
+    f.workspace = pwork; f.workspace_bytes = L.pair_work_bytes;
+    f.sums = sums; f.loss_fwd = a.losses; f.loss_bwd = a.losses + B; f.loss_sum = a.losses + 2 * (int64_t)B;
+    f.batch_size = B; f.image_size = is; f.height = a.height; f.width = a.width;
+    f.distance_thresh = a.distance_thresh; f.warp_thresh = a.warp_thresh; f.pair_thresh = a.pair_thresh;
+    f.list_header = hdr; f.list_entries = ents; f.list_capacity = cap; f.tile_bound = bound;
+    f.unit_grad = unit_grad; f.unit_grad_max = unit_max; f.scatter_work = swork;
+    // (the finalize launch's last workgroup leaves the mean in losses[3 B]; the B words behind it -- the caller's buffer has
+    // 4 B + 1 -- carry the samples' values to it; reset_list: it leaves the list header's counters zero for the next step)
+    f.mean_out = a.losses + 3 * (int64_t)B; f.mean_of = a.mean_of; f.reset_list = 1;
+    f.records = records; f.criterion = a.criterion;
+    return launch_flow_pair_forward(f, (hipStream_t)stream);
 }
 
 extern "C" int mr_pair_step_backward(const MrPairStep* step, mr_stream_t stream) {
@@ -230,12 +213,16 @@ extern "C" int mr_pair_step_backward(const MrPairStep* step, mr_stream_t stream)
     const int B = a.batch_size, B2 = L.B2, V = L.V, is = a.image_size;
     float* grad_cols = (float*)(sv + L.grad_buf);
     // (a direction without its own gradient array still takes the sum's / the mean's share: the scatter adds them up)
-    rc = mr_flow_pair_backward_unit_tiles_ex((const int32_t*)(sv + L.fim), (const uint32_t*)(sv + L.tile_hit), (const float*)(sv + L.wmap),
-                                             (const int32_t*)(sv + L.vid), (const float*)(sv + L.unit_grad),
-                                             (const float*)(sv + L.unit_max), (const float*)(sv + L.sums), a.grad_loss_fwd,
-                                             a.grad_loss_bwd, a.grad_loss_sum, a.grad_mean, a.mean_of, a.height, a.width, grad_cols, B2,
-                                             V, L.F0, a.fill_back, is, a.eps, (a.flags & MR_PAIR_STEP_GRAD_BUFFER_USED) ? 0 : MR_FLAG_OUTPUT_ZEROED, a.texel_layout,
-                                             sv + L.scatter_work, stream);
+    UnitScatterArgs u{};
+    u.face_index_map = (const int32_t*)(sv + L.fim); u.tile_hit = (const uint32_t*)(sv + L.tile_hit);
+    u.weight_map = (const float*)(sv + L.wmap); u.vertex_id_map = (const int32_t*)(sv + L.vid);
+    u.unit_grad = (const float*)(sv + L.unit_grad); u.unit_grad_max = (const float*)(sv + L.unit_max); u.sums = (const float*)(sv + L.sums);
+    u.grad_loss_fwd = a.grad_loss_fwd; u.grad_loss_bwd = a.grad_loss_bwd; u.grad_loss_sum = a.grad_loss_sum; u.grad_mean = a.grad_mean;
+    u.mean_of = a.mean_of; u.height = a.height; u.width = a.width; u.grad_vcolors = grad_cols;
+    u.batch_size = B2; u.num_verts = V; u.num_faces = L.F0; u.fill_back = a.fill_back; u.image_size = is; u.eps = a.eps;
+    u.flags = (a.flags & MR_PAIR_STEP_GRAD_BUFFER_USED) ? 0 : MR_FLAG_OUTPUT_ZEROED; u.texel_layout = a.texel_layout;
+    u.scatter_work = sv + L.scatter_work;
+    rc = launch_unit_scatter_tiles(u, (hipStream_t)stream);
     if (rc != MR_OK) return rc;
     return mr_flow_vertices_parts_backward(a.verts1a, a.verts1b, a.verts2a, a.verts2b, a.num_verts_a, a.num_verts_b, a.K1, a.K2,
                                            grad_cols, grad_cols + (int64_t)B * V * 3, a.grad_verts1a, a.grad_verts1b, a.grad_verts2a,

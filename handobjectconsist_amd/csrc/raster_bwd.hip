@@ -23,6 +23,7 @@
 //   * pixel_map_strip_kernel<IMG, L> -- kernel D by strips of image lines staged in LDS, fed by per-image owner
 //     records from compact_owners_kernel (the default when a workspace is given; see the comment there).
 #include "mr_common.hpp"
+#include "pair_launch.hpp"
 #include "warp_device.hpp"
 #include <algorithm>
 #include <type_traits>
@@ -2294,6 +2295,15 @@ struct FusedGather {
     bool tex, depth;
     int64_t threads;
 };
+// the marking pass over the face index map, four pixels per thread where the raster allows; `weights` (nullable): the strip
+// weights it clears on the way, one word per thread
+static int launch_mark_owners(const int32_t* fim, uint8_t* owns, int B, int is, int F, unsigned* weights, int64_t n_weights,
+                              hipStream_t s) {
+    const int64_t ppi = (int64_t)is * is, npx = ppi * B;
+    if (ppi % 4 == 0) return launch1d(mark_owners_kernel, std::max(npx / 4, n_weights), s, fim, owns, npx / 4, ppi, F, weights, n_weights);
+    return launch1d(mark_owners_scalar_kernel, std::max(npx, n_weights), s, fim, owns, npx, ppi, F, weights, n_weights);
+}
+
 template <bool IMG>
 static int launch_pixel_map(const PixelMapParams& p, void* workspace, int64_t workspace_bytes, int flags,
                             hipStream_t s, const FusedGather* fused = nullptr, bool* fused_done = nullptr) {
@@ -2304,12 +2314,10 @@ static int launch_pixel_map(const PixelMapParams& p, void* workspace, int64_t wo
     const int strip_l = strip_lines(p.is);
     hipError_t e0 = hipMemsetAsync(ol0.owns, 0, ol0.clear_bytes, s);  // flags and the counts behind them
     if (e0 != hipSuccess) return (int)e0;
-    const int64_t ppi = (int64_t)p.is * p.is, npx = ppi * p.B;
     const StripLists sl = strip_lists(workspace, p.B, p.F, p.is);
     // (the marking pass clears the weights, one word per thread: 2 B is / L words -- more than B is^2 / 4 pixel quads for
     // rasters of one or two pixels, found by tests/fuzz_parity.py: the launch then covers the weights, the kernels guard)
-    int rc = (ppi % 4 == 0) ? launch1d(mark_owners_kernel, std::max(npx / 4, sl.n_weights), s, p.fim, ol0.owns, npx / 4, ppi, p.F, sl.weights, sl.n_weights)
-                            : launch1d(mark_owners_scalar_kernel, std::max(npx, sl.n_weights), s, p.fim, ol0.owns, npx, ppi, p.F, sl.weights, sl.n_weights);
+    int rc = launch_mark_owners(p.fim, ol0.owns, p.B, p.is, p.F, sl.weights, sl.n_weights, s);
     if (rc != MR_OK || nfaces == 0) return rc;
     PixelMapParams q = p;
     q.zero_owner_rows = 1;
@@ -2436,7 +2444,6 @@ extern "C" int mr_render_backward(const float* faces, const float* textures,
     if (batch_size == 0 || num_faces == 0) return MR_OK;
     if (!faces || !face_index_map) return MR_ERR_BADARG;
     if (grad_textures && (!return_rgb || !grad_rgb_img || texture_size < 2)) return MR_ERR_BADARG;
-    if (batch_size == 0 || num_faces == 0) return MR_OK;
     hipStream_t s = (hipStream_t)stream;
     const int64_t nfaces = (int64_t)batch_size * num_faces;
     const int64_t npx = (int64_t)batch_size * image_size * image_size;
@@ -2490,9 +2497,7 @@ extern "C" int mr_render_backward(const float* faces, const float* textures,
         const OwnerList ol = owner_list(workspace, batch_size, num_faces);
         hipError_t e = hipMemsetAsync(ol.owns, 0, ol.clear_bytes, s);  // flags and the counts behind them
         if (e != hipSuccess) return (int)e;
-        const int64_t ppi = (int64_t)image_size * image_size;
-        if (ppi % 4 == 0) rc = launch1d(mark_owners_kernel, npx / 4, s, face_index_map, ol.owns, npx / 4, ppi, num_faces, (unsigned*)nullptr, (int64_t)0);
-        else rc = launch1d(mark_owners_scalar_kernel, npx, s, face_index_map, ol.owns, npx, ppi, num_faces, (unsigned*)nullptr, (int64_t)0);
+        rc = launch_mark_owners(face_index_map, ol.owns, batch_size, image_size, num_faces, nullptr, 0, s);
         if (rc != MR_OK) return rc;
         PixelMapParams q{};
         q.faces = faces; q.grad_faces = grad_faces; q.B = batch_size; q.F = num_faces; q.is = image_size;
@@ -2543,6 +2548,44 @@ extern "C" int mr_render_vc_backward(const float* verts, const int32_t* faces_id
     return launch1d(gather_vc_kernel<0>, (int64_t)batch_size * num_faces * GLPF, s, g);
 }
 
+// ---- the tile-scatter launches: mr_render_flow_backward, mr_flow_pair_backward_tiles, mr_flow_pair_backward_unit_tiles ----
+// What they share.  The entry point has filled sp.g, sp.weight / tile_hit / vid_map / split / H / W and its own fields; this
+// runs the common checks in the entry points' common order, zeroes the output unless MR_FLAG_OUTPUT_ZEROED (the workgroups of
+// an image meet in global atomics on a zeroed output), completes sp (tiles_x / tiles_y / groups) and launches `kernel` with
+// the colour table's LDS bytes.  `args_ok` / `maps_ok`: the entry point's own checks, which take their turn before the
+// memset / behind the num_faces == 0 return.  `pairs`: the images are the two frames of batch_size / 2 pairs.
+static int launch_scatter_tiles(ScatterTilesParams& sp, int flags, bool pairs, bool args_ok, bool maps_ok,
+                                void (*kernel)(ScatterTilesParams), hipStream_t s) {
+    const GatherVCParams& g = sp.g;
+    if (g.B < 0 || (pairs && (g.B & 1)) || g.F0 < 0 || g.V < 0 || g.is <= 0 || !texel_layout_ok(g.texel)) return MR_ERR_BADARG;
+    if (!g.grad_vcolors && (int64_t)g.B * g.V > 0) return MR_ERR_BADARG;
+    if (g.B == 0 || g.V == 0) return MR_OK;
+    if (!args_ok) return MR_ERR_BADARG;
+    if (!(flags & MR_FLAG_OUTPUT_ZEROED)) {
+        hipError_t e = hipMemsetAsync(g.grad_vcolors, 0, (size_t)g.B * g.V * 3 * sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (g.F0 == 0) return MR_OK;
+    if (!g.fim || !sp.weight || !(g.eps >= 1e-6f) || !maps_ok) return MR_ERR_BADARG;
+    // the tile walk reads 4-pixel groups with 16-byte loads and keeps the colour table in LDS: three sums per vertex for a
+    // colour-space gradient, two for a flow-space one
+    const int64_t table_bytes = (((int64_t)g.V * (g.grad_rgb ? 3 : 2) + 1) / 2) * 16;
+    sp.tiles_x = (g.is + ST_TW - 1) / ST_TW; sp.tiles_y = (g.is + ST_TH - 1) / ST_TH;
+    if (g.is % 4 != 0 || table_bytes > SV_MAX_TABLE_BYTES || (int64_t)sp.tiles_x * sp.tiles_y > ST_MAX_TILES) return MR_ERR_NOTIMPL;
+    // workgroups per image.  mr_render_flow_backward: ST_G.  The pair launches walk a workgroup's covered tiles a wave (the
+    // pair loss's backward, pass 1: two tiles, one behind the other) at a time, and larger rasters have more of them per image
+    // (a sixth of 256 / 900 / 1600 tiles), so they get more workgroups, ~8 tiles each: 8 / 32 / 32.  A 480 x 480 pair at
+    // B = 8: 73 -> 46 us (mr_flow_pair_backward_tiles), 30 -> 19 us (_unit_tiles) with 32 instead of 8; 640 x 640 at B = 32:
+    // 86 -> 74 us cold (_unit_tiles)
+    sp.groups = ST_G;
+    while (pairs && sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
+    const int64_t blocks = (int64_t)g.B * sp.groups;
+    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
+
 extern "C" int mr_render_flow_backward(const float* verts, const int32_t* faces_idx, const int32_t* face_index_map,
                                        const uint32_t* tile_hit, const float* weight_map, const float* depth_img,
                                        const float* grad_rgb_img, const float* grad_flow, const float* mask_pre,
@@ -2551,42 +2594,20 @@ extern "C" int mr_render_flow_backward(const float* verts, const int32_t* faces_
                                        int num_faces, int fill_back, int image_size, float eps, int flags,
                                        const int32_t* vertex_id_map, int texel_layout, const float* grad_bound,
                                        mr_stream_t stream) {
-    if (batch_size < 0 || num_faces < 0 || num_verts < 0 || image_size <= 0 || !texel_layout_ok(texel_layout)) return MR_ERR_BADARG;
-    if (!grad_vcolors && (int64_t)batch_size * num_verts > 0) return MR_ERR_BADARG;
-    if (batch_size == 0 || num_verts == 0) return MR_OK;
     const bool flowgrad = grad_rgb_img == nullptr;
-    if (flowgrad && (!grad_flow || !mask_pre || !mask_x_lo || !occl || height <= 0 || width <= 0 || height > image_size ||
-                     width > image_size || split < 0 || split > batch_size || (split < batch_size && !mask_x_hi)))
-        return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (!(flags & MR_FLAG_OUTPUT_ZEROED)) {  // (the workgroups of an image meet in global atomics on a zeroed output)
-        hipError_t e = hipMemsetAsync(grad_vcolors, 0, (size_t)batch_size * num_verts * 3 * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (num_faces == 0) return MR_OK;
-    if (!face_index_map || !weight_map || !(eps >= 1e-6f)) return MR_ERR_BADARG;
-    if (!vertex_id_map && (!verts || !faces_idx || !depth_img)) return MR_ERR_BADARG;
-    const int64_t table_bytes = (((int64_t)num_verts * (flowgrad ? 2 : 3) + 1) / 2) * 16;
-    // the tile walk reads 4-pixel groups with 16-byte loads and keeps the colour table in LDS
-    if (image_size % 4 != 0 || table_bytes > SV_MAX_TABLE_BYTES ||
-        (int64_t)((image_size + ST_TW - 1) / ST_TW) * ((image_size + ST_TH - 1) / ST_TH) > ST_MAX_TILES)
-        return MR_ERR_NOTIMPL;
     ScatterTilesParams sp{};
     sp.g = GatherVCParams{verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces,
                           fill_back, image_size, eps, texel_layout};
     sp.weight = weight_map; sp.depth = depth_img; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.grad_flow = grad_flow; sp.m_pre = mask_pre; sp.m_x_lo = mask_x_lo; sp.m_x_hi = mask_x_hi; sp.occl = occl;
     sp.split = split; sp.H = height; sp.W = width;
-    sp.tiles_x = (image_size + ST_TW - 1) / ST_TW; sp.tiles_y = (image_size + ST_TH - 1) / ST_TH;
     sp.grad_bound = flowgrad ? grad_bound : nullptr;
-    sp.groups = ST_G;
-    const int64_t blocks = (int64_t)batch_size * sp.groups;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
+    const bool args_ok = !flowgrad || (grad_flow && mask_pre && mask_x_lo && occl && height > 0 && width > 0 && height <= image_size &&
+                                       width <= image_size && split >= 0 && split <= batch_size && (split == batch_size || mask_x_hi));
     auto kernel = vertex_id_map ? (flowgrad ? scatter_tiles_kernel<true, true> : scatter_tiles_kernel<false, true>)
                                 : (flowgrad ? scatter_tiles_kernel<true, false> : scatter_tiles_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch_scatter_tiles(sp, flags, false, args_ok, vertex_id_map || (verts && faces_idx && depth_img), kernel,
+                                (hipStream_t)stream);
 }
 
 extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
@@ -2599,48 +2620,21 @@ extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, c
                                                 int fill_back, int image_size, float eps, float pair_thresh, int flags,
                                                 int texel_layout, mr_stream_t stream, int criterion) {
     if (criterion != MR_CRITERION_L1 && criterion != MR_CRITERION_L2) return MR_ERR_BADARG;
-    if (batch_size < 0 || (batch_size & 1) || num_faces < 0 || num_verts < 0 || image_size <= 0 || !texel_layout_ok(texel_layout))
-        return MR_ERR_BADARG;
-    if (!grad_vcolors && (int64_t)batch_size * num_verts > 0) return MR_ERR_BADARG;
-    if (batch_size == 0 || num_verts == 0) return MR_OK;
-    if (!flows || !image_ref || !image || !jitter_ref || !jitter || !sums || !grad_loss_fwd || !mask_pre || !mask_x_lo ||
-        !mask_x_hi || !occl || !grad_flow_scratch || !tile_hit)
-        return MR_ERR_BADARG;
-    if (jitter_channels != 1 && jitter_channels != 3) return MR_ERR_BADARG;
-    if (height <= 0 || width < 2 || height > image_size || width > image_size || (int64_t)height * width > (1LL << 29))
-        return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (!(flags & MR_FLAG_OUTPUT_ZEROED)) {
-        hipError_t e = hipMemsetAsync(grad_vcolors, 0, (size_t)batch_size * num_verts * 3 * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (num_faces == 0) return MR_OK;
-    if (!face_index_map || !weight_map || !vertex_id_map || !(eps >= 1e-6f)) return MR_ERR_BADARG;
-    const int64_t table_bytes = (((int64_t)num_verts * 2 + 1) / 2) * 16;
-    if (image_size % 4 != 0 || table_bytes > SV_MAX_TABLE_BYTES ||
-        (int64_t)((image_size + ST_TW - 1) / ST_TW) * ((image_size + ST_TH - 1) / ST_TH) > ST_MAX_TILES)
-        return MR_ERR_NOTIMPL;
     ScatterTilesParams sp{};
     sp.g = GatherVCParams{nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces,
                           fill_back, image_size, eps, texel_layout};
     sp.weight = weight_map; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.m_pre = mask_pre; sp.m_x_lo = mask_x_lo; sp.m_x_hi = mask_x_hi; sp.occl = occl;
     sp.split = batch_size / 2; sp.H = height; sp.W = width;
-    sp.tiles_x = (image_size + ST_TW - 1) / ST_TW; sp.tiles_y = (image_size + ST_TH - 1) / ST_TH;
-    // workgroups per image: pass 1 (the pair loss's backward) walks a workgroup's tiles two at a time, one behind the other
-    // -- larger rasters have more covered tiles per image (a sixth of 256 / 900 / 1600), so they get more workgroups:
-    // ~8 tiles each (a 480 x 480 pair at B = 8: 73 -> 46 us with 32 instead of 8)
-    sp.groups = ST_G;
-    while (sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
     sp.stash = grad_flow_scratch; sp.flow = flows; sp.image_ref = image_ref; sp.image = image; sp.jitter_ref = jitter_ref;
     sp.jitter = jitter; sp.Cj = jitter_channels; sp.sums = sums; sp.gl_fwd = grad_loss_fwd; sp.gl_bwd = grad_loss_bwd;
     sp.pair_thresh = pair_thresh;
-    const int64_t blocks = (int64_t)batch_size * sp.groups;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-    hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_scatter_tiles_l2_kernel : pair_scatter_tiles_kernel,
-                       dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    const bool args_ok = flows && image_ref && image && jitter_ref && jitter && sums && grad_loss_fwd && mask_pre && mask_x_lo &&
+                         mask_x_hi && occl && grad_flow_scratch && tile_hit && (jitter_channels == 1 || jitter_channels == 3) &&
+                         height > 0 && width >= 2 && height <= image_size && width <= image_size &&
+                         (int64_t)height * width <= (1LL << 29);
+    return launch_scatter_tiles(sp, flags, true, args_ok, vertex_id_map != nullptr,
+                                criterion == MR_CRITERION_L2 ? pair_scatter_tiles_l2_kernel : pair_scatter_tiles_kernel, (hipStream_t)stream);
 }
 
 extern "C" int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
@@ -2659,57 +2653,22 @@ extern "C" int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const 
                                             MR_CRITERION_L1);
 }
 
-// mr_flow_pair_backward_unit_tiles with the two extra incoming gradients of mr_pair_step_backward (pair_step.hip): of
-// loss_bwd + loss_fwd and of the batch mean (ScatterTilesParams::gl_sum / gl_mean)
-int mr_flow_pair_backward_unit_tiles_ex(const int32_t* face_index_map, const uint32_t* tile_hit,
-                                        const float* weight_map, const int32_t* vertex_id_map, const float* unit_grad,
-                                        const float* unit_grad_max, const float* sums, const float* grad_loss_fwd,
-                                        const float* grad_loss_bwd, const float* grad_loss_sum, const float* grad_mean,
-                                        int mean_of, int height, int width, float* grad_vcolors,
-                                        int batch_size, int num_verts, int num_faces, int fill_back, int image_size,
-                                        float eps, int flags, int texel_layout, const void* scatter_work,
-                                        mr_stream_t stream) {
-    if (batch_size < 0 || (batch_size & 1) || num_faces < 0 || num_verts < 0 || image_size <= 0 || !texel_layout_ok(texel_layout))
-        return MR_ERR_BADARG;
-    if (!grad_vcolors && (int64_t)batch_size * num_verts > 0) return MR_ERR_BADARG;
-    if (batch_size == 0 || num_verts == 0) return MR_OK;
-    if (!unit_grad || !unit_grad_max || !sums || !(grad_loss_fwd || grad_loss_sum || grad_mean) || !tile_hit) return MR_ERR_BADARG;
-    if (height <= 0 || width < 2 || height > image_size || width > image_size || (int64_t)height * width > (1LL << 29))
-        return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (!(flags & MR_FLAG_OUTPUT_ZEROED)) {
-        hipError_t e = hipMemsetAsync(grad_vcolors, 0, (size_t)batch_size * num_verts * 3 * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (num_faces == 0) return MR_OK;
-    if (!face_index_map || !weight_map || !vertex_id_map || !(eps >= 1e-6f)) return MR_ERR_BADARG;
-    const int64_t table_bytes = (((int64_t)num_verts * 2 + 1) / 2) * 16;
-    if (image_size % 4 != 0 || table_bytes > SV_MAX_TABLE_BYTES ||
-        (int64_t)((image_size + ST_TW - 1) / ST_TW) * ((image_size + ST_TH - 1) / ST_TH) > ST_MAX_TILES)
-        return MR_ERR_NOTIMPL;
+int mr::launch_unit_scatter_tiles(const UnitScatterArgs& a, hipStream_t s) {
     ScatterTilesParams sp{};
-    sp.g = GatherVCParams{nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces,
-                          fill_back, image_size, eps, texel_layout};
-    sp.weight = weight_map; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
-    sp.split = batch_size / 2; sp.H = height; sp.W = width;
-    sp.tiles_x = (image_size + ST_TW - 1) / ST_TW; sp.tiles_y = (image_size + ST_TH - 1) / ST_TH;
-    // workgroups per image: a wave takes a covered tile per round, and larger rasters have more of them per image (a sixth of
-    // 256 / 900 / 1600 tiles): 8 / 32 / 32 -- a 480 x 480 pair at B = 8: 30 -> 19 us, 640 x 640 at B = 32: 86 -> 74 us cold
-    sp.groups = ST_G;
-    while (sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
-    sp.unit_grad = unit_grad; sp.unit_max = unit_grad_max; sp.sums = sums; sp.gl_fwd = grad_loss_fwd; sp.gl_bwd = grad_loss_bwd;
-    sp.gl_sum = grad_loss_sum; sp.gl_mean = grad_mean; sp.mean_div = (float)(batch_size / 2); sp.mean_of = mean_of;
-    const int64_t blocks = (int64_t)batch_size * sp.groups;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-    // (the covered-tile lists need the workgroup split's head room: grid > images)
-    if (scatter_work && sp.groups >= 2) {
-        sp.work = scatter_work_at(const_cast<void*>(scatter_work), batch_size);
-        hipLaunchKernelGGL(unit_scatter_tiles_kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
-    } else {
-        hipLaunchKernelGGL(unit_scatter_listing_kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
-    }
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    sp.g = GatherVCParams{nullptr, nullptr, a.face_index_map, nullptr, a.grad_vcolors, a.batch_size, a.num_verts, a.num_faces,
+                          a.fill_back, a.image_size, a.eps, a.texel_layout};
+    sp.weight = a.weight_map; sp.tile_hit = a.tile_hit; sp.vid_map = a.vertex_id_map;
+    sp.split = a.batch_size / 2; sp.H = a.height; sp.W = a.width;
+    sp.unit_grad = a.unit_grad; sp.unit_max = a.unit_grad_max; sp.sums = a.sums; sp.gl_fwd = a.grad_loss_fwd; sp.gl_bwd = a.grad_loss_bwd;
+    sp.gl_sum = a.grad_loss_sum; sp.gl_mean = a.grad_mean; sp.mean_div = (float)(a.batch_size / 2); sp.mean_of = a.mean_of;
+    const bool args_ok = a.unit_grad && a.unit_grad_max && a.sums && (a.grad_loss_fwd || a.grad_loss_sum || a.grad_mean) && a.tile_hit &&
+                         a.height > 0 && a.width >= 2 && a.height <= a.image_size && a.width <= a.image_size &&
+                         (int64_t)a.height * a.width <= (1LL << 29);
+    // (the covered-tile lists need the workgroup split's head room, grid > images: every launch has ST_G or more per image)
+    static_assert(ST_G >= 2, "unit_scatter_tiles_kernel splits an image's covered tiles over its workgroups");
+    if (a.scatter_work) sp.work = scatter_work_at(const_cast<void*>(a.scatter_work), a.batch_size);
+    return launch_scatter_tiles(sp, a.flags, true, args_ok, a.vertex_id_map != nullptr,
+                                a.scatter_work ? unit_scatter_tiles_kernel : unit_scatter_listing_kernel, s);
 }
 
 extern "C" int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, const uint32_t* tile_hit,
@@ -2720,10 +2679,13 @@ extern "C" int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, c
                                                 float eps, int flags, int texel_layout, const void* scatter_work,
                                                 mr_stream_t stream) {
     if (!grad_loss_fwd && (int64_t)batch_size * num_verts > 0) return MR_ERR_BADARG;
-    return mr_flow_pair_backward_unit_tiles_ex(face_index_map, tile_hit, weight_map, vertex_id_map, unit_grad, unit_grad_max, sums,
-                                               grad_loss_fwd, grad_loss_bwd, nullptr, nullptr, 0, height, width, grad_vcolors,
-                                               batch_size, num_verts, num_faces, fill_back, image_size, eps, flags, texel_layout,
-                                               scatter_work, stream);
+    UnitScatterArgs a{};
+    a.face_index_map = face_index_map; a.tile_hit = tile_hit; a.weight_map = weight_map; a.vertex_id_map = vertex_id_map;
+    a.unit_grad = unit_grad; a.unit_grad_max = unit_grad_max; a.sums = sums; a.grad_loss_fwd = grad_loss_fwd; a.grad_loss_bwd = grad_loss_bwd;
+    a.height = height; a.width = width; a.grad_vcolors = grad_vcolors;
+    a.batch_size = batch_size; a.num_verts = num_verts; a.num_faces = num_faces; a.fill_back = fill_back; a.image_size = image_size;
+    a.eps = eps; a.flags = flags; a.texel_layout = texel_layout; a.scatter_work = scatter_work;
+    return launch_unit_scatter_tiles(a, (hipStream_t)stream);
 }
 
 extern "C" int mr_pixel_map_terms(uint64_t* terms_host, int reset) {

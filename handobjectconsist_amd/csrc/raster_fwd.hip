@@ -51,7 +51,7 @@
 #include <algorithm>
 
 #include "mr_common.hpp"
-#include "vertex_stage_device.hpp"
+#include "pair_launch.hpp"
 
 namespace mr {
 
@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(256) face_records_kernel(BinParams p) {
 // below).  The last arriver also re-zeroes the counter for the next launch.
 // The order of the records inside a bin's list differs from the one-workgroup order -- as it already does from run to run (LDS
 // atomics) -- and the image does not depend on it (z-buffer keys).
-// PROLOGUE (round 6, pair steps: mr_render_flow_forward_pair): the vertex stage of the frame pair runs HERE instead of in a
+// PROLOGUE (round 6, pair steps: FlowRenderArgs::pro): the vertex stage of the frame pair runs HERE instead of in a
 // launch of its own in front (pair_prologue_kernel, 7.4 us for 2B = 128 meshes -- most of it a launch's floor).  The
 // workgroup(s) of stack image b project the image's vertices into LDS (both frames' 2-D projections for the flow colour, the
 // image's own frame through nr.projection: pair_vertex_of_frame -- vertex_stage_device.hpp, the arithmetic of
@@ -1851,19 +1851,6 @@ extern "C" int mr_render_vc_forward(const float* verts, const int32_t* faces_idx
     return launch_tiles<true, true>(p, s);
 }
 
-// mr_render_flow_forward of the 2B stacked meshes of a frame pair whose vertex stage has NOT run yet (mr_pair_step_forward,
-// pair_step.hip): `verts` (unused where the stage runs inside the binning pass), `faces_idx` and `vcolors` are the buffers that
-// stage fills -- pro->v.ndc1 / cols12 and pro->f.out point into them
-int mr_render_flow_forward_pair(const float* verts, const int32_t* faces_idx, const float* vcolors,
-                                const float* background, int bg_stride, const float* keep_lut, int n_lut,
-                                float alpha_thresh, float* rgb_img, float* alpha_img, float* mask_img,
-                                float* depth_img, float* weight_map, int32_t* face_index_map, uint8_t* tile_hit,
-                                void* workspace, int64_t workspace_bytes, int batch_size,
-                                int num_verts, int num_faces, int fill_back, int image_size, float near_,
-                                float far_, float eps, int flags, int32_t* vertex_id_map, int tile_bound,
-                                uint32_t* tile_count_out, float* zero_fill, int64_t zero_fill_count,
-                                int texel_layout, mr_stream_t stream, const mr::PairPrologue* pro, void* records);
-
 extern "C" int mr_render_flow_forward(const float* verts, const int32_t* faces_idx, const float* vcolors,
                                       const float* background, int bg_stride, const float* keep_lut, int n_lut,
                                       float alpha_thresh, float* rgb_img, float* alpha_img, float* mask_img,
@@ -1873,67 +1860,62 @@ extern "C" int mr_render_flow_forward(const float* verts, const int32_t* faces_i
                                       float far_, float eps, int flags, int32_t* vertex_id_map, int tile_bound,
                                       uint32_t* tile_count_out, float* zero_fill, int64_t zero_fill_count,
                                       int texel_layout, mr_stream_t stream) {
-    return mr_render_flow_forward_pair(verts, faces_idx, vcolors, background, bg_stride, keep_lut, n_lut, alpha_thresh, rgb_img,
-                                       alpha_img, mask_img, depth_img, weight_map, face_index_map, tile_hit, workspace,
-                                       workspace_bytes, batch_size, num_verts, num_faces, fill_back, image_size, near_, far_, eps,
-                                       flags, vertex_id_map, tile_bound, tile_count_out, zero_fill, zero_fill_count, texel_layout,
-                                       stream, nullptr, nullptr);
+    FlowRenderArgs a{};
+    a.verts = verts; a.faces_idx = faces_idx; a.vcolors = vcolors; a.background = background; a.bg_stride = bg_stride;
+    a.keep_lut = keep_lut; a.n_lut = n_lut; a.alpha_thresh = alpha_thresh;
+    a.rgb_img = rgb_img; a.alpha_img = alpha_img; a.mask_img = mask_img; a.depth_img = depth_img; a.weight_map = weight_map;
+    a.face_index_map = face_index_map; a.tile_hit = tile_hit; a.vertex_id_map = vertex_id_map;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.batch_size = batch_size; a.num_verts = num_verts; a.num_faces = num_faces; a.fill_back = fill_back; a.image_size = image_size;
+    a.near_ = near_; a.far_ = far_; a.eps = eps; a.flags = flags; a.tile_bound = tile_bound; a.texel_layout = texel_layout;
+    a.tile_count_out = tile_count_out; a.zero_fill = zero_fill; a.zero_fill_count = zero_fill_count;
+    return launch_flow_render(a, (hipStream_t)stream);
 }
 
-int mr_render_flow_forward_pair(const float* verts, const int32_t* faces_idx, const float* vcolors,
-                                const float* background, int bg_stride, const float* keep_lut, int n_lut,
-                                float alpha_thresh, float* rgb_img, float* alpha_img, float* mask_img,
-                                float* depth_img, float* weight_map, int32_t* face_index_map, uint8_t* tile_hit,
-                                void* workspace, int64_t workspace_bytes, int batch_size,
-                                int num_verts, int num_faces, int fill_back, int image_size, float near_,
-                                float far_, float eps, int flags, int32_t* vertex_id_map, int tile_bound,
-                                uint32_t* tile_count_out, float* zero_fill, int64_t zero_fill_count,
-                                int texel_layout, mr_stream_t stream, const mr::PairPrologue* pro, void* records) {
-    const int F = fill_back ? 2 * num_faces : num_faces;
-    if (!texel_layout_ok(texel_layout)) return MR_ERR_BADARG;
-    if (batch_size < 0 || num_faces < 0 || num_verts < 0 || image_size <= 0 || image_size > 16384) return MR_ERR_BADARG;
-    if (((!verts || !faces_idx || !vcolors) && num_faces > 0) || !face_index_map || !workspace) return MR_ERR_BADARG;
-    if (vertex_id_map && !weight_map) return MR_ERR_BADARG;
-    // (`records`: [B,is,is] 16-byte records {colour 0, colour 1, alpha, mask} in place of the three planes -- listed sparse
-    // launches only: the dense background stream writes planes)
-    if (records ? (rgb_img || alpha_img || mask_img || ((uintptr_t)records & 15) || !(flags & MR_FLAG_SPARSE_TILES) || tile_bound == 0)
-                : (!rgb_img || !alpha_img || !mask_img))
+int mr::launch_flow_render(const FlowRenderArgs& a, hipStream_t s) {
+    const int F = a.fill_back ? 2 * a.num_faces : a.num_faces;
+    if (!texel_layout_ok(a.texel_layout)) return MR_ERR_BADARG;
+    if (a.batch_size < 0 || a.num_faces < 0 || a.num_verts < 0 || a.image_size <= 0 || a.image_size > 16384) return MR_ERR_BADARG;
+    if (((!a.verts || !a.faces_idx || !a.vcolors) && a.num_faces > 0) || !a.face_index_map || !a.workspace) return MR_ERR_BADARG;
+    if (a.vertex_id_map && !a.weight_map) return MR_ERR_BADARG;
+    if (a.records ? (a.rgb_img || a.alpha_img || a.mask_img || ((uintptr_t)a.records & 15) || !(a.flags & MR_FLAG_SPARSE_TILES) || a.tile_bound == 0)
+                  : (!a.rgb_img || !a.alpha_img || !a.mask_img))
         return MR_ERR_BADARG;
-    if (!background || !(eps >= 1e-6f)) return MR_ERR_BADARG;
-    if ((bg_stride != 0 && bg_stride != 3) || (keep_lut && n_lut <= 0)) return MR_ERR_BADARG;
-    if (workspace_bytes < mr_render_workspace_bytes(batch_size, F, image_size)) return MR_ERR_BADARG;
-    if (zero_fill_count < 0 || (zero_fill_count > 0 && !zero_fill)) return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (batch_size == 0) {
-        if (zero_fill && zero_fill_count > 0) return (int)hipMemsetAsync(zero_fill, 0, (size_t)zero_fill_count * sizeof(float), s);
+    if (!a.background || !(a.eps >= 1e-6f)) return MR_ERR_BADARG;
+    if ((a.bg_stride != 0 && a.bg_stride != 3) || (a.keep_lut && a.n_lut <= 0)) return MR_ERR_BADARG;
+    if (a.workspace_bytes < mr_render_workspace_bytes(a.batch_size, F, a.image_size)) return MR_ERR_BADARG;
+    if (a.zero_fill_count < 0 || (a.zero_fill_count > 0 && !a.zero_fill)) return MR_ERR_BADARG;
+    if (a.batch_size == 0) {
+        if (a.zero_fill && a.zero_fill_count > 0) return (int)hipMemsetAsync(a.zero_fill, 0, (size_t)a.zero_fill_count * sizeof(float), s);
         return MR_OK;
     }
-    if (batch_size > 65535) return MR_ERR_BADARG;
-    if (pro && ((batch_size & 1) || pro->v.B * 2 != batch_size || pro->v.V != num_verts || pro->f.Fh + pro->f.Fo != num_faces))
+    if (a.batch_size > 65535) return MR_ERR_BADARG;
+    const PairPrologue* pro = a.pro;
+    if (pro && ((a.batch_size & 1) || pro->v.B * 2 != a.batch_size || pro->v.V != a.num_verts || pro->f.Fh + pro->f.Fo != a.num_faces))
         return MR_ERR_BADARG;
     FwdParams p{};
     BinParams bp{};
-    bp.verts = verts; bp.fidx = faces_idx; bp.V = num_verts; bp.F0 = num_faces; bp.fill_back = fill_back;
-    bp.zero_fill = zero_fill_count > 0 ? zero_fill : nullptr; bp.zero_count = zero_fill_count;
-    if ((flags & MR_FLAG_SPARSE_TILES) && !tile_hit) return MR_ERR_BADARG;
-    const bool listed = (flags & MR_FLAG_SPARSE_TILES) && tile_bound != 0;
-    const int rc = launch_bins<true>(bp, p, workspace, batch_size, F, image_size, s, flags, listed ? tile_hit : nullptr, false,
-                                     (flags & MR_FLAG_TILE_LIST_CLEARED) != 0, pro);
+    bp.verts = a.verts; bp.fidx = a.faces_idx; bp.V = a.num_verts; bp.F0 = a.num_faces; bp.fill_back = a.fill_back;
+    bp.zero_fill = a.zero_fill_count > 0 ? a.zero_fill : nullptr; bp.zero_count = a.zero_fill_count;
+    if ((a.flags & MR_FLAG_SPARSE_TILES) && !a.tile_hit) return MR_ERR_BADARG;
+    const bool listed = (a.flags & MR_FLAG_SPARSE_TILES) && a.tile_bound != 0;
+    const int rc = launch_bins<true>(bp, p, a.workspace, a.batch_size, F, a.image_size, s, a.flags, listed ? a.tile_hit : nullptr, false,
+                                     (a.flags & MR_FLAG_TILE_LIST_CLEARED) != 0, pro);
     if (rc != MR_OK) return rc;
-    p.tile_count_out = p.tlist ? tile_count_out : nullptr;
-    p.background = background; p.bg_stride = bg_stride;
-    p.rgb = rgb_img; p.rgb_channels = 2;
-    p.alpha = alpha_img; p.mask = mask_img; p.rec4 = (float4*)records;
-    if (records && !p.tlist) return MR_ERR_NOTIMPL;  // (no tile list for this raster: pair_step_layout has asked before)
-    p.depth = depth_img; p.weight = weight_map; p.sparse_wd = 1; p.tile_hit = tile_hit; p.vid_map = vertex_id_map;
-    p.sparse_tiles = (flags & MR_FLAG_SPARSE_TILES) ? 1 : 0;
-    if (p.sparse_tiles && !tile_hit) return MR_ERR_BADARG;
-    p.keep_lut = keep_lut; p.n_lut = n_lut; p.alpha_thresh = alpha_thresh;
-    p.fim = face_index_map;
-    p.B = batch_size; p.F = F; p.is = image_size; p.ts = 2;
-    p.near_ = near_; p.far_ = far_; p.eps = eps;
-    p.verts = verts; p.fidx = faces_idx; p.vcolors = vcolors; p.V = num_verts; p.F0 = num_faces;
-    p.texel = texel_layout;
-    p.plain_div = (flags & MR_FLAG_PLAIN_DIVISIONS) ? 1 : 0;
-    return launch_tiles<true, true>(p, s, tile_bound);
+    p.tile_count_out = p.tlist ? a.tile_count_out : nullptr;
+    p.background = a.background; p.bg_stride = a.bg_stride;
+    p.rgb = a.rgb_img; p.rgb_channels = 2;
+    p.alpha = a.alpha_img; p.mask = a.mask_img; p.rec4 = (float4*)a.records;
+    if (a.records && !p.tlist) return MR_ERR_NOTIMPL;  // (no tile list for this raster: pair_step_layout has asked before)
+    p.depth = a.depth_img; p.weight = a.weight_map; p.sparse_wd = 1; p.tile_hit = a.tile_hit; p.vid_map = a.vertex_id_map;
+    p.sparse_tiles = (a.flags & MR_FLAG_SPARSE_TILES) ? 1 : 0;
+    if (p.sparse_tiles && !a.tile_hit) return MR_ERR_BADARG;
+    p.keep_lut = a.keep_lut; p.n_lut = a.n_lut; p.alpha_thresh = a.alpha_thresh;
+    p.fim = a.face_index_map;
+    p.B = a.batch_size; p.F = F; p.is = a.image_size; p.ts = 2;
+    p.near_ = a.near_; p.far_ = a.far_; p.eps = a.eps;
+    p.verts = a.verts; p.fidx = a.faces_idx; p.vcolors = a.vcolors; p.V = a.num_verts; p.F0 = a.num_faces;
+    p.texel = a.texel_layout;
+    p.plain_div = (a.flags & MR_FLAG_PLAIN_DIVISIONS) ? 1 : 0;
+    return launch_tiles<true, true>(p, s, a.tile_bound);
 }

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "mr_common.hpp"
+#include "pair_launch.hpp"
 #include "warp_device.hpp"
 
 namespace mr {
@@ -1096,6 +1097,27 @@ extern "C" int64_t mr_pair_consist_workspace_bytes(int batch_size, int height, i
 // MR_CRITERION_* -> is it one the pair kernels are instantiated for
 static inline bool criterion_ok(int criterion) { return criterion == MR_CRITERION_L1 || criterion == MR_CRITERION_L2; }
 
+// What mr_pair_consist_forward_crit and _backward_crit share: the argument checks (`ptrs_ok`: the caller's own pointers and
+// workspace; every refusal is MR_ERR_BADARG, so their order does not show) and the tile arithmetic of the launch.
+struct PairGrid {
+    int tiles_x, nblk;             // 64 x 4 pixel tiles per row / per image
+    int hit_tiles_x, hit_stride;   // coverage bytes: tiles per raster row, bytes per image
+};
+static int pair_consist_grid(bool ptrs_ok, int criterion, int jitter_channels, int batch_size, int height, int width, bool has_hit,
+                             int hit_image_size, PairGrid& g) {
+    if (!criterion_ok(criterion) || !ptrs_ok) return MR_ERR_BADARG;
+    if (has_hit && (hit_image_size < height || hit_image_size < width)) return MR_ERR_BADARG;
+    if (jitter_channels != 1 && jitter_channels != 3) return MR_ERR_BADARG;
+    if (batch_size < 0 || height <= 0 || width <= 0) return MR_ERR_BADARG;
+    if (width < 2 || (int64_t)height * width > (1LL << 29)) return MR_ERR_BADARG;  // row-pair taps, 32-bit byte offsets
+    g.tiles_x = (width + PT_W - 1) / PT_W;
+    g.nblk = g.tiles_x * ((height + PT_H - 1) / PT_H);
+    if ((int64_t)g.nblk * batch_size > 0x7fffffffLL) return MR_ERR_BADARG;
+    g.hit_tiles_x = (hit_image_size + 31) / 32;
+    g.hit_stride = g.hit_tiles_x * ((hit_image_size + 7) / 8) * 4;
+    return MR_OK;
+}
+
 extern "C" int mr_pair_consist_forward_crit(const float* flow12, const float* flow21, const float* image_ref,
                                             const float* image, const float* jitter_ref, const float* jitter,
                                             int jitter_channels, void* workspace, int64_t workspace_bytes,
@@ -1105,22 +1127,16 @@ extern "C" int mr_pair_consist_forward_crit(const float* flow12, const float* fl
                                             int batch_size, int height, int width, float thresh,
                                             const uint8_t* tile_hit12, const uint8_t* tile_hit21, int hit_image_size,
                                             mr_stream_t stream, int criterion) {
-    if (!criterion_ok(criterion)) return MR_ERR_BADARG;
-    if (!flow12 || !flow21 || !image_ref || !image || !jitter_ref || !jitter || !workspace || !sums)
-        return MR_ERR_BADARG;
-    if ((tile_hit12 || tile_hit21) && (hit_image_size < height || hit_image_size < width)) return MR_ERR_BADARG;
-    if (jitter_channels != 1 && jitter_channels != 3) return MR_ERR_BADARG;
-    if (batch_size < 0 || height <= 0 || width <= 0) return MR_ERR_BADARG;
-    if (workspace_bytes < mr_pair_consist_workspace_bytes(batch_size, height, width)) return MR_ERR_BADARG;
-    if (width < 2 || (int64_t)height * width > (1LL << 29)) return MR_ERR_BADARG;  // row-pair taps, 32-bit byte offsets
-    if (batch_size == 0) return MR_OK;
-    const int tiles_x = (width + PT_W - 1) / PT_W;
-    const int nblk = tiles_x * ((height + PT_H - 1) / PT_H);
-    if ((int64_t)nblk * batch_size > 0x7fffffffLL) return MR_ERR_BADARG;
+    PairGrid g;
+    const int rc = pair_consist_grid(flow12 && flow21 && image_ref && image && jitter_ref && jitter && workspace && sums &&
+                                         workspace_bytes >= mr_pair_consist_workspace_bytes(batch_size, height, width),
+                                     criterion, jitter_channels, batch_size, height, width, tile_hit12 || tile_hit21, hit_image_size, g);
+    if (rc != MR_OK || batch_size == 0) return rc;
+    const int nblk = g.nblk;
     PairParams p{flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, (float*)workspace,
                  full_mask1, full_mask2, warp_mask1, warp_mask2, warp1, warp2, diff1, diff2,
-                 batch_size, height, width, nblk, tiles_x, thresh, tile_hit12, tile_hit21, hit_image_size,
-                 (hit_image_size + 31) / 32, ((hit_image_size + 31) / 32) * ((hit_image_size + 7) / 8) * 4};
+                 batch_size, height, width, nblk, g.tiles_x, thresh, tile_hit12, tile_hit21, hit_image_size,
+                 g.hit_tiles_x, g.hit_stride};
     hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_consist_forward_l2_kernel : pair_consist_forward_kernel,
                        dim3((unsigned)(nblk * batch_size)), dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
@@ -1152,22 +1168,16 @@ extern "C" int mr_pair_consist_backward_crit(const float* flow12, const float* f
                                              int batch_size, int height, int width, float thresh,
                                              const uint8_t* tile_hit12, const uint8_t* tile_hit21, int hit_image_size,
                                              float* grad_max, mr_stream_t stream, int criterion) {
-    if (!criterion_ok(criterion)) return MR_ERR_BADARG;
-    if (!flow12 || !flow21 || !image_ref || !image || !jitter_ref || !jitter || !sums || !grad_loss_fwd ||
-        !grad_flow12 || !grad_flow21)
-        return MR_ERR_BADARG;
-    if ((tile_hit12 || tile_hit21) && (hit_image_size < height || hit_image_size < width)) return MR_ERR_BADARG;
-    if (jitter_channels != 1 && jitter_channels != 3) return MR_ERR_BADARG;
-    if (batch_size < 0 || height <= 0 || width <= 0) return MR_ERR_BADARG;
-    if (width < 2 || (int64_t)height * width > (1LL << 29)) return MR_ERR_BADARG;  // row-pair taps, 32-bit byte offsets
-    if (batch_size == 0) return MR_OK;
-    const int tiles_x = (width + PT_W - 1) / PT_W;
-    const int nblk = tiles_x * ((height + PT_H - 1) / PT_H);
-    if ((int64_t)nblk * batch_size > 0x7fffffffLL) return MR_ERR_BADARG;
+    PairGrid g;
+    const int rc = pair_consist_grid(flow12 && flow21 && image_ref && image && jitter_ref && jitter && sums && grad_loss_fwd &&
+                                         grad_flow12 && grad_flow21,
+                                     criterion, jitter_channels, batch_size, height, width, tile_hit12 || tile_hit21, hit_image_size, g);
+    if (rc != MR_OK || batch_size == 0) return rc;
+    const int nblk = g.nblk;
     PairBwdParams p{flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, sums,
                     grad_loss_fwd, grad_loss_bwd, grad_flow12, grad_flow21, batch_size, height, width, nblk,
-                    tiles_x, thresh, tile_hit12, tile_hit21, hit_image_size, (hit_image_size + 31) / 32,
-                    ((hit_image_size + 31) / 32) * ((hit_image_size + 7) / 8) * 4, reinterpret_cast<unsigned*>(grad_max)};
+                    g.tiles_x, thresh, tile_hit12, tile_hit21, hit_image_size, g.hit_tiles_x, g.hit_stride,
+                    reinterpret_cast<unsigned*>(grad_max)};
     hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_consist_backward_l2_kernel : pair_consist_backward_kernel,
                        dim3((unsigned)((nblk * batch_size + PT_SUB - 1) / PT_SUB)), dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
@@ -1283,10 +1293,12 @@ extern "C" int64_t mr_flow_pair_scatter_work_bytes(int batch_size, int image_siz
     return scatter_work_bytes(2 * batch_size, ((image_size + 31) / 32) * ((image_size + 7) / 8));
 }
 
+// the checks the listed pair-loss launches share; `p` (mr_pair_consist_*_tiles): gets the PairTilesParams fields they share
 static int pair_tiles_args_ok(const float* flow12, const float* flow21, const float* image_ref, const float* image,
                               const float* jitter_ref, const float* jitter, int jitter_channels, int batch_size, int height,
                               int width, const uint8_t* tile_hit12, const uint8_t* tile_hit21, int hit_image_size,
-                              const void* list_header, const void* list_entries, int64_t list_capacity) {
+                              const void* list_header, const void* list_entries, int64_t list_capacity, float thresh = 0.0f,
+                              PairTilesParams* p = nullptr) {
     if (!flow12 || !flow21 || !image_ref || !image || !jitter_ref || !jitter || !tile_hit12 || !tile_hit21 || !list_header ||
         !list_entries)
         return MR_ERR_BADARG;
@@ -1295,6 +1307,14 @@ static int pair_tiles_args_ok(const float* flow12, const float* flow21, const fl
     if (width < 2 || (int64_t)height * width > (1LL << 29)) return MR_ERR_BADARG;  // row-pair taps, 32-bit byte offsets
     const int64_t T = (int64_t)((hit_image_size + 31) / 32) * ((hit_image_size + 7) / 8);
     if (list_capacity != 2LL * batch_size * T || list_capacity > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (!p) return MR_OK;
+    p->flow[0] = flow12; p->flow[1] = flow21;
+    p->image_ref = image_ref; p->image = image; p->jitter_ref = jitter_ref; p->jitter = jitter; p->Cj = jitter_channels;
+    p->hit[0] = tile_hit12; p->hit[1] = tile_hit21;
+    p->B = batch_size; p->H = height; p->W = width; p->is = hit_image_size;
+    p->tiles_x = (hit_image_size + 31) / 32; p->tiles_y = (hit_image_size + 7) / 8;
+    p->thresh = thresh;
+    p->list = ListArgs{(const TileList*)list_header, (const uint4*)list_entries, (unsigned)list_capacity};
     return MR_OK;
 }
 
@@ -1306,21 +1326,14 @@ extern "C" int mr_pair_consist_forward_tiles_crit(const float* flow12, const flo
                                                   int hit_image_size, const void* list_header, const void* list_entries,
                                                   int64_t list_capacity, int64_t tile_bound, mr_stream_t stream, int criterion) {
     if (!criterion_ok(criterion)) return MR_ERR_BADARG;
-    const int rc = pair_tiles_args_ok(flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, batch_size, height,
-                                      width, tile_hit12, tile_hit21, hit_image_size, list_header, list_entries, list_capacity);
+    PairTilesParams p{};
+    const int rc = pair_tiles_args_ok(flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, batch_size, height, width,
+                                      tile_hit12, tile_hit21, hit_image_size, list_header, list_entries, list_capacity, thresh, &p);
     if (rc != MR_OK) return rc;
     if (!workspace || !sums || workspace_bytes < mr_pair_consist_tiles_workspace_bytes(batch_size, hit_image_size))
         return MR_ERR_BADARG;
     if (batch_size == 0) return MR_OK;
-    PairTilesParams p{};
-    p.flow[0] = flow12; p.flow[1] = flow21;
-    p.image_ref = image_ref; p.image = image; p.jitter_ref = jitter_ref; p.jitter = jitter; p.Cj = jitter_channels;
     p.partial = (float*)workspace;
-    p.hit[0] = tile_hit12; p.hit[1] = tile_hit21;
-    p.B = batch_size; p.H = height; p.W = width; p.is = hit_image_size;
-    p.tiles_x = (hit_image_size + 31) / 32; p.tiles_y = (hit_image_size + 7) / 8;
-    p.thresh = thresh;
-    p.list = ListArgs{(const TileList*)list_header, (const uint4*)list_entries, (unsigned)list_capacity};
     hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_consist_forward_tiles_l2_kernel : pair_consist_forward_tiles_kernel,
                        dim3(listed_grid(tile_bound, list_capacity)), dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
@@ -1355,19 +1368,12 @@ extern "C" int mr_pair_consist_backward_tiles_crit(const float* flow12, const fl
                                                    float* grad_max, const void* list_header, const void* list_entries,
                                                    int64_t list_capacity, int64_t tile_bound, mr_stream_t stream, int criterion) {
     if (!criterion_ok(criterion)) return MR_ERR_BADARG;
-    const int rc = pair_tiles_args_ok(flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, batch_size, height,
-                                      width, tile_hit12, tile_hit21, hit_image_size, list_header, list_entries, list_capacity);
+    PairTilesParams p{};
+    const int rc = pair_tiles_args_ok(flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, batch_size, height, width,
+                                      tile_hit12, tile_hit21, hit_image_size, list_header, list_entries, list_capacity, thresh, &p);
     if (rc != MR_OK) return rc;
     if (!sums || !grad_loss_fwd || !grad_flow12 || !grad_flow21) return MR_ERR_BADARG;
     if (batch_size == 0) return MR_OK;
-    PairTilesParams p{};
-    p.flow[0] = flow12; p.flow[1] = flow21;
-    p.image_ref = image_ref; p.image = image; p.jitter_ref = jitter_ref; p.jitter = jitter; p.Cj = jitter_channels;
-    p.hit[0] = tile_hit12; p.hit[1] = tile_hit21;
-    p.B = batch_size; p.H = height; p.W = width; p.is = hit_image_size;
-    p.tiles_x = (hit_image_size + 31) / 32; p.tiles_y = (hit_image_size + 7) / 8;
-    p.thresh = thresh;
-    p.list = ListArgs{(const TileList*)list_header, (const uint4*)list_entries, (unsigned)list_capacity};
     p.sums = sums; p.grad_loss_fwd = grad_loss_fwd; p.grad_loss_bwd = grad_loss_bwd;
     p.grad_flow[0] = grad_flow12; p.grad_flow[1] = grad_flow21;
     p.grad_max = reinterpret_cast<unsigned*>(grad_max);
@@ -1392,117 +1398,50 @@ extern "C" int mr_pair_consist_backward_tiles(const float* flow12, const float* 
 }
 
 
-static int flow_pair_forward_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,
-                                   const float* flow21, int64_t flow_bstride, const float* flow12_scale,
-                                   const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
-                                   float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
-                                   const float* image_ref, const float* image, const float* jitter_ref,
-                                   const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
-                                   float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
-                                   int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
-                                   const void* list_header, const void* list_entries, int64_t list_capacity,
-                                   int64_t tile_bound, float* unit_grad, float* unit_grad_max, float* loss_sum,
-                                   void* scatter_work, mr_stream_t stream, float* mean_out = nullptr, int mean_of = 0,
-                                   int reset_list = 0, const void* records = nullptr, int criterion = MR_CRITERION_L1) {
-    // (`records`, mr_pair_step_forward: the render's 16-byte pixel records [2B,is,is] in place of the mask / flow / scale
-    // planes, which are not looked at then; occl1 / occl2 may be NULL -- the occlusion maps are not kept)
-    if (records ? (!unit_grad || ((uintptr_t)records & 15)) : (!mask_flow1 || !mask_flow2 || !flow12 || !flow21 || !occl1 || !occl2))
+int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
+    const bool grad = a.unit_grad != nullptr;
+    if (a.records ? (!grad || ((uintptr_t)a.records & 15))
+                  : (!a.mask_flow1 || !a.mask_flow2 || !a.flow12 || !a.flow21 || !a.occl1 || !a.occl2))
         return MR_ERR_BADARG;
-    if (!flow_out12 || !flow_out21 || !criterion_ok(criterion)) return MR_ERR_BADARG;
-    if (batch_size < 0 || image_size <= 0 || (!records && flow_bstride < 2LL * image_size * image_size)) return MR_ERR_BADARG;
-    const int rc = pair_tiles_args_ok(flow_out12, flow_out21, image_ref, image, jitter_ref, jitter, jitter_channels, batch_size,
-                                      height, width, tile_hit1, tile_hit2, image_size, list_header, list_entries, list_capacity);
+    if (!a.flow_out12 || !a.flow_out21 || !criterion_ok(a.criterion)) return MR_ERR_BADARG;
+    if (a.batch_size < 0 || a.image_size <= 0 || (!a.records && a.flow_bstride < 2LL * a.image_size * a.image_size)) return MR_ERR_BADARG;
+    const int rc = pair_tiles_args_ok(a.flow_out12, a.flow_out21, a.image_ref, a.image, a.jitter_ref, a.jitter, a.jitter_channels,
+                                      a.batch_size, a.height, a.width, a.tile_hit1, a.tile_hit2, a.image_size, a.list_header,
+                                      a.list_entries, a.list_capacity);
     if (rc != MR_OK) return rc;
-    if (!workspace || !sums || workspace_bytes < mr_pair_consist_tiles_workspace_bytes(batch_size, image_size))
+    if (!a.workspace || !a.sums || a.workspace_bytes < mr_pair_consist_tiles_workspace_bytes(a.batch_size, a.image_size))
         return MR_ERR_BADARG;
-    if (batch_size == 0) return MR_OK;
-    const int tiles_x = (image_size + 31) / 32, tiles_y = (image_size + 7) / 8;
+    if (a.batch_size == 0) return MR_OK;
+    const int tiles_x = (a.image_size + 31) / 32, tiles_y = (a.image_size + 7) / 8;
+    const TileList* header = (const TileList*)a.list_header;
     FlowPairFwdParams q{};
-    q.o = OcclTilesParams{{mask_flow1, mask_flow2}, {flow12, flow21}, {flow12_scale, flow21_scale}, {occl1, occl2},
-                          {flow_out12, flow_out21}, {tile_hit1, tile_hit2}, flow_bstride, batch_size, image_size, height,
-                          width, tiles_x, tiles_y, distance_thresh, warp_thresh,
-                          {(const TileList*)list_header, (const uint4*)list_entries, (unsigned)list_capacity}};
-    q.image_ref = image_ref; q.image = image; q.jitter_ref = jitter_ref; q.jitter = jitter; q.Cj = jitter_channels;
-    q.partial = (float*)workspace; q.thresh = pair_thresh;
-    q.unit_grad = unit_grad;
-    q.tile_max = reinterpret_cast<unsigned*>(q.partial + 2LL * batch_size * tiles_x * tiles_y * 2);
-    q.rec = (const float4*)records;
+    q.o = OcclTilesParams{{a.mask_flow1, a.mask_flow2}, {a.flow12, a.flow21}, {a.flow12_scale, a.flow21_scale}, {a.occl1, a.occl2},
+                          {a.flow_out12, a.flow_out21}, {a.tile_hit1, a.tile_hit2}, a.flow_bstride, a.batch_size, a.image_size,
+                          a.height, a.width, tiles_x, tiles_y, a.distance_thresh, a.warp_thresh,
+                          {header, (const uint4*)a.list_entries, (unsigned)a.list_capacity}};
+    q.image_ref = a.image_ref; q.image = a.image; q.jitter_ref = a.jitter_ref; q.jitter = a.jitter; q.Cj = a.jitter_channels;
+    q.partial = (float*)a.workspace; q.thresh = a.pair_thresh;
+    q.unit_grad = a.unit_grad;
+    q.tile_max = reinterpret_cast<unsigned*>(q.partial + 2LL * a.batch_size * tiles_x * tiles_y * 2);
+    q.rec = (const float4*)a.records;
     // (the form -- records / unit gradient / loss only -- and the criterion are chosen here, once per launch)
-    const bool l2 = criterion == MR_CRITERION_L2;
+    const bool l2 = a.criterion == MR_CRITERION_L2;
     void (*kernel)(FlowPairFwdParams) =
-        records ? (l2 ? flow_pair_forward_tiles_l2_kernel<true, true> : flow_pair_forward_tiles_kernel<true, true>)
-        : unit_grad ? (l2 ? flow_pair_forward_tiles_l2_kernel<true> : flow_pair_forward_tiles_kernel<true>)
-                    : (l2 ? flow_pair_forward_tiles_l2_kernel<false> : flow_pair_forward_tiles_kernel<false>);
-    hipLaunchKernelGGL(kernel, dim3(listed_grid(tile_bound, list_capacity)), dim3(256), 0, (hipStream_t)stream, q);
+        a.records ? (l2 ? flow_pair_forward_tiles_l2_kernel<true, true> : flow_pair_forward_tiles_kernel<true, true>)
+        : grad    ? (l2 ? flow_pair_forward_tiles_l2_kernel<true> : flow_pair_forward_tiles_kernel<true>)
+                  : (l2 ? flow_pair_forward_tiles_l2_kernel<false> : flow_pair_forward_tiles_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3(listed_grid(a.tile_bound, a.list_capacity)), dim3(256), 0, s, q);
     MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pair_consist_finalize_tiles_kernel, dim3(batch_size), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)workspace, reinterpret_cast<const uint32_t*>(tile_hit1),
-                       reinterpret_cast<const uint32_t*>(tile_hit2), batch_size, tiles_x * tiles_y, sums, loss_fwd, loss_bwd,
-                       unit_grad ? (const unsigned*)q.tile_max : (const unsigned*)nullptr,
-                       unit_grad ? reinterpret_cast<unsigned*>(unit_grad_max) : (unsigned*)nullptr, loss_sum,
-                       scatter_work_at(unit_grad ? scatter_work : nullptr, 2 * batch_size),
+    hipLaunchKernelGGL(pair_consist_finalize_tiles_kernel, dim3(a.batch_size), dim3(256), 0, s, (const float*)a.workspace,
+                       reinterpret_cast<const uint32_t*>(a.tile_hit1), reinterpret_cast<const uint32_t*>(a.tile_hit2), a.batch_size,
+                       tiles_x * tiles_y, a.sums, a.loss_fwd, a.loss_bwd, grad ? (const unsigned*)q.tile_max : (const unsigned*)nullptr,
+                       grad ? reinterpret_cast<unsigned*>(a.unit_grad_max) : (unsigned*)nullptr, a.loss_sum,
+                       scatter_work_at(grad ? a.scatter_work : nullptr, 2 * a.batch_size),
                        // (the arrival counter of the batch mean: a spare word of the list header the caller cleared with it)
-                       mean_out ? const_cast<unsigned*>(&((const TileList*)list_header)->pad[0]) : (unsigned*)nullptr, mean_out, mean_of,
-                       reset_list ? const_cast<unsigned*>(&((const TileList*)list_header)->n_heavy) : (unsigned*)nullptr);
+                       a.mean_out ? const_cast<unsigned*>(&header->pad[0]) : (unsigned*)nullptr, a.mean_out, a.mean_of,
+                       a.reset_list ? const_cast<unsigned*>(&header->n_heavy) : (unsigned*)nullptr);
     MR_CHECK_LAUNCH();
     return MR_OK;
-}
-
-// mr_flow_pair_forward_grad_tiles + the mean over the batch (mr_pair_step_forward, pair_step.hip): mean_out[0] = the mean of
-// loss_bwd + loss_fwd (mean_of = 0) or of loss_fwd (1); mean_out[1 .. B] scratch.  The list header's spare words must have
-// been cleared with the header (MR_FLAG_TILE_LIST_CLEARED's region: the pair prologue does it).
-int mr_flow_pair_forward_grad_tiles_ex(const float* mask_flow1, const float* mask_flow2, const float* flow12, const float* flow21,
-                                       int64_t flow_bstride, const float* flow12_scale, const float* flow21_scale, float* occl1,
-                                       float* occl2, float* flow_out12, float* flow_out21, const uint8_t* tile_hit1,
-                                       const uint8_t* tile_hit2, const float* image_ref, const float* image, const float* jitter_ref,
-                                       const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
-                                       float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size, int height,
-                                       int width, float distance_thresh, float warp_thresh, float pair_thresh, const void* list_header,
-                                       const void* list_entries, int64_t list_capacity, int64_t tile_bound, float* unit_grad,
-                                       float* unit_grad_max, float* loss_sum, void* scatter_work, float* mean_out, int mean_of,
-                                       int reset_list, const void* records, mr_stream_t stream, int criterion) {
-    if (!unit_grad || !unit_grad_max) return MR_ERR_BADARG;
-    return flow_pair_forward_tiles(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1, occl2,
-                                   flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter,
-                                   jitter_channels, workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size, image_size,
-                                   height, width, distance_thresh, warp_thresh, pair_thresh, list_header, list_entries,
-                                   list_capacity, tile_bound, unit_grad, unit_grad_max, loss_sum, scatter_work, stream, mean_out,
-                                   mean_of, reset_list, records, criterion);
-}
-
-extern "C" int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
-                                               const float* flow21, int64_t flow_bstride, const float* flow12_scale,
-                                               const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
-                                               float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
-                                               const float* image_ref, const float* image, const float* jitter_ref,
-                                               const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
-                                               float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
-                                               int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
-                                               const void* list_header, const void* list_entries, int64_t list_capacity,
-                                               int64_t tile_bound, mr_stream_t stream, int criterion) {
-    return flow_pair_forward_tiles(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1, occl2,
-                                   flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter,
-                                   jitter_channels, workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size, image_size,
-                                   height, width, distance_thresh, warp_thresh, pair_thresh, list_header, list_entries,
-                                   list_capacity, tile_bound, nullptr, nullptr, nullptr, nullptr, stream, nullptr, 0, 0, nullptr,
-                                   criterion);
-}
-
-extern "C" int mr_flow_pair_forward_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,
-                                          const float* flow21, int64_t flow_bstride, const float* flow12_scale,
-                                          const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
-                                          float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
-                                          const float* image_ref, const float* image, const float* jitter_ref,
-                                          const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
-                                          float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
-                                          int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
-                                          const void* list_header, const void* list_entries, int64_t list_capacity,
-                                          int64_t tile_bound, mr_stream_t stream) {
-    return mr_flow_pair_forward_tiles_crit(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1,
-                                           occl2, flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter,
-                                           jitter_channels, workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size,
-                                           image_size, height, width, distance_thresh, warp_thresh, pair_thresh, list_header,
-                                           list_entries, list_capacity, tile_bound, stream, MR_CRITERION_L1);
 }
 
 extern "C" int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
@@ -1518,12 +1457,20 @@ extern "C" int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, con
                                                     float* unit_grad, float* unit_grad_max, float* loss_sum,
                                                     void* scatter_work, mr_stream_t stream, int criterion) {
     if (!unit_grad || !unit_grad_max) return MR_ERR_BADARG;
-    return flow_pair_forward_tiles(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1, occl2,
-                                   flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter,
-                                   jitter_channels, workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size, image_size,
-                                   height, width, distance_thresh, warp_thresh, pair_thresh, list_header, list_entries,
-                                   list_capacity, tile_bound, unit_grad, unit_grad_max, loss_sum, scatter_work, stream, nullptr, 0,
-                                   0, nullptr, criterion);
+    FlowPairFwdArgs a{};
+    a.mask_flow1 = mask_flow1; a.mask_flow2 = mask_flow2; a.flow12 = flow12; a.flow21 = flow21; a.flow_bstride = flow_bstride;
+    a.flow12_scale = flow12_scale; a.flow21_scale = flow21_scale;
+    a.occl1 = occl1; a.occl2 = occl2; a.flow_out12 = flow_out12; a.flow_out21 = flow_out21;
+    a.tile_hit1 = tile_hit1; a.tile_hit2 = tile_hit2;
+    a.image_ref = image_ref; a.image = image; a.jitter_ref = jitter_ref; a.jitter = jitter; a.jitter_channels = jitter_channels;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.sums = sums; a.loss_fwd = loss_fwd; a.loss_bwd = loss_bwd;
+    a.batch_size = batch_size; a.image_size = image_size; a.height = height; a.width = width;
+    a.distance_thresh = distance_thresh; a.warp_thresh = warp_thresh; a.pair_thresh = pair_thresh;
+    a.list_header = list_header; a.list_entries = list_entries; a.list_capacity = list_capacity; a.tile_bound = tile_bound;
+    a.unit_grad = unit_grad; a.unit_grad_max = unit_grad_max; a.loss_sum = loss_sum; a.scatter_work = scatter_work;
+    a.criterion = criterion;
+    return launch_flow_pair_forward(a, (hipStream_t)stream);
 }
 
 extern "C" int mr_flow_pair_forward_grad_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,
@@ -1544,4 +1491,46 @@ extern "C" int mr_flow_pair_forward_grad_tiles(const float* mask_flow1, const fl
                                                 loss_bwd, batch_size, image_size, height, width, distance_thresh, warp_thresh,
                                                 pair_thresh, list_header, list_entries, list_capacity, tile_bound, unit_grad,
                                                 unit_grad_max, loss_sum, scatter_work, stream, MR_CRITERION_L1);
+}
+
+extern "C" int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                               const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                               const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                               float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                               const float* image_ref, const float* image, const float* jitter_ref,
+                                               const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                               float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
+                                               int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
+                                               const void* list_header, const void* list_entries, int64_t list_capacity,
+                                               int64_t tile_bound, mr_stream_t stream, int criterion) {
+    FlowPairFwdArgs a{};
+    a.mask_flow1 = mask_flow1; a.mask_flow2 = mask_flow2; a.flow12 = flow12; a.flow21 = flow21; a.flow_bstride = flow_bstride;
+    a.flow12_scale = flow12_scale; a.flow21_scale = flow21_scale;
+    a.occl1 = occl1; a.occl2 = occl2; a.flow_out12 = flow_out12; a.flow_out21 = flow_out21;
+    a.tile_hit1 = tile_hit1; a.tile_hit2 = tile_hit2;
+    a.image_ref = image_ref; a.image = image; a.jitter_ref = jitter_ref; a.jitter = jitter; a.jitter_channels = jitter_channels;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+    a.sums = sums; a.loss_fwd = loss_fwd; a.loss_bwd = loss_bwd;
+    a.batch_size = batch_size; a.image_size = image_size; a.height = height; a.width = width;
+    a.distance_thresh = distance_thresh; a.warp_thresh = warp_thresh; a.pair_thresh = pair_thresh;
+    a.list_header = list_header; a.list_entries = list_entries; a.list_capacity = list_capacity; a.tile_bound = tile_bound;
+    a.criterion = criterion;
+    return launch_flow_pair_forward(a, (hipStream_t)stream);
+}
+
+extern "C" int mr_flow_pair_forward_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                          const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                          const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                          float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                          const float* image_ref, const float* image, const float* jitter_ref,
+                                          const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                          float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
+                                          int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
+                                          const void* list_header, const void* list_entries, int64_t list_capacity,
+                                          int64_t tile_bound, mr_stream_t stream) {
+    return mr_flow_pair_forward_tiles_crit(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1,
+                                           occl2, flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter,
+                                           jitter_channels, workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size,
+                                           image_size, height, width, distance_thresh, warp_thresh, pair_thresh, list_header,
+                                           list_entries, list_capacity, tile_bound, stream, MR_CRITERION_L1);
 }

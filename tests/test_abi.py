@@ -240,3 +240,212 @@ def test_call_switches_to_the_device_of_its_stream(monkeypatch):
     s0.device_index = 0
     _lib.call("mr_fake", None, 3, s0)
     assert events == [("launch", 0)]
+
+
+def _prototype(name):
+    """[(kind, parameter name)] of a header prototype, kind in {"ptr", "stream", "int", "int64", "float"}"""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    m = re.search(r"MR_API\s+(?:int64_t|int)\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S)
+    assert m, name
+    out = []
+    for decl in m.group(1).split(","):
+        words = decl.replace("*", " * ").split()
+        kind = "stream" if "mr_stream_t" in words else "ptr" if "*" in words else \
+            {"int": "int", "int64_t": "int64", "float": "float"}[[w for w in words[:-1] if w != "const"][0]]
+        out.append((kind, words[-1]))
+    return out
+
+
+# An argument set every entry point below accepts: batch_size 2 at an 8 x 8 raster (one 32 x 8 tile per image), every
+# pointer non-NULL (never dereferenced: each row of the table changes something that returns before the first HIP call).
+_VALID = dict(batch_size=2, image_size=8, hit_image_size=8, height=8, width=8, jitter_channels=3, num_verts=4, num_faces=2,
+              fill_back=1, split=1, flags=0, texel_layout=0, criterion=0, eps=1e-3, flow_bstride=128, workspace_bytes=1 << 30,
+              list_capacity=4, tile_bound=-1)
+_ZEROED = 4  # MR_FLAG_OUTPUT_ZEROED: no memset in front of the later checks
+_SCATTER = ("mr_render_flow_backward", "mr_flow_pair_backward_tiles", "mr_flow_pair_backward_tiles_crit",
+            "mr_flow_pair_backward_unit_tiles")
+_PAIR_SCATTER = _SCATTER[1:]
+_FLOW_FWD = ("mr_flow_pair_forward_tiles", "mr_flow_pair_forward_tiles_crit", "mr_flow_pair_forward_grad_tiles",
+             "mr_flow_pair_forward_grad_tiles_crit")
+_CONSIST = ("mr_pair_consist_forward", "mr_pair_consist_forward_crit", "mr_pair_consist_backward", "mr_pair_consist_backward_crit")
+_CONSIST_TILES = ("mr_pair_consist_forward_tiles", "mr_pair_consist_forward_tiles_crit", "mr_pair_consist_backward_tiles",
+                  "mr_pair_consist_backward_tiles_crit")
+_CRIT = tuple(n for n in _SCATTER + _FLOW_FWD + _CONSIST + _CONSIST_TILES if n.endswith("_crit"))
+_WITH_WORKSPACE = _FLOW_FWD + _CONSIST[:2] + _CONSIST_TILES[:2]
+
+# (entry points, overrides of _VALID -- None = NULL --, expected return)
+_VALIDATION_TABLE = [
+    # ---- tile scatter backward (raster_bwd.hip) ----
+    (_SCATTER, dict(batch_size=-1), -1),
+    (_SCATTER, dict(num_verts=-1), -1),
+    (_SCATTER, dict(num_faces=-1), -1),
+    (_SCATTER, dict(image_size=0), -1),
+    (_SCATTER, dict(texel_layout=63), -1),
+    (_SCATTER, dict(texel_layout=0b000101), -1),
+    (_SCATTER, dict(grad_vcolors=None), -1),
+    (_SCATTER, dict(batch_size=0), 0),
+    (_SCATTER, dict(batch_size=0, grad_vcolors=None), 0),
+    (_SCATTER, dict(num_verts=0), 0),
+    (_SCATTER, dict(num_verts=0, grad_vcolors=None, face_index_map=None), 0),
+    (_PAIR_SCATTER, dict(batch_size=3), -1),
+    (_PAIR_SCATTER, dict(batch_size=3, num_verts=0), -1),
+    (_PAIR_SCATTER, dict(tile_hit=None), -1),
+    (_PAIR_SCATTER, dict(sums=None), -1),
+    (_PAIR_SCATTER, dict(grad_loss_fwd=None), -1),
+    (_PAIR_SCATTER, dict(grad_loss_fwd=None, batch_size=0), 0),
+    (_PAIR_SCATTER, dict(width=1), -1),
+    (_PAIR_SCATTER, dict(height=0), -1),
+    (_PAIR_SCATTER, dict(height=9), -1),
+    (_PAIR_SCATTER, dict(width=9), -1),
+    (_PAIR_SCATTER, dict(width=1, flags=_ZEROED, image_size=10), -1),
+    (_PAIR_SCATTER, dict(flags=_ZEROED, num_faces=0), 0),
+    (_PAIR_SCATTER, dict(flags=_ZEROED, num_faces=0, vertex_id_map=None, eps=0.0, image_size=10), 0),
+    (_PAIR_SCATTER, dict(flags=_ZEROED, vertex_id_map=None), -1),
+    (_PAIR_SCATTER, dict(flags=_ZEROED, vertex_id_map=None, image_size=10), -1),
+    (_SCATTER, dict(flags=_ZEROED, face_index_map=None), -1),
+    (_SCATTER, dict(flags=_ZEROED, weight_map=None), -1),
+    (_SCATTER, dict(flags=_ZEROED, eps=0.0), -1),
+    (_SCATTER, dict(flags=_ZEROED, eps=0.0, image_size=10), -1),
+    (_SCATTER, dict(flags=_ZEROED, image_size=10), -2),
+    (_SCATTER, dict(flags=_ZEROED, image_size=10, grad_loss_bwd=None, grad_bound=None, scatter_work=None), -2),
+    (_SCATTER, dict(flags=_ZEROED, num_verts=100000), -2),
+    (_SCATTER, dict(flags=_ZEROED, image_size=4100, height=4100, width=4100), -2),  # more than 4096 tiles per image
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, batch_size=3, image_size=10), -2),  # (no pairs: odd batches pass)
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, num_faces=0, face_index_map=None), 0),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, grad_rgb_img=None), -2),  # the flow-gradient form
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, grad_flow=None), -2),  # (colour form: not looked at)
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, grad_flow=None), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, mask_pre=None), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, mask_x_lo=None), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, occl=None), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, height=9), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, width=0), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, split=3), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, split=-1), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, mask_x_hi=None), -1),
+    (("mr_render_flow_backward",), dict(grad_rgb_img=None, mask_x_hi=None, split=2, flags=_ZEROED, image_size=10), -2),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, height=99, width=0, split=7), -2),  # (colour form)
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, vertex_id_map=None), -2),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, vertex_id_map=None, verts=None), -1),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, vertex_id_map=None, faces_idx=None), -1),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, vertex_id_map=None, depth_img=None), -1),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, image_size=10, verts=None, faces_idx=None, depth_img=None), -2),
+    # (three table entries per vertex in the colour form, two in the flow-gradient form: 60 KB of 16-byte entry pairs)
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, num_verts=2561), -2),
+    (("mr_render_flow_backward",), dict(flags=_ZEROED, num_verts=3841, grad_rgb_img=None), -2),
+    (_PAIR_SCATTER, dict(flags=_ZEROED, num_verts=3841), -2),
+    (_PAIR_SCATTER[:2], dict(jitter_channels=2), -1),
+    (_PAIR_SCATTER[:2], dict(jitter_channels=2, batch_size=0), 0),
+    (_PAIR_SCATTER[:2], dict(flows=None), -1),
+    (_PAIR_SCATTER[:2], dict(image_ref=None), -1),
+    (_PAIR_SCATTER[:2], dict(jitter=None), -1),
+    (_PAIR_SCATTER[:2], dict(mask_x_hi=None), -1),
+    (_PAIR_SCATTER[:2], dict(occl=None), -1),
+    (_PAIR_SCATTER[:2], dict(grad_flow_scratch=None), -1),
+    (("mr_flow_pair_backward_unit_tiles",), dict(unit_grad=None), -1),
+    (("mr_flow_pair_backward_unit_tiles",), dict(unit_grad_max=None), -1),
+    (("mr_flow_pair_backward_unit_tiles",), dict(grad_loss_fwd=None, num_verts=0), 0),
+    (("mr_flow_pair_backward_unit_tiles",), dict(grad_loss_fwd=None, batch_size=-2), -1),
+    # ---- the criterion comes first wherever there is one ----
+    (_CRIT, dict(criterion=2), -1),
+    (_CRIT, dict(criterion=-1), -1),
+    (_CRIT, dict(criterion=2, batch_size=0, list_capacity=0), -1),
+    (_CRIT, dict(criterion=1, batch_size=0, list_capacity=0), 0),
+    # ---- flow-pair forward over the tile list (warp.hip) ----
+    (_FLOW_FWD, dict(mask_flow1=None), -1),
+    (_FLOW_FWD, dict(mask_flow2=None), -1),
+    (_FLOW_FWD, dict(flow12=None), -1),
+    (_FLOW_FWD, dict(flow21=None), -1),
+    (_FLOW_FWD, dict(occl1=None), -1),
+    (_FLOW_FWD, dict(occl2=None), -1),
+    (_FLOW_FWD, dict(flow_out12=None), -1),
+    (_FLOW_FWD, dict(flow_out21=None), -1),
+    (_FLOW_FWD, dict(batch_size=-1), -1),
+    (_FLOW_FWD, dict(image_size=0), -1),
+    (_FLOW_FWD, dict(flow_bstride=127), -1),
+    (_FLOW_FWD, dict(tile_hit1=None), -1),
+    (_FLOW_FWD, dict(tile_hit2=None), -1),
+    (_FLOW_FWD, dict(height=9), -1),
+    (_FLOW_FWD, dict(width=9), -1),
+    (_FLOW_FWD, dict(batch_size=0, list_capacity=0), 0),
+    (_FLOW_FWD, dict(batch_size=0, list_capacity=0, workspace_bytes=0, flow12_scale=None, flow21_scale=None, loss_fwd=None,
+                     loss_bwd=None, loss_sum=None, scatter_work=None), 0),
+    (_FLOW_FWD, dict(batch_size=0, list_capacity=0, occl1=None), -1),
+    (_FLOW_FWD[2:], dict(unit_grad=None), -1),
+    (_FLOW_FWD[2:], dict(unit_grad_max=None), -1),
+    (_FLOW_FWD[2:], dict(unit_grad=None, batch_size=0, list_capacity=0), -1),
+    # ---- what the pair-loss launchers share (warp.hip) ----
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(image_ref=None), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(image=None), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(jitter_ref=None), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(jitter=None), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(jitter_channels=2), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(jitter_channels=0), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(jitter_channels=2, batch_size=0, list_capacity=0), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(width=1), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(width=1, batch_size=0, list_capacity=0), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(height=0), -1),
+    (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(sums=None), -1),
+    (_CONSIST + _CONSIST_TILES, dict(flow12=None), -1),
+    (_CONSIST + _CONSIST_TILES, dict(flow21=None), -1),
+    (_CONSIST + _CONSIST_TILES, dict(batch_size=-1), -1),
+    (_CONSIST + _CONSIST_TILES, dict(hit_image_size=7), -1),
+    (_CONSIST + _CONSIST_TILES, dict(batch_size=0, list_capacity=0), 0),
+    (_CONSIST + _CONSIST_TILES, dict(height=32768, width=32768, hit_image_size=32768, batch_size=0, list_capacity=0), -1),
+    (_WITH_WORKSPACE, dict(workspace=None), -1),
+    (_WITH_WORKSPACE, dict(workspace_bytes=0), -1),
+    (_WITH_WORKSPACE, dict(workspace_bytes=0, batch_size=0, list_capacity=0), 0),
+    (_CONSIST[2:] + _CONSIST_TILES[2:], dict(grad_loss_fwd=None), -1),
+    (_CONSIST[2:] + _CONSIST_TILES[2:], dict(grad_flow12=None), -1),
+    (_CONSIST[2:] + _CONSIST_TILES[2:], dict(grad_flow21=None), -1),
+    (_CONSIST[2:] + _CONSIST_TILES[2:], dict(grad_loss_bwd=None, grad_max=None, batch_size=0, list_capacity=0), 0),
+    (_CONSIST, dict(tile_hit12=None, tile_hit21=None, hit_image_size=0, batch_size=0), 0),  # (coverage bytes are optional)
+    (_CONSIST, dict(tile_hit21=None, hit_image_size=7), -1),
+    (_CONSIST, dict(height=32768, width=32768, hit_image_size=32768, batch_size=-1), -1),
+    (_CONSIST[:2], dict(full_mask1=None, full_mask2=None, warp_mask1=None, warp_mask2=None, warp1=None, warp2=None, diff1=None,
+                        diff2=None, loss_fwd=None, loss_bwd=None, batch_size=0), 0),
+    (_FLOW_FWD + _CONSIST_TILES, dict(list_header=None), -1),
+    (_FLOW_FWD + _CONSIST_TILES, dict(list_entries=None), -1),
+    (_FLOW_FWD + _CONSIST_TILES, dict(list_capacity=3), -1),
+    (_FLOW_FWD + _CONSIST_TILES, dict(list_capacity=8), -1),
+    (_FLOW_FWD + _CONSIST_TILES, dict(batch_size=0), -1),  # (the capacity is checked before the empty batch returns)
+    (_CONSIST_TILES, dict(tile_hit12=None), -1),
+    (_CONSIST_TILES, dict(tile_hit21=None), -1),
+    # (2 B tiles_x tiles_y beyond 31 bits)
+    (_FLOW_FWD + _CONSIST_TILES, dict(batch_size=1 << 20, image_size=4096, hit_image_size=4096, flow_bstride=1 << 26,
+                                      list_capacity=(2 << 20) * 128 * 512), -1),
+]
+
+
+def test_validation_returns_of_the_pair_launchers():
+    """What the frame-pair path's entry points answer to arguments they refuse -- or accept without work -- before any HIP
+    call: MR_ERR_BADARG (-1), MR_ERR_NOTIMPL (-2) or MR_OK (0), entry point by entry point and in each one's own order of
+    checks (rows with two faults pin which one is seen first).  Needs no device."""
+    from handobjectconsist_amd import _lib
+
+    lib = _lib.load()
+    protos = {name: _prototype(name) for names, _, _ in _VALIDATION_TABLE for name in names}
+    ran = 0
+    for names, over, want in _VALIDATION_TABLE:
+        assert set(over) <= {p for name in names for _, p in protos[name]}, over  # (a misspelt parameter)
+        for name in names:
+            proto = protos[name]
+            pnames = {p for _, p in proto}
+            # (a row shared by several entry points may name parameters only some of them have; each has at least one)
+            mine = {k: v for k, v in over.items() if k in pnames}
+            assert mine, (name, over)
+            args = []
+            for kind, p in proto:
+                if kind == "stream":
+                    args.append(None)
+                elif kind == "ptr":
+                    args.append(mine.get(p, 0x1000))
+                elif kind == "float":
+                    args.append(float(mine.get(p, _VALID.get(p, 0.5))))
+                else:
+                    assert p in mine or p in _VALID, (name, p)
+                    args.append(int(mine.get(p, _VALID.get(p))))
+            got = getattr(lib, name)(*args)
+            assert got == want, f"{name}({over}) returned {got}, expected {want}"
+            ran += 1
+    assert ran > 500
