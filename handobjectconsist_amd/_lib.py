@@ -25,6 +25,13 @@ FLAG_FORCE_GATHER = 32 << 8  # mr_render_vc_backward: the per-face gather also w
 FLAG_COUNT_PIXEL_MAP_TERMS = 1024 << 8  # mr_render_backward: count the terms mr_pixel_map_terms reads back
 CRITERION_L1 = 0  # MR_CRITERION_L1: the pair loss's per-channel term |res|
 CRITERION_L2 = 1  # MR_CRITERION_L2: res * res
+# MR_DTYPE_*: element types of an image batch (fp32 images + fp32 masks by default; the compact batch is bf16 + u8)
+DTYPE_F32, DTYPE_BF16, DTYPE_U8 = 0, 1, 2
+DTYPE_CODES = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.uint8: DTYPE_U8}
+IMAGE_DTYPES = (torch.float32, torch.bfloat16)
+MASK_DTYPES = (torch.float32, torch.uint8)
+# (image, mask) pairs the fused pair kernels are instantiated for
+FUSED_BATCH_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.uint8), (torch.bfloat16, torch.float32))
 
 _c = ctypes
 _P, _I, _F, _L = _c.c_void_p, _c.c_int, _c.c_float, _c.c_int64
@@ -90,6 +97,9 @@ SIGNATURES = {
     "mr_flow_pair_forward_tiles_crit": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _I]),
     "mr_flow_pair_backward_tiles_crit": (_I, [_P] * 9 + [_I] + [_P] * 8 + [_I, _I, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _P, _I]),
     "mr_flow_pair_forward_grad_tiles_crit": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _P, _P, _P, _P, _I]),
+    # the compact image batch: the flow-pair forward entry points with void* images / masks + criterion + the two MR_DTYPE_* codes
+    "mr_flow_pair_forward_tiles_typed": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _I, _I, _I]),
+    "mr_flow_pair_forward_grad_tiles_typed": (_I, [_P] * 4 + [_L] + [_P] * 12 + [_I, _P, _L, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P, _L, _L, _P, _P, _P, _P, _P, _I, _I, _I]),
     "mr_pair_step_struct_bytes": (_L, []),
     "mr_pair_step_field_offsets": (_I, [_P, _I]),
     "mr_pair_step_sizes": (_I, [_P, _P, _P, _P]),
@@ -97,6 +107,7 @@ SIGNATURES = {
     "mr_pair_step_backward": (_I, [_P, _P]),
     "mr_frames_to_batch_workspace_bytes": (_L, [_I, _I, _I]),
     "mr_frames_to_batch": (_I, [_P] * 3 + [_F] * 6 + [_P, _L, _P, _P] + [_I] * 6 + [_P]),
+    "mr_frames_to_batch_typed": (_I, [_P] * 3 + [_F] * 6 + [_P, _L, _P, _P] + [_I] * 6 + [_P, _I, _I]),
     "mr_bn_act_forward": (_I, [_P] * 6 + [_F, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mr_bn_act_backward_workspace_bytes": (_L, [_I, _I]),
     "mr_bn_act_backward": (_I, [_P] * 8 + [_F, _I, _I, _I] + [_P] * 5 + [_L, _I, _I, _I, _P]),
@@ -186,6 +197,18 @@ def crit_call(name, criterion, *args):
     if criterion == CRITERION_L1:
         return call(name, *args)
     return call(name + "_crit", *args, int(criterion))
+
+
+def batch_dtypes(image_ref, image, jitter_ref, jitter):
+    """The (image, mask) element types the fused pair kernels would read this pair's batch as, or None when they have no
+    instantiation for it.  fp32 images: the fp32 kernels, masks of any type are cast to fp32 (what has always happened).
+    bf16 images (the compact batch): both images bf16 and both masks uint8, or both masks fp32 -- nothing is cast."""
+    if image.dtype == torch.float32:
+        return torch.float32, torch.float32
+    if image.dtype == torch.bfloat16 and image_ref.dtype == torch.bfloat16 and jitter.dtype == jitter_ref.dtype \
+            and (image.dtype, jitter.dtype) in FUSED_BATCH_DTYPES:
+        return torch.bfloat16, jitter.dtype
+    return None
 
 
 def tile_list(workspace, batch_size, num_faces, image_size):

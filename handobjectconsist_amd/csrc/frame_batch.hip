@@ -7,7 +7,8 @@
 //   jittermask = to_tensor(transform_img(white image, affinetrans, inp_res))
 // (and the optional left-right flip of handobjset.py:124-125).
 //
-// Byte work, HBM-bound: per output pixel 3 source bytes in, 12 B of image + 4 or 12 B of mask out.
+// Byte work, HBM-bound: per output pixel 3 source bytes in, 12 B of image + 4 or 12 B of mask out (fp32 batch; the compact
+// batch of mr_frames_to_batch_typed -- bf16 image, u8 mask -- is 6 B + 1 or 3 B).
 // Bit-exact with Pillow: the source pixel of every output pixel is computed exactly the way Pillow's
 // Geometry.c does it, in each of its three regimes --
 //   scale      (b == 0 && d == 0)  positions ACCUMULATED in double along each axis, one table per axis
@@ -39,8 +40,8 @@ struct FrameBatchParams {
     double* rowy;           // [N,H]
     int* xtab;              // [N,W]   FB_SCALE: source column (or -1)
     int* ytab;              // [N,H]
-    float* image;           // [N,3,H,W]
-    float* mask;            // [N,mc,H,W] or NULL
+    void* image;            // [N,3,H,W]   float or bf16 (the kernel's image type)
+    void* mask;             // [N,mc,H,W] or NULL; float or u8 (the kernel's mask type)
     int mask_channels;
     int N, Hs, Ws, H, W;
     int Hs_ld, Ws_ld;       // max(Hs, 1), max(Ws, 1): clamp range of the unconditional source loads
@@ -138,6 +139,22 @@ __device__ __forceinline__ void store4_stream(float* dst, float a, float b, floa
     __builtin_nontemporal_store(v, reinterpret_cast<fb_f4*>(dst));
 }
 
+// ... of the compact batch's element types: 8 bytes of bf16, 4 bytes of u8 per 4 pixels
+__device__ __forceinline__ void store4_stream(bf16_t* dst, bf16_t a, bf16_t b, bf16_t c, bf16_t d) {
+    typedef unsigned fb_u2 __attribute__((ext_vector_type(2)));
+    fb_u2 v = {(unsigned)a | ((unsigned)b << 16), (unsigned)c | ((unsigned)d << 16)};
+    __builtin_nontemporal_store(v, reinterpret_cast<fb_u2*>(dst));
+}
+__device__ __forceinline__ void store4_stream(uint8_t* dst, uint8_t a, uint8_t b, uint8_t c, uint8_t d) {
+    const unsigned v = (unsigned)a | ((unsigned)b << 8) | ((unsigned)c << 16) | ((unsigned)d << 24);
+    __builtin_nontemporal_store(v, reinterpret_cast<unsigned*>(dst));
+}
+// the fp32 value the kernel computes as an element of the output type: itself, its nearest-even bf16, or (mask) 1 where it is 1
+template <typename T> __device__ __forceinline__ T fb_out(float v);
+template <> __device__ __forceinline__ float fb_out<float>(float v) { return v; }
+template <> __device__ __forceinline__ bf16_t fb_out<bf16_t>(float v) { return f32_to_bf16(v); }
+template <> __device__ __forceinline__ uint8_t fb_out<uint8_t>(float v) { return v == 1.0f ? (uint8_t)1 : (uint8_t)0; }
+
 constexpr int FB_PX = 4;    // output pixels per thread and row (one 16-byte store per plane)
 constexpr int FB_ROWS = 4;  // rows per thread: 16 source pixels requested before the first is used (B=64 bench shape, inputs cold:
                             // 100 us vs 107 with one row; putting all tiles of a frame on one XCD measured slower: 128 us)
@@ -179,6 +196,9 @@ __device__ __forceinline__ void source_pos(const FrameBatchParams& p, const Fram
 
 // grid (ceil(W / 256), ceil(H / (4 FB_ROWS)), N), block (64, 4): a wave covers 256 consecutive pixels of rows y0 + ty, y0 + ty + 4, ...  Per thread: the x-table slice once, then ALL source bytes of its FB_ROWS x FB_PX pixels
 // are requested -- unconditionally, from clamped addresses -- before the first is used, then the stores.
+// IT / MT: the element types of the image and of the mask (chosen by the host per launch, nothing branches on them here;
+// <float, float> is the fp32 batch's kernel, instruction for instruction what it was before the types became parameters)
+template <typename IT, typename MT>
 __global__ __launch_bounds__(256) void frames_to_batch_kernel(FrameBatchParams p) {
     __shared__ float lut[768];
     for (int e = threadIdx.y * 64 + threadIdx.x; e < 768; e += 256) lut[e] = p.lut[e];
@@ -221,7 +241,7 @@ __global__ __launch_bounds__(256) void frames_to_batch_kernel(FrameBatchParams p
     __syncthreads();  // the lookup table is in LDS
     if (x0 >= p.W) return;
     const size_t plane = (size_t)p.H * p.W;
-    const bool vec = (p.W % FB_PX) == 0;  // rows and planes stay 16-byte aligned
+    const bool vec = (p.W % FB_PX) == 0;  // rows and planes stay aligned to the FB_PX-element store
 #pragma unroll
     for (int r = 0; r < FB_ROWS; r++) {
         const int y = ybase + 4 * r;
@@ -235,24 +255,24 @@ __global__ __launch_bounds__(256) void frames_to_batch_kernel(FrameBatchParams p
             float px[FB_PX];
 #pragma unroll
             for (int i = 0; i < FB_PX; i++) px[i] = lut[ch * 256 + (in[r][i] ? c[r][i][ch] : 0u)];
-            float* dst = p.image + ((size_t)n * 3 + ch) * plane + o;
+            IT* dst = static_cast<IT*>(p.image) + ((size_t)n * 3 + ch) * plane + o;
             if (vec) {
-                store4_stream(dst, px[0], px[1], px[2], px[3]);
+                store4_stream(dst, fb_out<IT>(px[0]), fb_out<IT>(px[1]), fb_out<IT>(px[2]), fb_out<IT>(px[3]));
             } else {
 #pragma unroll
                 for (int i = 0; i < FB_PX; i++)
-                    if (x0 + i < p.W) dst[i] = px[i];
+                    if (x0 + i < p.W) dst[i] = fb_out<IT>(px[i]);
             }
         }
         if (p.mask) {
             for (int ch = 0; ch < p.mask_channels; ch++) {
-                float* dst = p.mask + ((size_t)n * p.mask_channels + ch) * plane + o;
+                MT* dst = static_cast<MT*>(p.mask) + ((size_t)n * p.mask_channels + ch) * plane + o;
                 if (vec) {
-                    store4_stream(dst, mk[0], mk[1], mk[2], mk[3]);
+                    store4_stream(dst, fb_out<MT>(mk[0]), fb_out<MT>(mk[1]), fb_out<MT>(mk[2]), fb_out<MT>(mk[3]));
                 } else {
 #pragma unroll
                     for (int i = 0; i < FB_PX; i++)
-                        if (x0 + i < p.W) dst[i] = mk[i];
+                        if (x0 + i < p.W) dst[i] = fb_out<MT>(mk[i]);
                 }
             }
         }
@@ -270,12 +290,13 @@ extern "C" int64_t mr_frames_to_batch_workspace_bytes(int num_frames, int height
            mr::fb_align(n * H * 4);
 }
 
-extern "C" int mr_frames_to_batch(const uint8_t* frames, const double* coeffs, const uint8_t* flip, float mean0,
-                                  float mean1, float mean2, float std0, float std1, float std2, void* workspace,
-                                  int64_t workspace_bytes, float* image, float* jittermask, int mask_channels,
-                                  int num_frames, int src_height, int src_width, int height, int width,
-                                  mr_stream_t stream) {
+extern "C" int mr_frames_to_batch_typed(const uint8_t* frames, const double* coeffs, const uint8_t* flip, float mean0,
+                                        float mean1, float mean2, float std0, float std1, float std2, void* workspace,
+                                        int64_t workspace_bytes, void* image, void* jittermask, int mask_channels,
+                                        int num_frames, int src_height, int src_width, int height, int width,
+                                        mr_stream_t stream, int image_dtype, int mask_dtype) {
     using namespace mr;
+    if (!image_dtype_ok(image_dtype) || !mask_dtype_ok(mask_dtype)) return MR_ERR_BADARG;
     if (num_frames < 0 || src_height < 0 || src_width < 0 || height < 0 || width < 0) return MR_ERR_BADARG;
     if (jittermask && mask_channels != 1 && mask_channels != 3) return MR_ERR_BADARG;
     if (num_frames == 0 || height == 0 || width == 0) return MR_OK;
@@ -309,7 +330,20 @@ extern "C" int mr_frames_to_batch(const uint8_t* frames, const double* coeffs, c
     const dim3 block(64, 4);
     const dim3 grid((unsigned)((width + 64 * FB_PX - 1) / (64 * FB_PX)), (unsigned)((height + 4 * FB_ROWS - 1) / (4 * FB_ROWS)),
                     (unsigned)num_frames);
-    hipLaunchKernelGGL(frames_to_batch_kernel, grid, block, 0, (hipStream_t)stream, p);
+    const bool bf = image_dtype == MR_DTYPE_BF16, u8 = mask_dtype == MR_DTYPE_U8;
+    void (*kernel)(FrameBatchParams) = bf ? (u8 ? frames_to_batch_kernel<bf16_t, uint8_t> : frames_to_batch_kernel<bf16_t, float>)
+                                          : (u8 ? frames_to_batch_kernel<float, uint8_t> : frames_to_batch_kernel<float, float>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
     return MR_OK;
+}
+
+extern "C" int mr_frames_to_batch(const uint8_t* frames, const double* coeffs, const uint8_t* flip, float mean0,
+                                  float mean1, float mean2, float std0, float std1, float std2, void* workspace,
+                                  int64_t workspace_bytes, float* image, float* jittermask, int mask_channels,
+                                  int num_frames, int src_height, int src_width, int height, int width,
+                                  mr_stream_t stream) {
+    return mr_frames_to_batch_typed(frames, coeffs, flip, mean0, mean1, mean2, std0, std1, std2, workspace, workspace_bytes, image,
+                                    jittermask, mask_channels, num_frames, src_height, src_width, height, width, stream,
+                                    MR_DTYPE_F32, MR_DTYPE_F32);
 }

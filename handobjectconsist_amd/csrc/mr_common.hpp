@@ -19,6 +19,18 @@
 
 namespace mr {
 
+// Element types of an image batch (MR_DTYPE_*): float, bf16 as its bit pattern, uint8_t.  bf16 -> fp32 is exact; fp32 -> bf16
+// rounds to nearest-even (NaN -> the quiet NaN 0x7fc0), which is what torch's cast does.
+typedef unsigned short bf16_t;
+__device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float((unsigned)v << 16); }
+__device__ __forceinline__ bf16_t f32_to_bf16(float v) {
+    const unsigned u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (bf16_t)0x7fc0;
+    return (bf16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+static inline bool image_dtype_ok(int d) { return d == MR_DTYPE_F32 || d == MR_DTYPE_BF16; }
+static inline bool mask_dtype_ok(int d) { return d == MR_DTYPE_F32 || d == MR_DTYPE_U8; }
+
 // Pixel-space bounding box of a face (inclusive); empty when x0 > x1.
 struct __attribute__((aligned(8))) FaceBox {
     int16_t x0, x1, y0, y1;

@@ -33,15 +33,17 @@ int launch_flow_render(const FlowRenderArgs& a, hipStream_t s);
 //   reset_list          the finalize launch leaves the list header's counters zero for the next step
 //   records             the render's 16-byte pixel records [2B,is,is] in place of the mask / flow / scale planes, which are
 //                       not looked at then (needs unit_grad); occl1 / occl2 may be NULL -- the occlusion maps are not kept
+//   image_dtype, mask_dtype   MR_DTYPE_* of image_ref / image and of jitter_ref / jitter (zero: fp32); (F32, F32), (BF16, U8)
+//                       and (BF16, F32) have kernels
 struct FlowPairFwdArgs {
     const float *mask_flow1, *mask_flow2, *flow12, *flow21; int64_t flow_bstride; const float *flow12_scale, *flow21_scale;
     float *occl1, *occl2, *flow_out12, *flow_out21; const uint8_t *tile_hit1, *tile_hit2;
-    const float *image_ref, *image, *jitter_ref, *jitter; int jitter_channels;
+    const void *image_ref, *image, *jitter_ref, *jitter; int jitter_channels;
     void* workspace; int64_t workspace_bytes; float *sums, *loss_fwd, *loss_bwd;
     int batch_size, image_size, height, width; float distance_thresh, warp_thresh, pair_thresh;
     const void *list_header, *list_entries; int64_t list_capacity, tile_bound;
     float *unit_grad, *unit_grad_max, *loss_sum; void* scatter_work; float* mean_out; int mean_of, reset_list;
-    const void* records; int criterion;
+    const void* records; int criterion, image_dtype, mask_dtype;
 };
 int launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s);
 

@@ -35,6 +35,10 @@ static int pair_step_layout(const MrPairStep& a, PairStepLayout& L) {
         (a.jitter_channels != 1 && a.jitter_channels != 3) || a.batch_size > (1 << 20) ||
         (a.criterion != MR_CRITERION_L1 && a.criterion != MR_CRITERION_L2))
         return MR_ERR_BADARG;
+    // the image batch's element types ride in `reserved`: image dtype in bits 0-7, mask dtype in bits 8-15, zero = fp32 / fp32
+    const int idt = a.reserved & 0xff, mdt = (a.reserved >> 8) & 0xff;
+    if ((a.reserved & ~0xffff) || !image_dtype_ok(idt) || !mask_dtype_ok(mdt)) return MR_ERR_BADARG;
+    if (idt == MR_DTYPE_F32 && mdt != MR_DTYPE_F32) return MR_ERR_NOTIMPL;
     const int64_t B2 = 2LL * a.batch_size, V = (int64_t)a.num_verts_a + a.num_verts_b;
     const int64_t F0 = (int64_t)a.num_hand_faces + a.num_obj_faces, F = a.fill_back ? 2 * F0 : F0;
     const int64_t is = a.image_size, px = is * is;
@@ -195,6 +199,7 @@ extern "C" int mr_pair_step_forward(const MrPairStep* step, mr_stream_t stream) 
     // 4 B + 1 -- carry the samples' values to it; reset_list: it leaves the list header's counters zero for the next step)
     f.mean_out = a.losses + 3 * (int64_t)B; f.mean_of = a.mean_of; f.reset_list = 1;
     f.records = records; f.criterion = a.criterion;
+    f.image_dtype = a.reserved & 0xff; f.mask_dtype = (a.reserved >> 8) & 0xff;
     return launch_flow_pair_forward(f, (hipStream_t)stream);
 }
 

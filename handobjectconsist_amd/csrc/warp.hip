@@ -686,10 +686,12 @@ __device__ __forceinline__ void pair_consist_forward_tiles_body(const PairTilesP
 // not depend on the flow: they are requested before the occlusion check's gathers and have arrived when the taps go out.
 struct FlowPairFwdParams {
     OcclTilesParams o;
-    const float* image_ref;   // [B,3,H,W], H = o.crop_h, W = o.crop_w
-    const float* image;
-    const float* jitter_ref;  // [B,Cj,H,W]
-    const float* jitter;
+    // (elements of the kernel's image type IT / mask type MT -- float, or the compact batch's bf16 / u8: the instantiation
+    // is chosen with them, launch_flow_pair_forward)
+    const void* image_ref;    // [B,3,H,W], H = o.crop_h, W = o.crop_w
+    const void* image;
+    const void* jitter_ref;   // [B,Cj,H,W]
+    const void* jitter;
     int Cj;
     float* partial;           // [2B, T, 2]
     float thresh;
@@ -703,7 +705,7 @@ struct FlowPairFwdParams {
     const float4* rec;        // [2B, is, is] image orientation: frame 1's B images, then frame 2's
 };
 
-template <bool GRAD, bool REC, PairCrit CRIT>
+template <bool GRAD, bool REC, PairCrit CRIT, typename IT = float, typename MT = float>
 __device__ __forceinline__ void flow_pair_forward_tiles_body(const FlowPairFwdParams& q) {
     __shared__ float red[2][4][2];
     __shared__ unsigned redm[2][4];
@@ -729,10 +731,10 @@ __device__ __forceinline__ void flow_pair_forward_tiles_body(const FlowPairFwdPa
         const bool in_crop = inside && t.y < H && t.x < W;
         const int64_t pixc = (int64_t)t.y * W + t.x;
         // direction 0 = frame 1's grid: flow12 warps `image` towards image_ref, gated by jitter_ref; direction 1: the reverse
-        const float* src = t.dir ? q.image_ref : q.image;
-        const float* tgt = t.dir ? q.image : q.image_ref;
-        const float* jit = t.dir ? q.jitter : q.jitter_ref;
-        DirRaw2 raw{};
+        const IT* src = static_cast<const IT*>(t.dir ? q.image_ref : q.image);
+        const IT* tgt = static_cast<const IT*>(t.dir ? q.image : q.image_ref);
+        const MT* jit = static_cast<const MT*>(t.dir ? q.jitter : q.jitter_ref);
+        DirRaw2T<IT, MT> raw{};
         float ma_p = 0.0f, sc = 1.0f, f0 = 0.0f, f1 = 0.0f;
         if (in_crop) pair_load_own(tgt, jit, q.Cj, t.b, pixc, hw_img, raw);
         if (inside) {
@@ -1015,6 +1017,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 template <bool GRAD, bool REC = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) flow_pair_forward_tiles_l2_kernel(FlowPairFwdParams q) {
     flow_pair_forward_tiles_body<GRAD, REC, PairCrit::L2>(q);
+}
+// ... on a compact image batch (MR_DTYPE_*): bf16 images with u8 or with fp32 jitter masks.  The same body; only its loads and
+// the widening behind them know the element types.
+template <bool GRAD, bool REC = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) flow_pair_forward_tiles_bf16u8_kernel(FlowPairFwdParams q) {
+    flow_pair_forward_tiles_body<GRAD, REC, PairCrit::L1, bf16_t, uint8_t>(q);
+}
+template <bool GRAD, bool REC = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) flow_pair_forward_tiles_l2_bf16u8_kernel(FlowPairFwdParams q) {
+    flow_pair_forward_tiles_body<GRAD, REC, PairCrit::L2, bf16_t, uint8_t>(q);
+}
+template <bool GRAD, bool REC = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) flow_pair_forward_tiles_bf16f32_kernel(FlowPairFwdParams q) {
+    flow_pair_forward_tiles_body<GRAD, REC, PairCrit::L1, bf16_t, float>(q);
+}
+template <bool GRAD, bool REC = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) flow_pair_forward_tiles_l2_bf16f32_kernel(FlowPairFwdParams q) {
+    flow_pair_forward_tiles_body<GRAD, REC, PairCrit::L2, bf16_t, float>(q);
 }
 
 }  // namespace mr
@@ -1404,8 +1424,12 @@ int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
                   : (!a.mask_flow1 || !a.mask_flow2 || !a.flow12 || !a.flow21 || !a.occl1 || !a.occl2))
         return MR_ERR_BADARG;
     if (!a.flow_out12 || !a.flow_out21 || !criterion_ok(a.criterion)) return MR_ERR_BADARG;
+    if (!image_dtype_ok(a.image_dtype) || !mask_dtype_ok(a.mask_dtype)) return MR_ERR_BADARG;
+    if (a.image_dtype == MR_DTYPE_F32 && a.mask_dtype != MR_DTYPE_F32) return MR_ERR_NOTIMPL;  // (no fp32-image / u8-mask kernel)
     if (a.batch_size < 0 || a.image_size <= 0 || (!a.records && a.flow_bstride < 2LL * a.image_size * a.image_size)) return MR_ERR_BADARG;
-    const int rc = pair_tiles_args_ok(a.flow_out12, a.flow_out21, a.image_ref, a.image, a.jitter_ref, a.jitter, a.jitter_channels,
+    // (the shared checks look at the four batch pointers for NULL only)
+    const float *im_ref = (const float*)a.image_ref, *im = (const float*)a.image, *jm_ref = (const float*)a.jitter_ref, *jm = (const float*)a.jitter;
+    const int rc = pair_tiles_args_ok(a.flow_out12, a.flow_out21, im_ref, im, jm_ref, jm, a.jitter_channels,
                                       a.batch_size, a.height, a.width, a.tile_hit1, a.tile_hit2, a.image_size, a.list_header,
                                       a.list_entries, a.list_capacity);
     if (rc != MR_OK) return rc;
@@ -1424,12 +1448,18 @@ int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
     q.unit_grad = a.unit_grad;
     q.tile_max = reinterpret_cast<unsigned*>(q.partial + 2LL * a.batch_size * tiles_x * tiles_y * 2);
     q.rec = (const float4*)a.records;
-    // (the form -- records / unit gradient / loss only -- and the criterion are chosen here, once per launch)
+    // (the form -- records / unit gradient / loss only --, the criterion and the batch's element types are chosen here, once
+    // per launch)
     const bool l2 = a.criterion == MR_CRITERION_L2;
+#define MR_PICK_FORM(L1K, L2K)                                 \
+    (a.records ? (l2 ? L2K<true, true> : L1K<true, true>)      \
+     : grad    ? (l2 ? L2K<true> : L1K<true>)                  \
+               : (l2 ? L2K<false> : L1K<false>))
     void (*kernel)(FlowPairFwdParams) =
-        a.records ? (l2 ? flow_pair_forward_tiles_l2_kernel<true, true> : flow_pair_forward_tiles_kernel<true, true>)
-        : grad    ? (l2 ? flow_pair_forward_tiles_l2_kernel<true> : flow_pair_forward_tiles_kernel<true>)
-                  : (l2 ? flow_pair_forward_tiles_l2_kernel<false> : flow_pair_forward_tiles_kernel<false>);
+        a.image_dtype == MR_DTYPE_F32 ? MR_PICK_FORM(flow_pair_forward_tiles_kernel, flow_pair_forward_tiles_l2_kernel)
+        : a.mask_dtype == MR_DTYPE_U8 ? MR_PICK_FORM(flow_pair_forward_tiles_bf16u8_kernel, flow_pair_forward_tiles_l2_bf16u8_kernel)
+                                      : MR_PICK_FORM(flow_pair_forward_tiles_bf16f32_kernel, flow_pair_forward_tiles_l2_bf16f32_kernel);
+#undef MR_PICK_FORM
     hipLaunchKernelGGL(kernel, dim3(listed_grid(a.tile_bound, a.list_capacity)), dim3(256), 0, s, q);
     MR_CHECK_LAUNCH();
     hipLaunchKernelGGL(pair_consist_finalize_tiles_kernel, dim3(a.batch_size), dim3(256), 0, s, (const float*)a.workspace,
@@ -1444,18 +1474,18 @@ int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
     return MR_OK;
 }
 
-extern "C" int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+extern "C" int mr_flow_pair_forward_grad_tiles_typed(const float* mask_flow1, const float* mask_flow2, const float* flow12,
                                                     const float* flow21, int64_t flow_bstride, const float* flow12_scale,
                                                     const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
                                                     float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
-                                                    const float* image_ref, const float* image, const float* jitter_ref,
-                                                    const float* jitter, int jitter_channels, void* workspace,
+                                                    const void* image_ref, const void* image, const void* jitter_ref,
+                                                    const void* jitter, int jitter_channels, void* workspace,
                                                     int64_t workspace_bytes, float* sums, float* loss_fwd, float* loss_bwd,
                                                     int batch_size, int image_size, int height, int width, float distance_thresh,
                                                     float warp_thresh, float pair_thresh, const void* list_header,
                                                     const void* list_entries, int64_t list_capacity, int64_t tile_bound,
                                                     float* unit_grad, float* unit_grad_max, float* loss_sum,
-                                                    void* scatter_work, mr_stream_t stream, int criterion) {
+                                                    void* scatter_work, mr_stream_t stream, int criterion, int image_dtype, int mask_dtype) {
     if (!unit_grad || !unit_grad_max) return MR_ERR_BADARG;
     FlowPairFwdArgs a{};
     a.mask_flow1 = mask_flow1; a.mask_flow2 = mask_flow2; a.flow12 = flow12; a.flow21 = flow21; a.flow_bstride = flow_bstride;
@@ -1469,8 +1499,27 @@ extern "C" int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, con
     a.distance_thresh = distance_thresh; a.warp_thresh = warp_thresh; a.pair_thresh = pair_thresh;
     a.list_header = list_header; a.list_entries = list_entries; a.list_capacity = list_capacity; a.tile_bound = tile_bound;
     a.unit_grad = unit_grad; a.unit_grad_max = unit_grad_max; a.loss_sum = loss_sum; a.scatter_work = scatter_work;
-    a.criterion = criterion;
+    a.criterion = criterion; a.image_dtype = image_dtype; a.mask_dtype = mask_dtype;
     return launch_flow_pair_forward(a, (hipStream_t)stream);
+}
+
+extern "C" int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                                    const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                                    const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                                    float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                                    const float* image_ref, const float* image, const float* jitter_ref,
+                                                    const float* jitter, int jitter_channels, void* workspace,
+                                                    int64_t workspace_bytes, float* sums, float* loss_fwd, float* loss_bwd,
+                                                    int batch_size, int image_size, int height, int width, float distance_thresh,
+                                                    float warp_thresh, float pair_thresh, const void* list_header,
+                                                    const void* list_entries, int64_t list_capacity, int64_t tile_bound,
+                                                    float* unit_grad, float* unit_grad_max, float* loss_sum,
+                                                    void* scatter_work, mr_stream_t stream, int criterion) {
+    return mr_flow_pair_forward_grad_tiles_typed(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale,
+        flow21_scale, occl1, occl2, flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter,
+        jitter_channels, workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size, image_size, height, width,
+        distance_thresh, warp_thresh, pair_thresh, list_header, list_entries, list_capacity, tile_bound, unit_grad,
+        unit_grad_max, loss_sum, scatter_work, stream, criterion, MR_DTYPE_F32, MR_DTYPE_F32);
 }
 
 extern "C" int mr_flow_pair_forward_grad_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,
@@ -1493,16 +1542,16 @@ extern "C" int mr_flow_pair_forward_grad_tiles(const float* mask_flow1, const fl
                                                 unit_grad_max, loss_sum, scatter_work, stream, MR_CRITERION_L1);
 }
 
-extern "C" int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+extern "C" int mr_flow_pair_forward_tiles_typed(const float* mask_flow1, const float* mask_flow2, const float* flow12,
                                                const float* flow21, int64_t flow_bstride, const float* flow12_scale,
                                                const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
                                                float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
-                                               const float* image_ref, const float* image, const float* jitter_ref,
-                                               const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                               const void* image_ref, const void* image, const void* jitter_ref,
+                                               const void* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
                                                float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
                                                int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
                                                const void* list_header, const void* list_entries, int64_t list_capacity,
-                                               int64_t tile_bound, mr_stream_t stream, int criterion) {
+                                               int64_t tile_bound, mr_stream_t stream, int criterion, int image_dtype, int mask_dtype) {
     FlowPairFwdArgs a{};
     a.mask_flow1 = mask_flow1; a.mask_flow2 = mask_flow2; a.flow12 = flow12; a.flow21 = flow21; a.flow_bstride = flow_bstride;
     a.flow12_scale = flow12_scale; a.flow21_scale = flow21_scale;
@@ -1514,8 +1563,25 @@ extern "C" int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const fl
     a.batch_size = batch_size; a.image_size = image_size; a.height = height; a.width = width;
     a.distance_thresh = distance_thresh; a.warp_thresh = warp_thresh; a.pair_thresh = pair_thresh;
     a.list_header = list_header; a.list_entries = list_entries; a.list_capacity = list_capacity; a.tile_bound = tile_bound;
-    a.criterion = criterion;
+    a.criterion = criterion; a.image_dtype = image_dtype; a.mask_dtype = mask_dtype;
     return launch_flow_pair_forward(a, (hipStream_t)stream);
+}
+
+extern "C" int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                               const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                               const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                               float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                               const float* image_ref, const float* image, const float* jitter_ref,
+                                               const float* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                               float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
+                                               int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
+                                               const void* list_header, const void* list_entries, int64_t list_capacity,
+                                               int64_t tile_bound, mr_stream_t stream, int criterion) {
+    return mr_flow_pair_forward_tiles_typed(mask_flow1, mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale,
+        occl1, occl2, flow_out12, flow_out21, tile_hit1, tile_hit2, image_ref, image, jitter_ref, jitter, jitter_channels,
+        workspace, workspace_bytes, sums, loss_fwd, loss_bwd, batch_size, image_size, height, width, distance_thresh,
+        warp_thresh, pair_thresh, list_header, list_entries, list_capacity, tile_bound, stream, criterion, MR_DTYPE_F32,
+        MR_DTYPE_F32);
 }
 
 extern "C" int mr_flow_pair_forward_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,

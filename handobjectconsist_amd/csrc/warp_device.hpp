@@ -194,6 +194,64 @@ __device__ __forceinline__ Quad quad_of(const Quad2& q, const PairAddr& a) {
     return r;
 }
 
+// Compact image batches (MR_DTYPE_BF16 images, MR_DTYPE_U8 jitter masks): the same row pairs and own values as RAW words --
+// both taps of a row are still ONE load, 4 bytes of bf16 or 2 bytes of u8 at the pair's element offset (PairAddr's offsets are
+// bytes of 4-byte elements: shifted down) -- held in 32-bit registers, pinned like the floats, and widened to fp32 by quad_of /
+// widen (exact: every operation behind them is the fp32 path's).  Pairs start at any element: the loads are aligned to the
+// element only.
+struct QuadH { unsigned n, s; };  // two bf16 per word: west tap in the low half
+struct QuadB { unsigned n, s; };  // two u8 per word: west tap in the low byte
+struct __attribute__((packed, aligned(2))) WordA2 { unsigned v; };
+struct __attribute__((packed, aligned(1))) HalfA1 { unsigned short v; };
+__device__ __forceinline__ QuadH load_quad2(const bf16_t* __restrict__ plane, const PairAddr& a) {
+    const char* base = reinterpret_cast<const char*>(plane);
+    QuadH q;
+    q.n = reinterpret_cast<const WordA2*>(base + (a.o_n >> 1))->v;
+    q.s = reinterpret_cast<const WordA2*>(base + (a.o_s >> 1))->v;
+    return q;
+}
+__device__ __forceinline__ QuadB load_quad2(const uint8_t* __restrict__ plane, const PairAddr& a) {
+    QuadB q;
+    q.n = reinterpret_cast<const HalfA1*>(plane + (a.o_n >> 2))->v;
+    q.s = reinterpret_cast<const HalfA1*>(plane + (a.o_s >> 2))->v;
+    return q;
+}
+__device__ __forceinline__ void pin(unsigned& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void pin(QuadH& q) { pin(q.n); pin(q.s); }
+__device__ __forceinline__ void pin(QuadB& q) { pin(q.n); pin(q.s); }
+__device__ __forceinline__ Quad quad_of(const QuadH& q, const PairAddr& a) {
+    const float nx = __uint_as_float(q.n << 16), ny = __uint_as_float(q.n & 0xffff0000u);
+    const float sx = __uint_as_float(q.s << 16), sy = __uint_as_float(q.s & 0xffff0000u);
+    Quad r;
+    r.nw = a.shr ? ny : nx; r.ne = a.shl ? nx : ny;
+    r.sw = a.shr ? sy : sx; r.se = a.shl ? sx : sy;
+    return r;
+}
+__device__ __forceinline__ Quad quad_of(const QuadB& q, const PairAddr& a) {
+    const float nx = (float)(q.n & 0xffu), ny = (float)(q.n >> 8), sx = (float)(q.s & 0xffu), sy = (float)(q.s >> 8);
+    Quad r;
+    r.nw = a.shr ? ny : nx; r.ne = a.shl ? nx : ny;
+    r.sw = a.shr ? sy : sx; r.se = a.shl ? sx : sy;
+    return r;
+}
+// what a thread holds of one element / one row pair of a plane of T between the load and the widening
+template <typename T> struct BatchElem;
+template <> struct BatchElem<float> {
+    typedef Quad2 quad2; typedef float word;
+    static __device__ __forceinline__ float load(const float* __restrict__ p, int64_t i) { return p[i]; }
+    static __device__ __forceinline__ float widen(float w) { return w; }
+};
+template <> struct BatchElem<bf16_t> {
+    typedef QuadH quad2; typedef unsigned word;
+    static __device__ __forceinline__ unsigned load(const bf16_t* __restrict__ p, int64_t i) { return p[i]; }
+    static __device__ __forceinline__ float widen(unsigned w) { return __uint_as_float(w << 16); }
+};
+template <> struct BatchElem<uint8_t> {
+    typedef QuadB quad2; typedef unsigned word;
+    static __device__ __forceinline__ unsigned load(const uint8_t* __restrict__ p, int64_t i) { return p[i]; }
+    static __device__ __forceinline__ float widen(unsigned w) { return (float)w; }
+};
+
 __device__ __forceinline__ void nearest_idx(float ix, float iy, int& xn, int& yn) {
     const float rx = rintf(ix), ry = rintf(iy);  // round half to even, as nearbyint
     xn = (rx == rx) ? (int)fminf(fmaxf(rx, -4.0f), 1.0e9f) : -4;
@@ -421,12 +479,15 @@ struct DirTaps {
     PairAddr a;
     float2 uv;
 };
-struct DirRaw2 {  // as loaded: one 8-byte pair per tap row
-    Quad2 src[3];
-    Quad2 jit[3];
-    float tgt[3];
-    float jd;
+// IT / MT: the element types of the images and of the jitter masks (float, or the compact batch's bf16_t / uint8_t: below)
+template <typename IT, typename MT>
+struct DirRaw2T {  // as loaded: one pair per tap row (8 bytes of float, 4 of bf16, 2 of u8), widened by unpack()
+    typename BatchElem<IT>::quad2 src[3];
+    typename BatchElem<MT>::quad2 jit[3];
+    typename BatchElem<IT>::word tgt[3];
+    typename BatchElem<MT>::word jd;
 };
+typedef DirRaw2T<float, float> DirRaw2;
 struct DirRaw {
     Quad src[3];
     Quad jit[3];
@@ -476,36 +537,40 @@ __device__ __forceinline__ void pair_load(const DirTaps& d, const float* __restr
 }
 
 // ... split for callers that can request the pixel's own values (target, direct jitter) BEFORE the flow is known:
-__device__ __forceinline__ void pair_load_own(const float* __restrict__ tgt, const float* __restrict__ jdirect, int Cj, int b,
-                                              int64_t pix, int64_t hw, DirRaw2& r) {
+template <typename IT, typename MT>
+__device__ __forceinline__ void pair_load_own(const IT* __restrict__ tgt, const MT* __restrict__ jdirect, int Cj, int b,
+                                              int64_t pix, int64_t hw, DirRaw2T<IT, MT>& r) {
 #pragma unroll
-    for (int c = 0; c < 3; c++) r.tgt[c] = tgt[((int64_t)b * 3 + c) * hw + pix];
-    r.jd = jdirect[(int64_t)b * Cj * hw + pix];
+    for (int c = 0; c < 3; c++) r.tgt[c] = BatchElem<IT>::load(tgt, ((int64_t)b * 3 + c) * hw + pix);
+    r.jd = BatchElem<MT>::load(jdirect, (int64_t)b * Cj * hw + pix);
 }
-__device__ __forceinline__ void pair_load_taps(const DirTaps& d, const float* __restrict__ src,
-                                               const float* __restrict__ jwarp, int Cj, int b, int64_t hw, DirRaw2& r) {
+template <typename IT, typename MT>
+__device__ __forceinline__ void pair_load_taps(const DirTaps& d, const IT* __restrict__ src,
+                                               const MT* __restrict__ jwarp, int Cj, int b, int64_t hw, DirRaw2T<IT, MT>& r) {
 #pragma unroll
     for (int c = 0; c < 3; c++) r.src[c] = load_quad2(src + ((int64_t)b * 3 + c) * hw, d.a);
     r.jit[0] = load_quad2(jwarp + (int64_t)b * Cj * hw, d.a);
-    const F2 z{0.0f, 0.0f};
-    r.jit[1].n = z; r.jit[1].s = z; r.jit[2].n = z; r.jit[2].s = z;
+    const typename BatchElem<MT>::quad2 z{};
+    r.jit[1] = z; r.jit[2] = z;
 }
 
-__device__ __forceinline__ void pin(DirRaw2& r) {
+template <typename IT, typename MT>
+__device__ __forceinline__ void pin(DirRaw2T<IT, MT>& r) {
 #pragma unroll
     for (int c = 0; c < 3; c++) { pin(r.src[c]); pin(r.jit[c]); pin(r.tgt[c]); }
     pin(r.jd);
 }
 
-__device__ __forceinline__ DirRaw unpack(const DirRaw2& r2, const PairAddr& a) {
+template <typename IT, typename MT>
+__device__ __forceinline__ DirRaw unpack(const DirRaw2T<IT, MT>& r2, const PairAddr& a) {
     DirRaw r;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         r.src[c] = quad_of(r2.src[c], a);
         r.jit[c] = quad_of(r2.jit[c], a);
-        r.tgt[c] = r2.tgt[c];
+        r.tgt[c] = BatchElem<IT>::widen(r2.tgt[c]);
     }
-    r.jd = r2.jd;
+    r.jd = BatchElem<MT>::widen(r2.jd);
     return r;
 }
 

@@ -9,7 +9,7 @@ from handobjectconsist_amd.datasets import handutils
 
 
 def frames_to_batch(frames, affinetrans, inp_res, flip=None, mean=(0.5, 0.5, 0.5), std=(1.0, 1.0, 1.0),
-                    jittermask=True, mask_channels=3):
+                    jittermask=True, mask_channels=3, image_dtype=torch.float32, mask_dtype=torch.float32):
     """
     Args:
         frames: uint8 CUDA tensor [N, Hs, Ws, 3] -- the decoded (and colour-jittered) frames, HWC as PIL
@@ -19,10 +19,19 @@ def frames_to_batch(frames, affinetrans, inp_res, flip=None, mean=(0.5, 0.5, 0.5
         inp_res: (W, H) of the network input
         flip: optional [N] bools -- mirror the frame left-right first (handobjset.py:124-125)
         mean / std: ``normalize`` constants (the reference: 0.5 / 1 unless normalize_img)
+        image_dtype: ``torch.float32`` (the default, the reference's batch format) or ``torch.bfloat16`` -- the fp32 value
+            rounded to nearest-even, i.e. ``image_fp32.bfloat16()`` bit for bit
+        mask_dtype: ``torch.float32`` or ``torch.uint8`` (1 where the fp32 mask is 1, else 0)
+            (bfloat16 + uint8 is the COMPACT batch, DESIGN section 14: a third of the bytes, read as it is by the fused pair
+            kernels and the bf16 trunk)
 
     Returns:
-        image [N,3,H,W] float32, jittermask [N,mask_channels,H,W] float32 in {0,1} (or None)
+        image [N,3,H,W] of ``image_dtype``, jittermask [N,mask_channels,H,W] of ``mask_dtype`` in {0,1} (or None)
     """
+    if image_dtype not in _lib.IMAGE_DTYPES:
+        raise ValueError(f"image_dtype must be torch.float32 or torch.bfloat16, got {image_dtype!r}")
+    if mask_dtype not in _lib.MASK_DTYPES:
+        raise ValueError(f"mask_dtype must be torch.float32 or torch.uint8, got {mask_dtype!r}")
     _lib.check_cuda(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError("frames must be uint8 [N, Hs, Ws, 3]")
@@ -43,11 +52,14 @@ def frames_to_batch(frames, affinetrans, inp_res, flip=None, mean=(0.5, 0.5, 0.5
         flip_d = torch.as_tensor(np.asarray(flip, dtype=np.uint8)).to(dev, non_blocking=True)
         if flip_d.shape != (N,):
             raise ValueError("flip must have one entry per frame")
-    image = torch.empty((N, 3, H, W), dtype=torch.float32, device=dev)
-    mask = torch.empty((N, mask_channels, H, W), dtype=torch.float32, device=dev) if jittermask else None
+    image = torch.empty((N, 3, H, W), dtype=image_dtype, device=dev)
+    mask = torch.empty((N, mask_channels, H, W), dtype=mask_dtype, device=dev) if jittermask else None
     wbytes = int(_lib.load().mr_frames_to_batch_workspace_bytes(N, H, W))
     work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-    _lib.call("mr_frames_to_batch", _lib.ptr(frames), _lib.ptr(coeffs_d), _lib.ptr(flip_d), *[float(m) for m in mean],
-              *[float(s) for s in std], _lib.ptr(work), wbytes, _lib.ptr(image), _lib.ptr(mask), int(mask_channels), N,
-              Hs, Ws, H, W, _lib.stream_ptr(dev))
+    args = (_lib.ptr(frames), _lib.ptr(coeffs_d), _lib.ptr(flip_d), *[float(m) for m in mean], *[float(s) for s in std],
+            _lib.ptr(work), wbytes, _lib.ptr(image), _lib.ptr(mask), int(mask_channels), N, Hs, Ws, H, W, _lib.stream_ptr(dev))
+    if image_dtype == torch.float32 and mask_dtype == torch.float32:
+        _lib.call("mr_frames_to_batch", *args)
+    else:
+        _lib.call("mr_frames_to_batch_typed", *args, _lib.DTYPE_CODES[image_dtype], _lib.DTYPE_CODES[mask_dtype])
     return image, mask

@@ -190,10 +190,12 @@ class HandObjSet(Dataset):
         return samples
 
 
-def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                   image_dtype=torch.float32, mask_dtype=torch.float32):
     """Collated batch (one frame's dict, or a list of them from ``seq_extend_collate``) -> device-resident
     tensors with ``image`` / ``jittermask`` built by the GPU from ``frame`` / ``affinetrans`` / ``flip``.
-    All frames of the step go through ONE ``frames_to_batch`` launch."""
+    All frames of the step go through ONE ``frames_to_batch`` launch.  ``image_dtype`` / ``mask_dtype``: the batch's element
+    types as ``frames_to_batch`` takes them (``torch.bfloat16`` / ``torch.uint8``: the compact batch)."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
     out = []
     for d in dicts:
@@ -205,7 +207,8 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
         affines = np.concatenate([np.asarray(dicts[i]["affinetrans"]) for i in with_frames], 0)
         flips = np.concatenate([np.asarray(dicts[i]["flip"]).reshape(-1) for i in with_frames], 0)
         m, s = (mean, std) if normalize_img else ((0.5, 0.5, 0.5), (1.0, 1.0, 1.0))
-        image, mask = frames_mod.frames_to_batch(frames, affines, inp_res, flip=flips, mean=m, std=s)
+        image, mask = frames_mod.frames_to_batch(frames, affines, inp_res, flip=flips, mean=m, std=s, image_dtype=image_dtype,
+                                                 mask_dtype=mask_dtype)
         lo = 0
         for i in with_frames:
             n = len(dicts[i]["frame"])

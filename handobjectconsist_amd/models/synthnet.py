@@ -429,8 +429,13 @@ class SynthMeshRegNet(nn.Module):
             self.base_net.to(memory_format=torch.channels_last)
 
     def encode(self, images):
-        """ResNet-18 trunk -> [B,512] fp32 features (optionally computed under bf16 autocast)."""
+        """ResNet-18 trunk -> [B,512] fp32 features (optionally computed under bf16 autocast).  ``images``: fp32, or the
+        compact batch's bf16 -- under autocast the first convolution takes it as it is (no cast launch); without autocast it
+        is cast to that convolution's weight type."""
         if self.encoder_dtype == torch.float32:
+            wdtype = self.base_net.conv1.weight.dtype
+            if images.dtype != wdtype and not torch.is_autocast_enabled("cuda"):
+                images = images.to(wdtype)
             return self.base_net(images)
         with torch.autocast("cuda", dtype=self.encoder_dtype):
             feats = self.base_net(images)

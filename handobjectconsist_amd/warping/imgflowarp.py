@@ -307,12 +307,18 @@ def pair_consist(
         image: Image of unannotated frame
         outputs: "full" (reference behaviour) or "loss" (masks / warps / diffs are None)
 
+    The kernels behind this function (dense and tile-list pair kernels, ``warp``) read fp32: a compact batch (bf16 images,
+    uint8 jitter masks -- ``frames_to_batch(..., image_dtype=, mask_dtype=)``) is upcast ONCE here with ``.float()``, which
+    is exact.  ``opticalflow.flow_pair_loss`` is the path that reads a compact batch as it is.
+
     Returns:
         warp_loss [batch_size], masks, warps, diffs
     """
     outputs = outputs or DEFAULT_PAIR_OUTPUTS
     image_ref, image = image_ref.cuda(), image.cuda()
     jitter_mask_ref, jitter_mask = jitter_mask_ref.cuda(), jitter_mask.cuda()
+    image_ref, image = (x.float() if x.dtype == torch.bfloat16 else x for x in (image_ref, image))
+    jitter_mask_ref, jitter_mask = (x.float() if x.dtype == torch.uint8 else x for x in (jitter_mask_ref, jitter_mask))
     # (the fused kernels fetch the two taps of a row with one 8-byte load: images at least 2 wide)
     crit = _fused_criterion(criterion)
     if crit is not None and image.shape[1] == 3 and jitter_mask.shape[1] in (1, 3) and image.shape[-1] >= 2:

@@ -571,7 +571,14 @@ class _FlowPairLossFunction(torch.autograd.Function):
         where = _lib.tile_list(r["work"], B2, r["F"], is_) if r["bound"] != 0 else None
         if where is None or r["vid"] is None:
             raise RuntimeError("the fused pair node needs the render's tile list and per-pixel records")
-        im_ref, im, jm_ref, jm = (_lib.contig(x) for x in (image_ref, image, jitter_ref, jitter))
+        # the compact batch as it is (bf16 images with uint8 / fp32 masks); anything else is read as fp32, cast where it is not
+        dtypes = _lib.batch_dtypes(image_ref, image, jitter_ref, jitter) or (torch.float32, torch.float32)
+        compact = dtypes[0] != torch.float32
+        if compact and ctx.needs_input_grad[2] and not USE_UNIT_GRADIENT:
+            raise RuntimeError("the recomputing backward (USE_UNIT_GRADIENT = False) reads fp32 images only: a compact batch "
+                               "needs the unit-gradient form, or image.float() / jitter_mask.float()")
+        im_ref, im = _lib.contig(image_ref, dtypes[0]), _lib.contig(image, dtypes[0])
+        jm_ref, jm = _lib.contig(jitter_ref, dtypes[1]), _lib.contig(jitter, dtypes[1])
         Cj = jm.shape[1]
         if (im.shape != (B, 3, height, width) or im_ref.shape != im.shape or Cj not in (1, 3)
                 or jm.shape != (B, Cj, height, width) or jm_ref.shape != jm.shape or width < 2):
@@ -593,10 +600,18 @@ class _FlowPairLossFunction(torch.autograd.Function):
             # the images' covered-tile lists: the finalize launch writes them, the backward hands out its workgroups over them
             scatter_work = (torch.empty((int(_lib.load().mr_flow_pair_scatter_work_bytes(B, is_)),), dtype=torch.uint8, device=dev)
                             if USE_SCATTER_WORK else None)
-            _lib.crit_call("mr_flow_pair_forward_grad_tiles", int(crit), *args, _lib.ptr(unit_grad), _lib.ptr(unit_max),
-                           _lib.ptr(loss_sum), _lib.ptr(scatter_work), st)
+            more = (_lib.ptr(unit_grad), _lib.ptr(unit_max), _lib.ptr(loss_sum), _lib.ptr(scatter_work), st)
+            if compact:
+                _lib.call("mr_flow_pair_forward_grad_tiles_typed", *args, *more, int(crit), _lib.DTYPE_CODES[dtypes[0]],
+                          _lib.DTYPE_CODES[dtypes[1]])
+            else:
+                _lib.crit_call("mr_flow_pair_forward_grad_tiles", int(crit), *args, *more)
         else:
-            _lib.crit_call("mr_flow_pair_forward_tiles", int(crit), *args, st)
+            if compact:
+                _lib.call("mr_flow_pair_forward_tiles_typed", *args, st, int(crit), _lib.DTYPE_CODES[dtypes[0]],
+                          _lib.DTYPE_CODES[dtypes[1]])
+            else:
+                _lib.crit_call("mr_flow_pair_forward_tiles", int(crit), *args, st)
             loss_sum = loss_bwd + loss_fwd
         # (the flows are defined under the covered tiles only: the list rides along with them, as for get_opticalflow(sparse_flows=True))
         if tile_out is not None:
@@ -688,7 +703,12 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
     output where the pair goes through ``pairstep`` (ABI 8: (hand, object) parts whose vertices want a gradient), a
     ``torch.mean`` otherwise.  ``criterion``: the photometric criterion as its MR_CRITERION_* code -- ``_lib.CRITERION_L1``
     (``PyramidCriterion("l1")``, the default) or ``_lib.CRITERION_L2`` (``PyramidCriterion("l2")``;
-    ``imgflowarp._fused_criterion`` maps a criterion object to its code)."""
+    ``imgflowarp._fused_criterion`` maps a criterion object to its code).
+
+    Images: fp32 (jitter masks of any type are then read as fp32), or the COMPACT batch of ``frames_to_batch(...,
+    image_dtype=torch.bfloat16, mask_dtype=torch.uint8)`` as it is -- both images bf16, both masks uint8 (or both fp32) --,
+    which the kernels widen on load: the losses equal those of ``image.float()`` / ``jitter_mask.float()`` bit for bit and no
+    cast is launched.  Any other combination of types: ``None``."""
     if criterion not in (_lib.CRITERION_L1, _lib.CRITERION_L2):
         raise ValueError(f"criterion must be an MR_CRITERION_* code (0: l1, 1: l2), got {criterion!r}")
     parts = isinstance(verts_cam[0], (tuple, list))  # (hand, object) vertex tensors per frame + (hand, object) faces
@@ -709,7 +729,9 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
             and USE_PIXEL_RECORDS and USE_TILE_LIST_WARP and _vertex_color_path(neurenderer, True)
             and hasattr(neurenderer, "render_projected_vertex_colors") and tensors_ok
             and _stacked_flow_node_ok(neurenderer, V) and image.is_cuda
-            and image.dtype == torch.float32 and image.dim() == 4 and image.shape[1] == 3 and image.shape[-1] >= 2
+            # (fp32 images, or the compact batch: bf16 images with uint8 / fp32 jitter masks, both frames of one type)
+            and _lib.batch_dtypes(image_ref, image, jitter_mask_ref, jitter_mask) is not None
+            and image.dim() == 4 and image.shape[1] == 3 and image.shape[-1] >= 2
             and jitter_mask.dim() == 4 and jitter_mask.shape[1] in (1, 3)
             # (the node differentiates w.r.t. the vertices only: images that want a gradient take the composed path)
             and not (image.requires_grad or image_ref.requires_grad or jitter_mask.requires_grad or jitter_mask_ref.requires_grad)):

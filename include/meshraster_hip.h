@@ -101,7 +101,10 @@ typedef void* mr_stream_t;
  *    backward's workgroups are handed out over), mr_flow_pair_scatter_work_bytes;
  * 8: mr_pair_step_* (the frame-pair step behind one argument struct), mr_pixel_map_terms;
  * 9: the pair loss's photometric criterion (MR_CRITERION_*): *_crit forms of the seven entry points that form the loss or
- *    its gradient, MrPairStep.criterion. */
+ *    its gradient, MrPairStep.criterion.
+ * Additions that change no existing signature keep the number: the compact image batch (MR_DTYPE_*: the *_typed forms of
+ * mr_frames_to_batch and of the two flow-pair forward entry points, the dtype byte pair in MrPairStep.reserved); a library
+ * without them fails the binding's symbol check, not the version check. */
 #define MR_ABI_VERSION 9
 MR_API int mr_abi_version(void);
 /* 1 if the calling thread's CURRENT HIP device is a gfx950, else 0.
@@ -504,6 +507,14 @@ MR_API int mr_flow_finalize_backward(const float* grad_flow, const float* mask_p
  * the form without the suffix is that call with MR_CRITERION_L1.  Any other value: MR_ERR_BADARG. */
 #define MR_CRITERION_L1 0
 #define MR_CRITERION_L2 1
+/* Element types of an image batch.  The default batch is fp32 images + fp32 jitter masks; the COMPACT batch is bf16 images
+ * (the fp32 value rounded to nearest-even) + u8 jitter masks (1 where the fp32 mask is 1, else 0).  Consumers widen on load:
+ * bf16 -> fp32 is exact, so a compact batch gives what the fp32 path gives for image.float() / mask.float(), bit for bit.
+ * The fused pair kernels exist for (image, mask) = (F32, F32), (BF16, U8) and (BF16, F32): other pairs of valid codes return
+ * MR_ERR_NOTIMPL, codes that name no type (or a type the operand cannot have) MR_ERR_BADARG. */
+#define MR_DTYPE_F32 0
+#define MR_DTYPE_BF16 1
+#define MR_DTYPE_U8 2
 
 /* Bytes of device workspace mr_pair_consist_forward needs (per-block partial sums). */
 MR_API int64_t mr_pair_consist_workspace_bytes(int batch_size, int height, int width);
@@ -675,6 +686,17 @@ MR_API int mr_flow_pair_forward_tiles_crit(const float* mask_flow1, const float*
                                            int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
                                            const void* list_header, const void* list_entries, int64_t list_capacity,
                                            int64_t tile_bound, mr_stream_t stream, int criterion);
+/* ... on an image batch of the element types image_dtype / mask_dtype (see mr_flow_pair_forward_grad_tiles_typed). */
+MR_API int mr_flow_pair_forward_tiles_typed(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                           const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                           const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                           float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                           const void* image_ref, const void* image, const void* jitter_ref,
+                                           const void* jitter, int jitter_channels, void* workspace, int64_t workspace_bytes,
+                                           float* sums, float* loss_fwd, float* loss_bwd, int batch_size, int image_size,
+                                           int height, int width, float distance_thresh, float warp_thresh, float pair_thresh,
+                                           const void* list_header, const void* list_entries, int64_t list_capacity,
+                                           int64_t tile_bound, mr_stream_t stream, int criterion, int image_dtype, int mask_dtype);
 MR_API int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
                                             const int32_t* vertex_id_map, const float* flows, const float* image_ref,
                                             const float* image, const float* jitter_ref, const float* jitter,
@@ -735,6 +757,22 @@ MR_API int mr_flow_pair_forward_grad_tiles_crit(const float* mask_flow1, const f
                                                 const void* list_entries, int64_t list_capacity, int64_t tile_bound,
                                                 float* unit_grad, float* unit_grad_max, float* loss_sum,
                                                 void* scatter_work, mr_stream_t stream, int criterion);
+/* ... on an image batch of the element types image_dtype / mask_dtype (MR_DTYPE_*; both images of one type, both jitter
+ * masks of one type).  (F32, F32) is the call above.  Same kernels' arithmetic after the loads: the results equal the fp32
+ * call's on the widened batch bit for bit. */
+MR_API int mr_flow_pair_forward_grad_tiles_typed(const float* mask_flow1, const float* mask_flow2, const float* flow12,
+                                                const float* flow21, int64_t flow_bstride, const float* flow12_scale,
+                                                const float* flow21_scale, float* occl1, float* occl2, float* flow_out12,
+                                                float* flow_out21, const uint8_t* tile_hit1, const uint8_t* tile_hit2,
+                                                const void* image_ref, const void* image, const void* jitter_ref,
+                                                const void* jitter, int jitter_channels, void* workspace,
+                                                int64_t workspace_bytes, float* sums, float* loss_fwd, float* loss_bwd,
+                                                int batch_size, int image_size, int height, int width, float distance_thresh,
+                                                float warp_thresh, float pair_thresh, const void* list_header,
+                                                const void* list_entries, int64_t list_capacity, int64_t tile_bound,
+                                                float* unit_grad, float* unit_grad_max, float* loss_sum,
+                                                void* scatter_work, mr_stream_t stream, int criterion, int image_dtype,
+                                                 int mask_dtype);
 MR_API int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, const uint32_t* tile_hit, const float* weight_map,
                                             const int32_t* vertex_id_map, const float* unit_grad, const float* unit_grad_max,
                                             const float* sums, const float* grad_loss_fwd, const float* grad_loss_bwd,
@@ -767,7 +805,11 @@ MR_API int mr_flow_pair_backward_unit_tiles(const int32_t* face_index_map, const
  *     same forward call again sets MR_PAIR_STEP_GRAD_BUFFER_USED in `flags` for the later calls (the buffer is then cleared
  *     first).
  *   criterion (ABI 9): MR_CRITERION_L1 or MR_CRITERION_L2, the pair loss's criterion (forward call; the backward's scatter
- *     does not depend on it); reserved: zero. */
+ *     does not depend on it);
+ *   reserved: the element types of the image batch (the field keeps its name: bindings list it), image dtype in bits 0-7,
+ *     jitter-mask dtype in bits 8-15 (MR_DTYPE_*), every other bit zero.  Zero = fp32 images and masks, what it always meant;
+ *     image_ref / image / jitter_ref / jitter then point to elements of those types whatever the fields' declared type says.
+ *     Forward call only (the backward reads no image). */
 #define MR_PAIR_STEP_GRAD_BUFFER_USED 1
 /* flags bit 1 (forward call): every stage as a launch of its own, as in ABI 8's first form -- the vertex stage + stacked faces
  * (mr_flow_pair_prologue_parts, which also clears the list header) otherwise run inside the render's binning pass.  Same
@@ -824,6 +866,15 @@ MR_API int mr_frames_to_batch(const uint8_t* frames, const double* coeffs, const
                               float std2, void* workspace, int64_t workspace_bytes, float* image,
                               float* jittermask, int mask_channels, int num_frames, int src_height,
                               int src_width, int height, int width, mr_stream_t stream);
+/* ... writing the element types image_dtype (MR_DTYPE_F32 or MR_DTYPE_BF16) and mask_dtype (MR_DTYPE_F32 or MR_DTYPE_U8):
+ * the bf16 image is the round-to-nearest-even of the fp32 image's value, the u8 mask is 1 where the fp32 mask is 1, else 0.
+ * mr_frames_to_batch is this call with (F32, F32).  Any other code: MR_ERR_BADARG. */
+MR_API int mr_frames_to_batch_typed(const uint8_t* frames, const double* coeffs, const uint8_t* flip,
+                                    float mean0, float mean1, float mean2, float std0, float std1,
+                                    float std2, void* workspace, int64_t workspace_bytes, void* image,
+                                    void* jittermask, int mask_channels, int num_frames, int src_height,
+                                    int src_width, int height, int width, mr_stream_t stream, int image_dtype,
+                                    int mask_dtype);
 
 /* ---- trainer side: BatchNorm with frozen statistics + residual add + ReLU -----------------
  * The reference trains with --freeze_batchnorm (trainmeshwarp.py:205-206, 237-240): every BatchNorm2d of the
