@@ -23,6 +23,16 @@ def _layout(x):
     return x.contiguous(), 0
 
 
+def _aligned(t, cl):
+    """``t`` itself, or -- for a channels-last operand whose storage does not start on the boundary of a 4-element
+    access (16 bytes fp32, 8 bytes bf16: a view into a larger buffer) -- a copy that does.  The channels-last kernels
+    have no scalar path and their entry points answer such a pointer with MR_ERR_BADARG; the NCHW kernels take their
+    scalar path for it and need no copy."""
+    if t is not None and cl and t.data_ptr() % (4 * t.element_size()):
+        return t.clone(memory_format=torch.preserve_format)
+    return t
+
+
 class _BnActFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, eps, relu, dup):
@@ -31,11 +41,13 @@ class _BnActFunction(torch.autograd.Function):
         if x.dim() < 2 or x.dtype not in _ACT_DTYPES:
             raise ValueError("expected an fp32 or bf16 [N, C, ...] tensor")
         xc, cl = _layout(x)
+        xc = _aligned(xc, cl)
         rc = None
         if residual is not None:
             if residual.shape != xc.shape or residual.dtype != xc.dtype:
                 raise ValueError("residual must match x")
             rc = residual.contiguous(memory_format=torch.channels_last) if cl else residual.contiguous()
+            rc = _aligned(rc, cl)
         N, C = xc.shape[:2]
         plane = xc[0, 0].numel() if N and C else 0
         w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
@@ -62,8 +74,8 @@ class _BnActFunction(torch.autograd.Function):
         if grad_y is None:
             return (None,) * 9
         fmt = torch.channels_last if cl else torch.contiguous_format
-        g = grad_y.to(xc.dtype).contiguous(memory_format=fmt)
-        g2 = grad_y2.to(xc.dtype).contiguous(memory_format=fmt) if grad_y2 is not None else None
+        g = _aligned(grad_y.to(xc.dtype).contiguous(memory_format=fmt), cl)
+        g2 = _aligned(grad_y2.to(xc.dtype).contiguous(memory_format=fmt), cl) if grad_y2 is not None else None
         dev = xc.device
         grad_x = torch.empty_like(xc)
         grad_r = torch.empty_like(xc) if (rc is not None and need_r) else None
@@ -95,6 +107,7 @@ class _StemPoolFunction(torch.autograd.Function):
         if x.dim() != 4 or x.dtype not in _ACT_DTYPES:
             raise ValueError("expected an fp32 or bf16 [N, C, H, W] tensor")
         xc, cl = _layout(x)
+        xc = _aligned(xc, cl)
         N, C, H, W = xc.shape
         w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
         m, v = running_mean.float().contiguous(), running_var.float().contiguous()
@@ -120,8 +133,8 @@ class _StemPoolFunction(torch.autograd.Function):
         if grad_y is None:
             return (None,) * 7
         fmt = torch.channels_last if cl else torch.contiguous_format
-        g = grad_y.to(xc.dtype).contiguous(memory_format=fmt)
-        g2 = grad_y2.to(xc.dtype).contiguous(memory_format=fmt) if grad_y2 is not None else None
+        g = _aligned(grad_y.to(xc.dtype).contiguous(memory_format=fmt), cl)
+        g2 = _aligned(grad_y2.to(xc.dtype).contiguous(memory_format=fmt), cl) if grad_y2 is not None else None
         grad_x = torch.empty_like(xc)
         grad_w = torch.empty_like(w) if need_w else None
         grad_b = torch.empty_like(b) if need_b else None

@@ -407,19 +407,23 @@ for case in range(min(n_cases, 300)):
         bn.running_mean.copy_(torch.randn(C, generator=g) * 0.4); bn.running_var.copy_(torch.rand(C, generator=g) * 2 + 0.02)
     x = torch.randn(N, C, H, Wd, generator=g).to(dev)
     res = torch.randn(N, C, H, Wd, generator=g).to(dev) if with_res else None
+    dup = bool(ri(0, 2))  # the form the trainer launches: the activation as two autograd outputs, two gradients summed on load
     outs = {}
     for hip in (True, False):
         xs = x.clone().requires_grad_(True)
         rs_ = res.clone().requires_grad_(True) if with_res else None
         bn.zero_grad(set_to_none=True)
         if hip:
-            y = frozen_bn.stem_pool(xs, bn) if stem else frozen_bn.bn_act(xs, bn, residual=rs_, relu=relu)
+            y = frozen_bn.stem_pool(xs, bn, dup=dup) if stem else frozen_bn.bn_act(xs, bn, residual=rs_, relu=relu, dup=dup)
+            y, y_dup = y if dup else (y, None)
         else:
             z = TF.batch_norm(xs, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
             zz = z if rs_ is None else z + rs_
             y = TF.max_pool2d(TF.relu(z), 3, 2, 1) if stem else (TF.relu(zz) if relu else zz)
-        gy = torch.randn(y.shape, generator=torch.Generator().manual_seed(seed)).to(dev)
-        y.backward(gy)
+        gg = torch.Generator().manual_seed(seed)
+        gy, gy2 = torch.randn(y.shape, generator=gg).to(dev), torch.randn(y.shape, generator=gg).to(dev)
+        if dup and hip: torch.autograd.backward([y, y_dup], [gy, gy2])
+        else: y.backward(gy + gy2 if dup else gy)   # the reference on the sum of the two gradients
         outs[hip] = (y.detach(), xs.grad, bn.weight.grad.clone(), bn.bias.grad.clone(), None if rs_ is None else rs_.grad)
     msg = []
     a, b_ = outs[True], outs[False]
@@ -433,7 +437,7 @@ for case in range(min(n_cases, 300)):
     if with_res and int(((a[4] - b_[4]).abs() > 1e-6 * sc(b_[4])).sum()) > max(3, x.numel() // 3000): msg.append("grad residual")
     if msg:
         bad6 += 1
-        print(f"seed {seed} {'stem' if stem else 'bn_act'} shape {(N, C, H, Wd)} relu={relu} res={with_res}: " + "; ".join(msg))
+        print(f"seed {seed} {'stem' if stem else 'bn_act'} shape {(N, C, H, Wd)} relu={relu} res={with_res} dup={dup}: " + "; ".join(msg))
 print(f"sweep 6 (trunk glue kernels): {min(n_cases, 300)} cases, {bad6} with mismatches")
 
 # ---- seventh sweep: frames -> batch (Pillow's nearest affine transform, bit-exact) vs the oracle
