@@ -30,6 +30,8 @@ DTYPE_F32, DTYPE_BF16, DTYPE_U8 = 0, 1, 2
 DTYPE_CODES = {torch.float32: DTYPE_F32, torch.bfloat16: DTYPE_BF16, torch.uint8: DTYPE_U8}
 IMAGE_DTYPES = (torch.float32, torch.bfloat16)
 MASK_DTYPES = (torch.float32, torch.uint8)
+# MR_COLOR_OP_*: the ops of a colour plan (mr_frames_color_augment)
+COLOR_OP_NONE, COLOR_OP_BRIGHTNESS, COLOR_OP_SATURATION, COLOR_OP_HUE, COLOR_OP_CONTRAST = 0, 1, 2, 3, 4
 # (image, mask) pairs the fused pair kernels are instantiated for
 FUSED_BATCH_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.uint8), (torch.bfloat16, torch.float32))
 
@@ -108,6 +110,8 @@ SIGNATURES = {
     "mr_frames_to_batch_workspace_bytes": (_L, [_I, _I, _I]),
     "mr_frames_to_batch": (_I, [_P] * 3 + [_F] * 6 + [_P, _L, _P, _P] + [_I] * 6 + [_P]),
     "mr_frames_to_batch_typed": (_I, [_P] * 3 + [_F] * 6 + [_P, _L, _P, _P] + [_I] * 6 + [_P, _I, _I]),
+    "mr_frames_color_augment_workspace_bytes": (_L, [_I, _I, _I]),
+    "mr_frames_color_augment": (_I, [_P] * 7 + [_L, _I, _I, _I, _P]),
     "mr_bn_act_forward": (_I, [_P] * 6 + [_F, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mr_bn_act_backward_workspace_bytes": (_L, [_I, _I]),
     "mr_bn_act_backward": (_I, [_P] * 8 + [_F, _I, _I, _I] + [_P] * 5 + [_L, _I, _I, _I, _P]),

@@ -1,6 +1,7 @@
 """Decoded frames -> network-input batch on the GPU (``mr_frames_to_batch``): the device counterpart of
 ``transform_img`` + crop + ``to_tensor`` + ``normalize`` + jitter-mask generation that the reference runs
-per sample in its DataLoader workers (meshreg/datasets/handobjset.py:361-379)."""
+per sample in its DataLoader workers (meshreg/datasets/handobjset.py:361-379) -- and, in front of it, of the colour
+augmentation of handobjset.py:339-358 (``mr_frames_color_augment``)."""
 import numpy as np
 import torch
 
@@ -63,3 +64,43 @@ def frames_to_batch(frames, affinetrans, inp_res, flip=None, mean=(0.5, 0.5, 0.5
     else:
         _lib.call("mr_frames_to_batch_typed", *args, _lib.DTYPE_CODES[image_dtype], _lib.DTYPE_CODES[mask_dtype])
     return image, mask
+
+
+def color_augment(frames, plans, flip=None):
+    """Gaussian blur + colour jitter of a batch of decoded frames on the GPU, byte for byte what ``coloraugm``'s host path
+    (Pillow) gives for the same draws.
+
+    Args:
+        frames: uint8 CUDA tensor [N, Hs, Ws, 3]
+        plans: [N, coloraugm.PLAN_LEN] plans of ``coloraugm.draw_color_plan`` (numpy or CPU tensor), one per frame
+        flip: optional [N] bools -- the samples the host path mirrors around its augmentation (the result does not depend
+            on them: every stage is mirror-symmetric)
+
+    Returns:
+        uint8 CUDA tensor [N, Hs, Ws, 3], a new tensor
+    """
+    _lib.check_cuda(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("frames must be uint8 [N, Hs, Ws, 3]")
+    frames = frames.contiguous()
+    N, Hs, Ws, _ = frames.shape
+    plans = np.ascontiguousarray(plans.detach().cpu().numpy() if torch.is_tensor(plans) else plans, dtype=np.float32)
+    if plans.shape != (N, 9):
+        raise ValueError("plans must hold one plan of 9 values per frame")
+    radius = np.ascontiguousarray(plans[:, 0])
+    if not np.all(np.abs(plans[:, 1:5]) <= 255) or np.any(plans[:, 1:5] != np.rint(plans[:, 1:5])):
+        raise ValueError("plans: op codes must be integers (coloraugm.OP_*)")  # (the cast would truncate 1.5 to op 1)
+    codes = np.ascontiguousarray(plans[:, 1:5]).astype(np.int32)
+    values = np.ascontiguousarray(plans[:, 5:9])
+    flip_h = None
+    if flip is not None:
+        flip_h = np.ascontiguousarray(np.asarray(flip, dtype=np.uint8))
+        if flip_h.shape != (N,):
+            raise ValueError("flip must have one entry per frame")
+    out = torch.empty_like(frames)
+    wbytes = int(_lib.load().mr_frames_color_augment_workspace_bytes(N, Hs, Ws))
+    work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=frames.device)
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731  (host arrays: read before the call returns)
+    _lib.call("mr_frames_color_augment", _lib.ptr(frames), _lib.ptr(out), host(flip_h), host(radius), host(codes), host(values),
+              _lib.ptr(work), wbytes, N, Hs, Ws, _lib.stream_ptr(frames.device))
+    return out

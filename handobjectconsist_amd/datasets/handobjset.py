@@ -15,7 +15,9 @@ sampling) re-cut for a GPU-side image path:
 (ho3dv2.py / fhbhands.py): get_image, get_center_scale, get_camintr, get_joints3d, get_hand_verts3d,
 get_obj_verts_trans, get_obj_faces, get_obj_verts_can, get_sides, get_dist_idx.  Colour jitter and blur
 (libyana colortrans + PIL filters on the host, handobjset.py:339-358) are a host callable: ``datasets/coloraugm.py``
-by default (blur pinned by a fixture, jitter restated), ``color_fn=None`` switches them off."""
+by default (blur pinned by a fixture, jitter restated), ``color_fn=None`` switches them off.  ``color_fn="device"``: the same
+draws, applied by ``assemble_batch`` on the GPU (``frames.color_augment``, byte for byte Pillow's result): the sample then
+carries the untouched frame and its ``color_plan``."""
 import random
 import traceback
 
@@ -57,7 +59,12 @@ class HandObjSet(Dataset):
             from handobjectconsist_amd.datasets import coloraugm
 
             color_fn = coloraugm.make_color_fn(jitter=True)
-        self.color_fn = color_fn  # (frame_u8, dataset, color_augm | None, blur_radius) -> (frame_u8, color_augm)
+        elif color_fn == "device":  # the same draws; the pixels are done on the GPU by assemble_batch
+            from handobjectconsist_amd.datasets import coloraugm
+
+            color_fn = coloraugm.make_color_fn(jitter=True, apply="device")
+        # (frame_u8, dataset, color_augm | None, blur_radius) -> (frame_u8, color_augm[, color_plan of a device path])
+        self.color_fn = color_fn
 
     def __len__(self):
         return len(self.pose_dataset)
@@ -105,10 +112,13 @@ class HandObjSet(Dataset):
                 blur_radius = Uniform(low=0, high=1).sample().item() * self.blur_radius
                 if self.color_fn is not None:
                     # (the reference blurs the MIRRORED image, handobjset.py:120-122 before :341; the frame travels unmirrored
-                    # to the GPU kernel, which flips on the fly: mirror, augment, mirror back -- PIL's box-blur passes are
-                    # not symmetric to the last bit)
+                    # to the GPU kernel, which flips on the fly: mirror, augment, mirror back, the reference's order of
+                    # operations kept as it is.  Blur and jitter are mirror-symmetric to the last bit -- each blur case of
+                    # tests/test_oracle_coloraugm.py also runs mirrored -- which is why a device plan carries no flip)
                     view = frame[:, ::-1] if flip else frame
-                    view, color_augm = self.color_fn(view, self, color_augm, blur_radius)
+                    view, color_augm, *plan = self.color_fn(view, self, color_augm, blur_radius)
+                    if plan:
+                        sample["color_plan"] = plan[0]
                     frame = view[:, ::-1] if flip else view
             sample["color_augm"] = color_augm if self.train else None
             sample["frame"] = np.ascontiguousarray(frame)
@@ -194,18 +204,26 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
                    image_dtype=torch.float32, mask_dtype=torch.float32):
     """Collated batch (one frame's dict, or a list of them from ``seq_extend_collate``) -> device-resident
     tensors with ``image`` / ``jittermask`` built by the GPU from ``frame`` / ``affinetrans`` / ``flip``.
-    All frames of the step go through ONE ``frames_to_batch`` launch.  ``image_dtype`` / ``mask_dtype``: the batch's element
+    All frames of the step go through ONE ``frames_to_batch`` launch -- after ``frames.color_augment`` where the dicts carry
+    ``color_plan`` (``HandObjSet(color_fn="device")``).  ``image_dtype`` / ``mask_dtype``: the batch's element
     types as ``frames_to_batch`` takes them (``torch.bfloat16`` / ``torch.uint8``: the compact batch)."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
     out = []
     for d in dicts:
         out.append({k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in d.items()
-                    if k not in ("frame", "affinetrans", "flip")})
+                    if k not in ("frame", "affinetrans", "flip", "color_plan")})
     with_frames = [i for i, d in enumerate(dicts) if "frame" in d]
     if with_frames:
         frames = torch.cat([torch.as_tensor(dicts[i]["frame"]) for i in with_frames], 0).to(device, non_blocking=True)
         affines = np.concatenate([np.asarray(dicts[i]["affinetrans"]) for i in with_frames], 0)
         flips = np.concatenate([np.asarray(dicts[i]["flip"]).reshape(-1) for i in with_frames], 0)
+        planned = [i for i in with_frames if "color_plan" in dicts[i]]
+        if planned and len(planned) != len(with_frames):
+            raise ValueError(f"color_plan in {len(planned)} of {len(with_frames)} frame dicts: a batch mixes samples of "
+                             "HandObjSet(color_fn=\"device\") with samples of a host colour path")
+        if planned:
+            plans = np.concatenate([np.asarray(dicts[i]["color_plan"]) for i in with_frames], 0)
+            frames = frames_mod.color_augment(frames, plans, flip=flips)
         m, s = (mean, std) if normalize_img else ((0.5, 0.5, 0.5), (1.0, 1.0, 1.0))
         image, mask = frames_mod.frames_to_batch(frames, affines, inp_res, flip=flips, mean=m, std=s, image_dtype=image_dtype,
                                                  mask_dtype=mask_dtype)

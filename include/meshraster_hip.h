@@ -876,6 +876,32 @@ MR_API int mr_frames_to_batch_typed(const uint8_t* frames, const double* coeffs,
                                     int src_width, int height, int width, mr_stream_t stream, int image_dtype,
                                     int mask_dtype);
 
+/* ---- dataset pipeline: colour augmentation of the decoded frames (handobjset.py:339-358) ------------------
+ * What datasets/coloraugm.py does per frame on the host with Pillow, for a batch of frames, byte for byte:
+ * ImageFilter.GaussianBlur(blur_radius[n]) (radius 0: a copy), then up to four ops in the order given:
+ * ImageEnhance.Brightness / Color (saturation) / Contrast with the blend factor op_values[n][k], or the hue shift
+ * H <- (H + (int)op_values[n][k]) & 255 through Pillow's RGB <-> HSV conversions.  Every frame has its own plan.
+ *   frames_in, frames_out [N, src_height, src_width, 3] u8 device memory, 4-byte aligned; frames_in == frames_out is
+ *   allowed (the blur goes through the workspace), any other overlap is not.
+ *   flip[N] (or NULL), blur_radius[N], op_codes[N,4], op_values[N,4]: HOST arrays, read before the call returns.
+ *   flip marks the samples the reference mirrors around its augmentation (mirror, augment, mirror back); every stage is
+ *   mirror-symmetric, so the flags do not change the result.
+ * MR_ERR_BADARG: an unknown op code, an op twice in one plan, a non-finite factor, a hue shift that is no integer in
+ * [-127, 127], a radius outside [0, 1024], a misaligned pointer, a workspace that is too small.  MR_ERR_NOTIMPL: a frame
+ * side above 10752 pixels (a line is held in a workgroup's LDS), more than 65535 frames in one call (a frame is a grid
+ * row).  num_frames == 0 or an empty frame: MR_OK, nothing is read or written.
+ * workspace: mr_frames_color_augment_workspace_bytes(N, src_height, src_width) bytes, 16-byte aligned. */
+#define MR_COLOR_OP_NONE 0
+#define MR_COLOR_OP_BRIGHTNESS 1
+#define MR_COLOR_OP_SATURATION 2
+#define MR_COLOR_OP_HUE 3
+#define MR_COLOR_OP_CONTRAST 4
+MR_API int64_t mr_frames_color_augment_workspace_bytes(int num_frames, int src_height, int src_width);
+MR_API int mr_frames_color_augment(const uint8_t* frames_in, uint8_t* frames_out, const uint8_t* flip,
+                                   const float* blur_radius, const int* op_codes, const float* op_values,
+                                   void* workspace, int64_t workspace_bytes, int num_frames, int src_height,
+                                   int src_width, mr_stream_t stream);
+
 /* ---- trainer side: BatchNorm with frozen statistics + residual add + ReLU -----------------
  * The reference trains with --freeze_batchnorm (trainmeshwarp.py:205-206, 237-240): every BatchNorm2d of the
  * ResNet-18 trunk runs in eval mode with trainable affine parameters, followed by ReLU, by "+ identity, ReLU"
