@@ -17,7 +17,9 @@ get_obj_verts_trans, get_obj_faces, get_obj_verts_can, get_sides, get_dist_idx. 
 (libyana colortrans + PIL filters on the host, handobjset.py:339-358) are a host callable: ``datasets/coloraugm.py``
 by default (blur pinned by a fixture, jitter restated), ``color_fn=None`` switches them off.  ``color_fn="device"``: the same
 draws, applied by ``assemble_batch`` on the GPU (``frames.color_augment``, byte for byte Pillow's result): the sample then
-carries the untouched frame and its ``color_plan``."""
+carries the untouched frame and its ``color_plan``.  ``decode="device"`` (needs ``pose_dataset.get_image_bytes``): the sample
+carries the JPEG file's entropy-decoded PACKED FRAME as ``frame_jpeg`` instead of ``frame``; ``assemble_batch`` uploads the
+stacked packed frames once and reconstructs the pixels on the GPU (``jpegdecode.reconstruct``, byte for byte Pillow's decode)."""
 import random
 import traceback
 
@@ -44,7 +46,15 @@ class HandObjSet(Dataset):
     def __init__(self, pose_dataset, center_idx=9, inp_res=(256, 256), max_rot=np.pi, normalize_img=False,
                  split="train", scale_jittering=0.3, center_jittering=0.2, train=True, hue=0.15, saturation=0.5,
                  contrast=0.5, brightness=0.5, blur_radius=0.5, spacing=2, queries=DEFAULT_QUERIES, sides="both",
-                 block_rot=False, sample_nb=None, has_dist2strong=False, color_fn="reference"):
+                 block_rot=False, sample_nb=None, has_dist2strong=False, color_fn="reference", decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
+        if decode == "device":
+            if color_fn not in ("device", None):
+                raise ValueError("decode=\"device\" leaves no pixels on the host: color_fn must be \"device\" or None")
+            if not hasattr(pose_dataset, "get_image_bytes"):
+                raise ValueError("decode=\"device\" needs a pose_dataset with get_image_bytes(idx) (the JPEG file's bytes)")
+        self.decode = decode
         self.pose_dataset = pose_dataset
         self.center_idx, self.inp_res = center_idx, tuple(inp_res)
         self.normalize_img, self.sides = normalize_img, sides
@@ -89,8 +99,14 @@ class HandObjSet(Dataset):
         want_img = "frame" in q
         if want_img:
             center, scale = ds.get_center_scale(idx)
-            frame = np.asarray(ds.get_image(idx))
-            width = frame.shape[1]
+            if self.decode == "device":
+                from handobjectconsist_amd.datasets import jpegdecode
+
+                frame, packed = None, jpegdecode.entropy_decode(ds.get_image_bytes(idx))
+                width = jpegdecode.packed_info(packed)["width"]  # (the file's own, as jpeg_info reads it: no second parse)
+            else:
+                frame = np.asarray(ds.get_image(idx))
+                width = frame.shape[1]
             if flip:
                 center = np.array(center).copy()
                 center[0] = width - center[0]
@@ -110,7 +126,11 @@ class HandObjSet(Dataset):
                 # the blur radius is drawn for EVERY training frame, also for the companions of a sequence that inherit
                 # their colour parameters (handobjset.py:341): part of how far a sample advances torch's RNG stream
                 blur_radius = Uniform(low=0, high=1).sample().item() * self.blur_radius
-                if self.color_fn is not None:
+                if self.color_fn is not None and frame is None:
+                    # the packed frame travels as it is: only the draws happen here (a device colour path never reads pixels)
+                    _, color_augm, *plan = self.color_fn(None, self, color_augm, blur_radius)
+                    sample["color_plan"] = plan[0]
+                elif self.color_fn is not None:
                     # (the reference blurs the MIRRORED image, handobjset.py:120-122 before :341; the frame travels unmirrored
                     # to the GPU kernel, which flips on the fly: mirror, augment, mirror back, the reference's order of
                     # operations kept as it is.  Blur and jitter are mirror-symmetric to the last bit -- each blur case of
@@ -121,7 +141,10 @@ class HandObjSet(Dataset):
                         sample["color_plan"] = plan[0]
                     frame = view[:, ::-1] if flip else view
             sample["color_augm"] = color_augm if self.train else None
-            sample["frame"] = np.ascontiguousarray(frame)
+            if frame is None:
+                sample["frame_jpeg"] = packed
+            else:
+                sample["frame"] = np.ascontiguousarray(frame)
             sample["flip"] = bool(flip)
         if "camintr" in q:
             camintr = ds.get_camintr(idx)
@@ -205,16 +228,32 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
     """Collated batch (one frame's dict, or a list of them from ``seq_extend_collate``) -> device-resident
     tensors with ``image`` / ``jittermask`` built by the GPU from ``frame`` / ``affinetrans`` / ``flip``.
     All frames of the step go through ONE ``frames_to_batch`` launch -- after ``frames.color_augment`` where the dicts carry
-    ``color_plan`` (``HandObjSet(color_fn="device")``).  ``image_dtype`` / ``mask_dtype``: the batch's element
+    ``color_plan`` (``HandObjSet(color_fn="device")``).  Dicts with ``frame_jpeg`` instead of ``frame``
+    (``HandObjSet(decode="device")``, all of a batch or none): the packed frames are stacked, uploaded in one copy and
+    reconstructed by ``jpegdecode.reconstruct`` first.  ``image_dtype`` / ``mask_dtype``: the batch's element
     types as ``frames_to_batch`` takes them (``torch.bfloat16`` / ``torch.uint8``: the compact batch)."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
     out = []
     for d in dicts:
         out.append({k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in d.items()
-                    if k not in ("frame", "affinetrans", "flip", "color_plan")})
-    with_frames = [i for i, d in enumerate(dicts) if "frame" in d]
+                    if k not in ("frame", "frame_jpeg", "affinetrans", "flip", "color_plan")})
+    with_frames = [i for i, d in enumerate(dicts) if "frame" in d or "frame_jpeg" in d]
+    packed = [i for i in with_frames if "frame_jpeg" in dicts[i]]
+    if packed and (len(packed) != len(with_frames) or any("frame" in dicts[i] for i in packed)):
+        raise ValueError(f"frame_jpeg in {len(packed)} of {len(with_frames)} frame dicts: a batch mixes samples of "
+                         "HandObjSet(decode=\"device\") with decoded frames")
     if with_frames:
-        frames = torch.cat([torch.as_tensor(dicts[i]["frame"]) for i in with_frames], 0).to(device, non_blocking=True)
+        if packed:
+            from handobjectconsist_amd.datasets import jpegdecode
+
+            rows = [torch.as_tensor(dicts[i]["frame_jpeg"]) for i in with_frames]
+            if any(r.dim() != 2 for r in rows):
+                raise ValueError("frame_jpeg must be collated: [frames, bytes] per dict, not one sample's flat packed frame")
+            if any(r.shape[1] != rows[0].shape[1] for r in rows):
+                raise ValueError("frame_jpeg: the batch's packed frames differ in size (one frame geometry per batch)")
+            frames = jpegdecode.reconstruct(torch.cat(rows, 0), device)
+        else:
+            frames = torch.cat([torch.as_tensor(dicts[i]["frame"]) for i in with_frames], 0).to(device, non_blocking=True)
         affines = np.concatenate([np.asarray(dicts[i]["affinetrans"]) for i in with_frames], 0)
         flips = np.concatenate([np.asarray(dicts[i]["flip"]).reshape(-1) for i in with_frames], 0)
         planned = [i for i in with_frames if "color_plan" in dicts[i]]
@@ -229,7 +268,7 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
                                                  mask_dtype=mask_dtype)
         lo = 0
         for i in with_frames:
-            n = len(dicts[i]["frame"])
+            n = len(dicts[i]["frame_jpeg" if packed else "frame"])
             out[i]["image"], out[i]["jittermask"] = image[lo:lo + n], mask[lo:lo + n]
             lo += n
     return out if isinstance(batch, (list, tuple)) else out[0]

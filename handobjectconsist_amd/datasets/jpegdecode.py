@@ -1,0 +1,164 @@
+"""JPEG files -> decoded frames in two stages: the serial half of a decode -- marker parsing and
+Huffman decoding -- on the host (``entropy_decode``: bytes -> one PACKED FRAME, a flat uint8 array whose size depends on the
+geometry only), the parallel half -- dequantisation, inverse DCT, chroma upsampling, YCbCr -> RGB -- on the GPU
+(``reconstruct``: a stacked batch of packed frames -> uint8 CUDA [N,H,W,3], byte for byte what Pillow's
+``Image.open(...).convert("RGB")`` gives; the tensor ``frames.color_augment`` / ``frames.frames_to_batch`` take).
+
+Baseline / extended-sequential Huffman streams, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0: what cameras and Pillow write by
+default.  Anything else (progressive, arithmetic, CMYK, ...) raises NotImplementedError -- ``decode_batch`` can hand exactly
+those files to Pillow on request, never silently."""
+import ctypes
+import io
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from handobjectconsist_amd import _lib
+
+INFO_FIELDS = ("width", "height", "components", "luma_h", "luma_v", "restart_interval")
+
+
+def _as_bytes(data):
+    if isinstance(data, np.ndarray):
+        data = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
+    return bytes(data)
+
+
+def _raise(rc, what):
+    if rc == -2:
+        raise NotImplementedError(f"{what}: not a baseline Huffman JPEG with one interleaved scan of grey or YCbCr "
+                                  "4:4:4 / 4:2:2 / 4:2:0 samples (progressive, arithmetic, 12-bit, CMYK, ... are not decoded here)")
+    raise ValueError(f"{what}: malformed or truncated JPEG data")
+
+
+def jpeg_info(data):
+    """Geometry of a JPEG stream from its headers: dict of ``INFO_FIELDS``.  ValueError for malformed streams,
+    NotImplementedError for streams ``entropy_decode`` does not support."""
+    data = _as_bytes(data)
+    info = (ctypes.c_int * 6)()
+    rc = _lib.load().mr_jpeg_info(data, len(data), info)
+    if rc != 0:
+        _raise(rc, "jpeg_info")
+    return dict(zip(INFO_FIELDS, (int(v) for v in info)))
+
+
+def packed_bytes(width, height, components, luma_h, luma_v):
+    n = int(_lib.load().mr_jpeg_packed_bytes(int(width), int(height), int(components), int(luma_h), int(luma_v)))
+    if n < 0:
+        raise ValueError("not a supported frame geometry")
+    return n
+
+
+def entropy_decode(data):
+    """bytes of one JPEG file -> its packed frame, np.uint8 [packed_bytes(geometry)] (the layout: include/meshraster_hip.h).
+    Runs without the GIL; needs no device."""
+    data = _as_bytes(data)
+    lib = _lib.load()
+    info = (ctypes.c_int * 6)()
+    rc = lib.mr_jpeg_info(data, len(data), info)
+    if rc != 0:
+        _raise(rc, "entropy_decode")
+    packed = np.empty(int(lib.mr_jpeg_packed_bytes(*info[:5])), np.uint8)
+    rc = lib.mr_jpeg_entropy_decode(data, len(data), packed.ctypes.data, packed.size)
+    if rc != 0:
+        _raise(rc, "entropy_decode")
+    return packed
+
+
+def packed_info(packed):
+    """The geometry a packed frame carries in its header: dict of ``INFO_FIELDS`` (no parse of the file)."""
+    hdr = np.ascontiguousarray(packed[:64]).view(np.int32)
+    if hdr[0] != _lib.JPEG_MAGIC:
+        raise ValueError("no packed frame")
+    return dict(zip(INFO_FIELDS, (int(hdr[k]) for k in (1, 2, 3, 4, 5, 9))))
+
+
+def batch_geometry(packed_batch):
+    """(width, height, components, luma_h, luma_v) of a [N, bytes] batch of packed frames after checking every frame's
+    header on the host: the device stage does not look at them.  ValueError for a mixed or damaged batch."""
+    if packed_batch.ndim != 2 or packed_batch.dtype != np.uint8 or packed_batch.shape[1] < _lib.JPEG_HEADER_BYTES:
+        raise ValueError("packed_batch must be uint8 [N, bytes] of packed frames")
+    hdr = np.ascontiguousarray(packed_batch[:, :64]).view(np.int32)
+    if np.any(hdr[:, 0] != _lib.JPEG_MAGIC):
+        raise ValueError("packed_batch: a row is no packed frame")
+    if np.any(hdr[:, 1:6] != hdr[:1, 1:6]):
+        raise ValueError("packed_batch mixes frames of different geometries (size, components or sampling)")
+    if np.any(hdr[:, 6:9] < 0) or np.any(hdr[:, 6:9] > 3):
+        raise ValueError("packed_batch: bad table selector")
+    geom = tuple(int(v) for v in hdr[0, 1:6])
+    if int(_lib.load().mr_jpeg_packed_bytes(*geom)) != packed_batch.shape[1]:
+        raise ValueError("packed_batch: the rows' length does not match their geometry")
+    return geom
+
+
+def reconstruct(packed_batch, device):
+    """[N, bytes] packed frames of ONE geometry (numpy or CPU tensor) -> uint8 CUDA [N,H,W,3].  One upload, two launches."""
+    if torch.is_tensor(packed_batch):
+        if packed_batch.is_cuda:
+            raise ValueError("packed_batch lives on the host (its headers are checked there)")
+        packed_batch = packed_batch.numpy()
+    packed_batch = np.ascontiguousarray(packed_batch)
+    if packed_batch.ndim == 2 and packed_batch.shape[0] == 0:
+        raise ValueError("an empty packed_batch has no geometry")
+    width, height, comps, lh, lv = geom = batch_geometry(packed_batch)
+    N = packed_batch.shape[0]
+    dev = torch.device(device)
+    packed_d = torch.from_numpy(packed_batch).to(dev, non_blocking=True)
+    out = torch.empty((N, height, width, 3), dtype=torch.uint8, device=dev)
+    wbytes = int(_lib.load().mr_jpeg_reconstruct_workspace_bytes(N, *geom))
+    work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+    _lib.call("mr_jpeg_reconstruct", _lib.ptr(packed_d), N, width, height, comps, lh, lv, _lib.ptr(out), _lib.ptr(work), wbytes,
+              _lib.stream_ptr(dev))
+    return out
+
+
+def _pillow_rgb(data):
+    from PIL import Image
+
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+
+def decode_batch(files, device, threads=None, unsupported="raise"):
+    """list of JPEG files' bytes (one frame size) -> uint8 CUDA [N,H,W,3].  Entropy decoding runs in ``threads`` threads
+    (default min(16, N)); files of one geometry share one upload and one ``reconstruct`` call.
+    unsupported="raise": a stream the host stage does not support raises NotImplementedError; "pillow": exactly those files
+    are decoded by Pillow on the host and their pixels uploaded."""
+    if unsupported not in ("raise", "pillow"):
+        raise ValueError("unsupported must be 'raise' or 'pillow'")
+    files = [_as_bytes(f) for f in files]
+    if not files:
+        raise ValueError("decode_batch needs at least one file")
+
+    def one(data):
+        try:
+            return entropy_decode(data)
+        except NotImplementedError:
+            if unsupported == "raise":
+                raise
+            return _pillow_rgb(data)  # [H, W, 3]: told apart from a packed frame by its rank
+
+    threads = min(16, len(files)) if threads is None else max(1, int(threads))
+    _lib.load()  # (once, before the pool's threads could race to be the first)
+    if threads == 1:
+        staged = [one(f) for f in files]
+    else:
+        with ThreadPoolExecutor(threads) as pool:
+            staged = list(pool.map(one, files))
+    dev = torch.device(device)
+    first = staged[0]
+    if all(s.ndim == 1 and s.size == first.size and np.array_equal(s[:24], first[:24]) for s in staged):
+        return reconstruct(np.stack(staged), dev)  # the usual case: one geometry
+    groups, frames = {}, [None] * len(files)
+    for i, s in enumerate(staged):
+        if s.ndim == 3:
+            frames[i] = torch.from_numpy(np.ascontiguousarray(s)).to(dev, non_blocking=True)
+        else:
+            groups.setdefault(s[:24].tobytes() + s.size.to_bytes(8, "little"), []).append(i)
+    for idxs in groups.values():
+        decoded = reconstruct(np.stack([staged[i] for i in idxs]), dev)
+        for k, i in enumerate(idxs):
+            frames[i] = decoded[k]
+    if len({tuple(f.shape) for f in frames}) != 1:
+        raise ValueError("decode_batch: the files have different frame sizes")
+    return frames[0][None] if len(frames) == 1 else torch.stack(frames)

@@ -11,8 +11,11 @@ from handobjectconsist_amd.utils import synth
 class SynthPoseDataset:
     has_dist2strong = False
 
-    def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",)):
-        """2 * num_pairs frames: frame 2k and 2k + 1 are the two time steps of scene k."""
+    def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",), jpeg_quality=None, jpeg_subsampling=2):
+        """2 * num_pairs frames: frame 2k and 2k + 1 are the two time steps of scene k.
+        jpeg_quality (None: frames are arrays, as ever): the frames exist as JPEG files' bytes, encoded by Pillow at this
+        quality and ``jpeg_subsampling`` (0 / 1 / 2: 4:4:4 / 4:2:2 / 4:2:0) -- ``get_image_bytes(idx)`` returns them (the
+        accessor ``HandObjSet(decode="device")`` needs) and ``get_image(idx)`` Pillow's decode of those same bytes."""
         self.frame_size = tuple(frame_size)  # (W, H)
         W, H = self.frame_size
         scene = synth.random_scene(num_pairs, seed=seed, image_size=256)
@@ -29,6 +32,17 @@ class SynthPoseDataset:
         self.obj_faces = scene["obj_faces"]
         self.frames = rng.integers(0, 256, (2 * num_pairs, H, W, 3), dtype=np.uint8)
         self.sides = [sides[i % len(sides)] for i in range(2 * num_pairs)]
+        self.jpeg = None
+        if jpeg_quality is not None:
+            import io
+
+            from PIL import Image
+
+            self.jpeg = []
+            for frame in self.frames:
+                buf = io.BytesIO()
+                Image.fromarray(frame).save(buf, "JPEG", quality=int(jpeg_quality), subsampling=int(jpeg_subsampling))
+                self.jpeg.append(buf.getvalue())
         obj_all = np.concatenate(self.obj)
         self.can_trans = obj_all.mean(0)
         self.can_scale = float(np.linalg.norm(obj_all - self.can_trans, axis=1).max())
@@ -37,7 +51,18 @@ class SynthPoseDataset:
         return len(self.frames)
 
     def get_image(self, idx):
+        if self.jpeg is not None:
+            import io
+
+            from PIL import Image
+
+            return np.asarray(Image.open(io.BytesIO(self.jpeg[idx])).convert("RGB"))
         return self.frames[idx]
+
+    def get_image_bytes(self, idx):
+        if self.jpeg is None:
+            raise RuntimeError("SynthPoseDataset(jpeg_quality=None) holds arrays, not files")
+        return self.jpeg[idx]
 
     def get_sides(self, idx):
         return self.sides[idx]

@@ -902,6 +902,52 @@ MR_API int mr_frames_color_augment(const uint8_t* frames_in, uint8_t* frames_out
                                    void* workspace, int64_t workspace_bytes, int num_frames, int src_height,
                                    int src_width, mr_stream_t stream);
 
+/* ---- JPEG frames: entropy decode on the host, reconstruction on the GPU ---------------------
+ * What Pillow's Image.open(...).convert("RGB") gives for a baseline JPEG file, byte for byte, in two stages.
+ * HOST stage (no device needed, re-entrant, no allocation): marker parser + Huffman decoder -> one PACKED FRAME per file.
+ * Supported: 8-bit SOF0 / SOF1 Huffman streams with one interleaved scan; 1 component or 3 components YCbCr (as libjpeg
+ * chooses the colour space) with luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma; 8- and 16-bit DQT; DRI / RST0..7; byte
+ * stuffing, fill bytes, APPn / COM; sides 1..10752.  MR_ERR_NOTIMPL, from the headers alone: progressive, arithmetic,
+ * lossless, 12-bit, 2 or 4 components, RGB-coded, other sampling factors, a scan over only some components.
+ * MR_ERR_BADARG: malformed or truncated data (no warn-and-continue recovery), and a coefficient whose product with its
+ * quantiser does not fit 16 bits (|c q| > 32767; no encoder of 8-bit samples writes one): the equality with Pillow is
+ * specified for streams encoded from 8-bit samples, whose intermediate values fit the device stage's 32-bit IDCT.  A
+ * missing EOI after complete entropy data is accepted.
+ *
+ * Packed frame: mr_jpeg_packed_bytes(width, height, components, luma_h, luma_v) bytes, a function of the geometry only
+ * (so the frames of a batch stack into one [N, bytes] array and travel in one copy):
+ *   bytes   0 ..  63  int32 header[16]: MR_JPEG_MAGIC, width, height, components, luma_h, luma_v, tq[3] (the quantisation
+ *                     table of each component), restart interval, packed bytes (low 32 bits), zeros
+ *   bytes  64 .. 575  four quantisation tables, uint16[64] each, natural (row-major) order; undefined tables are zeros
+ *   bytes 576 ..      coefficients, int16[64] per 8x8 block in natural (de-zigzagged) order, NOT dequantised: component
+ *                     after component (Y, Cb, Cr), each component's blocks row-major over its plane padded to whole MCUs:
+ *                     ceil(width / (8 luma_h)) * h blocks across, ceil(height / (8 luma_v)) * v down (h, v: the
+ *                     component's own factors).  16-byte aligned when the frame is.
+ * mr_jpeg_info: info[6] = width, height, components, luma_h, luma_v (1, 1 for grey), restart interval; the return code
+ * says whether mr_jpeg_entropy_decode supports the stream.  data, info, packed: HOST memory; packed 4-byte aligned and
+ * packed_bytes exactly the geometry's size.
+ *
+ * DEVICE stage, mr_jpeg_reconstruct: packed [num_frames] frames of ONE geometry in device memory (16-byte aligned, one
+ * after the other) -> frames_out uint8 [num_frames, height, width, 3] (4-byte aligned), the tensor mr_frames_color_augment
+ * and mr_frames_to_batch read.  Dequantisation + libjpeg's islow IDCT + range limit into per-component planes in the
+ * workspace, then libjpeg-turbo's fancy chroma upsampling + YCbCr -> RGB; grey frames replicate Y.  Two launches whatever
+ * num_frames; integer arithmetic only.  The device stage trusts the frames' headers for nothing but the table selectors
+ * (masked to 0..3): the caller checks magic and geometry on the host before the upload.
+ * workspace: mr_jpeg_reconstruct_workspace_bytes(...) bytes, 16-byte aligned.  MR_ERR_BADARG: a geometry the host stage
+ * does not produce, NULL or misaligned pointers, a workspace that is too small; num_frames == 0: MR_OK, nothing is touched;
+ * more than 2^32 - 4 pixels (12.9 GB of frames) or 2^32 - 512 blocks in one call: MR_ERR_NOTIMPL (a thread's pixel and
+ * block numbers are 32-bit). */
+#define MR_JPEG_MAGIC 0x314A524D
+#define MR_JPEG_HEADER_BYTES 576
+MR_API int mr_jpeg_info(const unsigned char* data, int64_t len, int* info);
+MR_API int64_t mr_jpeg_packed_bytes(int width, int height, int components, int luma_h, int luma_v);
+MR_API int mr_jpeg_entropy_decode(const unsigned char* data, int64_t len, unsigned char* packed, int64_t packed_bytes);
+MR_API int64_t mr_jpeg_reconstruct_workspace_bytes(int num_frames, int width, int height, int components, int luma_h,
+                                                   int luma_v);
+MR_API int mr_jpeg_reconstruct(const unsigned char* packed, int num_frames, int width, int height, int components,
+                               int luma_h, int luma_v, unsigned char* frames_out, void* workspace,
+                               int64_t workspace_bytes, mr_stream_t stream);
+
 /* ---- trainer side: BatchNorm with frozen statistics + residual add + ReLU -----------------
  * The reference trains with --freeze_batchnorm (trainmeshwarp.py:205-206, 237-240): every BatchNorm2d of the
  * ResNet-18 trunk runs in eval mode with trainable affine parameters, followed by ReLU, by "+ identity, ReLU"
