@@ -33,6 +33,8 @@ MASK_DTYPES = (torch.float32, torch.uint8)
 # MR_COLOR_OP_*: the ops of a colour plan (mr_frames_color_augment)
 COLOR_OP_NONE, COLOR_OP_BRIGHTNESS, COLOR_OP_SATURATION, COLOR_OP_HUE, COLOR_OP_CONTRAST = 0, 1, 2, 3, 4
 JPEG_MAGIC, JPEG_HEADER_BYTES = 0x314A524D, 576  # MR_JPEG_*: a packed frame of mr_jpeg_entropy_decode
+# MR_PNG_*: a packed frame of datasets/pngdecode.py; the rows of a band and the largest side of mr_png_unfilter
+PNG_MAGIC, PNG_HEADER_BYTES, PNG_BAND_ROWS, PNG_MAX_SIDE = 0x3150524D, 64, 64, 10752
 # (image, mask) pairs the fused pair kernels are instantiated for
 FUSED_BATCH_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.uint8), (torch.bfloat16, torch.float32))
 
@@ -118,6 +120,9 @@ SIGNATURES = {
     "mr_jpeg_entropy_decode": (_I, [_P, _L, _P, _L]),
     "mr_jpeg_reconstruct_workspace_bytes": (_L, [_I] * 6),
     "mr_jpeg_reconstruct": (_I, [_P] + [_I] * 6 + [_P, _P, _L, _P]),
+    "mr_png_packed_bytes": (_L, [_I] * 3),
+    "mr_png_unfilter_workspace_bytes": (_L, [_I] * 4),
+    "mr_png_unfilter": (_I, [_P] + [_I] * 4 + [_P, _P, _P]),
     "mr_bn_act_forward": (_I, [_P] * 6 + [_F, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mr_bn_act_backward_workspace_bytes": (_L, [_I, _I]),
     "mr_bn_act_backward": (_I, [_P] * 8 + [_F, _I, _I, _I] + [_P] * 5 + [_L, _I, _I, _I, _P]),

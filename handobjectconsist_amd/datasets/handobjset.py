@@ -19,7 +19,9 @@ by default (blur pinned by a fixture, jitter restated), ``color_fn=None`` switch
 draws, applied by ``assemble_batch`` on the GPU (``frames.color_augment``, byte for byte Pillow's result): the sample then
 carries the untouched frame and its ``color_plan``.  ``decode="device"`` (needs ``pose_dataset.get_image_bytes``): the sample
 carries the JPEG file's entropy-decoded PACKED FRAME as ``frame_jpeg`` instead of ``frame``; ``assemble_batch`` uploads the
-stacked packed frames once and reconstructs the pixels on the GPU (``jpegdecode.reconstruct``, byte for byte Pillow's decode)."""
+stacked packed frames once and reconstructs the pixels on the GPU (``jpegdecode.reconstruct``, byte for byte Pillow's decode).
+A file that starts with the PNG signature travels as ``frame_png`` instead: its inflated, still filtered scanlines
+(``pngdecode.inflate``), which ``assemble_batch`` unfilters on the GPU (``pngdecode.unfilter``)."""
 import random
 import traceback
 
@@ -53,7 +55,7 @@ class HandObjSet(Dataset):
             if color_fn not in ("device", None):
                 raise ValueError("decode=\"device\" leaves no pixels on the host: color_fn must be \"device\" or None")
             if not hasattr(pose_dataset, "get_image_bytes"):
-                raise ValueError("decode=\"device\" needs a pose_dataset with get_image_bytes(idx) (the JPEG file's bytes)")
+                raise ValueError("decode=\"device\" needs a pose_dataset with get_image_bytes(idx) (the JPEG or PNG file's bytes)")
         self.decode = decode
         self.pose_dataset = pose_dataset
         self.center_idx, self.inp_res = center_idx, tuple(inp_res)
@@ -100,10 +102,14 @@ class HandObjSet(Dataset):
         if want_img:
             center, scale = ds.get_center_scale(idx)
             if self.decode == "device":
-                from handobjectconsist_amd.datasets import jpegdecode
+                from handobjectconsist_amd.datasets import jpegdecode, pngdecode
 
-                frame, packed = None, jpegdecode.entropy_decode(ds.get_image_bytes(idx))
-                width = jpegdecode.packed_info(packed)["width"]  # (the file's own, as jpeg_info reads it: no second parse)
+                data = ds.get_image_bytes(idx)
+                packed_key, codec = "frame_jpeg", jpegdecode
+                if bytes(data[:8]) == pngdecode.SIGNATURE:
+                    packed_key, codec = "frame_png", pngdecode
+                frame, packed = None, (codec.inflate if codec is pngdecode else codec.entropy_decode)(data)
+                width = codec.packed_info(packed)["width"]  # (the file's own, as its headers give it: no second parse)
             else:
                 frame = np.asarray(ds.get_image(idx))
                 width = frame.shape[1]
@@ -142,7 +148,7 @@ class HandObjSet(Dataset):
                     frame = view[:, ::-1] if flip else view
             sample["color_augm"] = color_augm if self.train else None
             if frame is None:
-                sample["frame_jpeg"] = packed
+                sample[packed_key] = packed
             else:
                 sample["frame"] = np.ascontiguousarray(frame)
             sample["flip"] = bool(flip)
@@ -230,28 +236,35 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
     All frames of the step go through ONE ``frames_to_batch`` launch -- after ``frames.color_augment`` where the dicts carry
     ``color_plan`` (``HandObjSet(color_fn="device")``).  Dicts with ``frame_jpeg`` instead of ``frame``
     (``HandObjSet(decode="device")``, all of a batch or none): the packed frames are stacked, uploaded in one copy and
-    reconstructed by ``jpegdecode.reconstruct`` first.  ``image_dtype`` / ``mask_dtype``: the batch's element
+    reconstructed by ``jpegdecode.reconstruct`` first; dicts with ``frame_png`` likewise, through ``pngdecode.unfilter``.  A batch
+    holds one of the three.  ``image_dtype`` / ``mask_dtype``: the batch's element
     types as ``frames_to_batch`` takes them (``torch.bfloat16`` / ``torch.uint8``: the compact batch)."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
+    frame_keys = ("frame", "frame_jpeg", "frame_png")
     out = []
     for d in dicts:
         out.append({k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in d.items()
-                    if k not in ("frame", "frame_jpeg", "affinetrans", "flip", "color_plan")})
-    with_frames = [i for i, d in enumerate(dicts) if "frame" in d or "frame_jpeg" in d]
-    packed = [i for i in with_frames if "frame_jpeg" in dicts[i]]
-    if packed and (len(packed) != len(with_frames) or any("frame" in dicts[i] for i in packed)):
-        raise ValueError(f"frame_jpeg in {len(packed)} of {len(with_frames)} frame dicts: a batch mixes samples of "
-                         "HandObjSet(decode=\"device\") with decoded frames")
-    if with_frames:
+                    if k not in frame_keys + ("affinetrans", "flip", "color_plan")})
+    with_frames = [i for i, d in enumerate(dicts) if any(k in d for k in frame_keys)]
+    key = "frame"
+    for packed_key in ("frame_jpeg", "frame_png"):
+        packed = [i for i in with_frames if packed_key in dicts[i]]
+        if packed and (len(packed) != len(with_frames) or any(k in dicts[i] for i in packed for k in frame_keys if k != packed_key)):
+            raise ValueError(f"{packed_key} in {len(packed)} of {len(with_frames)} frame dicts: a batch mixes samples of "
+                             "HandObjSet(decode=\"device\") with decoded frames or with frames of another file format")
         if packed:
-            from handobjectconsist_amd.datasets import jpegdecode
+            key = packed_key
+    if with_frames:
+        if key != "frame":
+            from handobjectconsist_amd.datasets import jpegdecode, pngdecode
 
-            rows = [torch.as_tensor(dicts[i]["frame_jpeg"]) for i in with_frames]
+            rows = [torch.as_tensor(dicts[i][key]) for i in with_frames]
             if any(r.dim() != 2 for r in rows):
-                raise ValueError("frame_jpeg must be collated: [frames, bytes] per dict, not one sample's flat packed frame")
+                raise ValueError(f"{key} must be collated: [frames, bytes] per dict, not one sample's flat packed frame")
             if any(r.shape[1] != rows[0].shape[1] for r in rows):
-                raise ValueError("frame_jpeg: the batch's packed frames differ in size (one frame geometry per batch)")
-            frames = jpegdecode.reconstruct(torch.cat(rows, 0), device)
+                raise ValueError(f"{key}: the batch's packed frames differ in size (one frame geometry per batch)")
+            decode = jpegdecode.reconstruct if key == "frame_jpeg" else pngdecode.unfilter
+            frames = decode(torch.cat(rows, 0), device)
         else:
             frames = torch.cat([torch.as_tensor(dicts[i]["frame"]) for i in with_frames], 0).to(device, non_blocking=True)
         affines = np.concatenate([np.asarray(dicts[i]["affinetrans"]) for i in with_frames], 0)
@@ -268,7 +281,7 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
                                                  mask_dtype=mask_dtype)
         lo = 0
         for i in with_frames:
-            n = len(dicts[i]["frame_jpeg" if packed else "frame"])
+            n = len(dicts[i][key])
             out[i]["image"], out[i]["jittermask"] = image[lo:lo + n], mask[lo:lo + n]
             lo += n
     return out if isinstance(batch, (list, tuple)) else out[0]

@@ -11,11 +11,16 @@ from handobjectconsist_amd.utils import synth
 class SynthPoseDataset:
     has_dist2strong = False
 
-    def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",), jpeg_quality=None, jpeg_subsampling=2):
+    def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",), jpeg_quality=None, jpeg_subsampling=2,
+                 png_compress_level=None):
         """2 * num_pairs frames: frame 2k and 2k + 1 are the two time steps of scene k.
         jpeg_quality (None: frames are arrays, as ever): the frames exist as JPEG files' bytes, encoded by Pillow at this
         quality and ``jpeg_subsampling`` (0 / 1 / 2: 4:4:4 / 4:2:2 / 4:2:0) -- ``get_image_bytes(idx)`` returns them (the
-        accessor ``HandObjSet(decode="device")`` needs) and ``get_image(idx)`` Pillow's decode of those same bytes."""
+        accessor ``HandObjSet(decode="device")`` needs) and ``get_image(idx)`` Pillow's decode of those same bytes.
+        png_compress_level (None, or 0..9; not together with jpeg_quality): the same for PNG files, written by Pillow at this
+        zlib level -- lossless, so ``get_image(idx)`` equals the array."""
+        if jpeg_quality is not None and png_compress_level is not None:
+            raise ValueError("jpeg_quality and png_compress_level: the frames are files of one format")
         self.frame_size = tuple(frame_size)  # (W, H)
         W, H = self.frame_size
         scene = synth.random_scene(num_pairs, seed=seed, image_size=256)
@@ -43,6 +48,16 @@ class SynthPoseDataset:
                 buf = io.BytesIO()
                 Image.fromarray(frame).save(buf, "JPEG", quality=int(jpeg_quality), subsampling=int(jpeg_subsampling))
                 self.jpeg.append(buf.getvalue())
+        if png_compress_level is not None:
+            import io
+
+            from PIL import Image
+
+            self.jpeg = []  # (the files' bytes, whatever their format)
+            for frame in self.frames:
+                buf = io.BytesIO()
+                Image.fromarray(frame).save(buf, "PNG", compress_level=int(png_compress_level))
+                self.jpeg.append(buf.getvalue())
         obj_all = np.concatenate(self.obj)
         self.can_trans = obj_all.mean(0)
         self.can_scale = float(np.linalg.norm(obj_all - self.can_trans, axis=1).max())
@@ -61,7 +76,7 @@ class SynthPoseDataset:
 
     def get_image_bytes(self, idx):
         if self.jpeg is None:
-            raise RuntimeError("SynthPoseDataset(jpeg_quality=None) holds arrays, not files")
+            raise RuntimeError("SynthPoseDataset(jpeg_quality=None, png_compress_level=None) holds arrays, not files")
         return self.jpeg[idx]
 
     def get_sides(self, idx):

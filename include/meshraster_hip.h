@@ -948,6 +948,39 @@ MR_API int mr_jpeg_reconstruct(const unsigned char* packed, int num_frames, int 
                                int luma_h, int luma_v, unsigned char* frames_out, void* workspace,
                                int64_t workspace_bytes, mr_stream_t stream);
 
+/* ---- PNG frames: inflate on the host, unfilter on the GPU -----------------------------------
+ * What Pillow's Image.open(...).convert("RGB") gives for an 8-bit, non-interlaced PNG file of colour type 0 (grey),
+ * 2 (RGB), 4 (grey + alpha) or 6 (RGBA), byte for byte.  The HOST stage is Python (datasets/pngdecode.py: chunk parser +
+ * zlib); it produces one PACKED FRAME per file, mr_png_packed_bytes(width, height, channels) bytes, a function of the
+ * geometry only:
+ *   bytes  0 .. 63  int32 header[16]: MR_PNG_MAGIC, width, height, channels (bytes per pixel: 1, 3, 2, 4 for the colour
+ *                   types above), colour type, zeros
+ *   bytes 64 ..     the height filtered scanlines exactly as inflated, 1 + width * channels bytes each, the filter byte
+ *                   (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) first; then zeros up to a multiple of 16 bytes
+ * mr_png_packed_bytes: -1 for channels outside 1..4 and sides outside 1..MR_PNG_MAX_SIDE.
+ *
+ * DEVICE stage, mr_png_unfilter: packed [num_frames] frames of ONE geometry in device memory (16-byte aligned, one after
+ * the other) -> frames_out uint8 [num_frames, height, width, 3] (4-byte aligned), the tensor mr_frames_color_augment and
+ * mr_frames_to_batch read.  Recon(x) = Filt(x) + pred(a, b, c) mod 256 with a the byte `channels` to the left, b the byte
+ * above, c the byte above-left, 0 outside the image; pred = 0, a, b, floor((a + b) / 2), Paeth(a, b, c) (nearest of a, b,
+ * c to a + b - c, ties in that order).  Alpha is dropped, grey replicated.  One launch whatever num_frames: one wave per
+ * frame walks it in bands of MR_PNG_BAND_ROWS rows, the rows of a band as a skewed wavefront (csrc/frame_png.hip); integer
+ * arithmetic only.  The device stage reads nothing of the frames' headers: the caller checks magic, geometry and all
+ * filter bytes on the host before the upload.  A filter byte above 4 is treated as filter 0.
+ * workspace: mr_png_unfilter_workspace_bytes(num_frames, width, height, channels) bytes = 0 (NULL is accepted; -1 for what
+ * mr_png_packed_bytes refuses or num_frames < 0).  num_frames == 0: MR_OK, nothing is touched.  MR_ERR_BADARG: num_frames
+ * < 0, channels outside 1..4, a side below 1, NULL or misaligned pointers.  MR_ERR_NOTIMPL: a side above MR_PNG_MAX_SIDE
+ * = 10752 pixels (a reconstructed row, up to 4 bytes per pixel, is held in the workgroup's LDS, and a frame's byte
+ * offsets are 32-bit). */
+#define MR_PNG_MAGIC 0x3150524D
+#define MR_PNG_HEADER_BYTES 64
+#define MR_PNG_BAND_ROWS 64
+#define MR_PNG_MAX_SIDE 10752
+MR_API int64_t mr_png_packed_bytes(int width, int height, int channels);
+MR_API int64_t mr_png_unfilter_workspace_bytes(int num_frames, int width, int height, int channels);
+MR_API int mr_png_unfilter(const unsigned char* packed, int num_frames, int width, int height, int channels,
+                           unsigned char* frames_out, void* workspace, mr_stream_t stream);
+
 /* ---- trainer side: BatchNorm with frozen statistics + residual add + ReLU -----------------
  * The reference trains with --freeze_batchnorm (trainmeshwarp.py:205-206, 237-240): every BatchNorm2d of the
  * ResNet-18 trunk runs in eval mode with trainable affine parameters, followed by ReLU, by "+ identity, ReLU"
