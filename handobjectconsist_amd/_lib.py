@@ -35,6 +35,7 @@ COLOR_OP_NONE, COLOR_OP_BRIGHTNESS, COLOR_OP_SATURATION, COLOR_OP_HUE, COLOR_OP_
 JPEG_MAGIC, JPEG_HEADER_BYTES = 0x314A524D, 576  # MR_JPEG_*: a packed frame of mr_jpeg_entropy_decode
 # MR_PNG_*: a packed frame of datasets/pngdecode.py; the rows of a band and the largest side of mr_png_unfilter
 PNG_MAGIC, PNG_HEADER_BYTES, PNG_BAND_ROWS, PNG_MAX_SIDE = 0x3150524D, 64, 64, 10752
+MANO_POSE_PCA, MANO_POSE_AXISANG = 0, 1  # MR_MANO_POSE_*: the pose form of mr_mano_forward_full / mr_mano_backward_full
 # (image, mask) pairs the fused pair kernels are instantiated for
 FUSED_BATCH_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.uint8), (torch.bfloat16, torch.float32))
 
@@ -71,6 +72,10 @@ SIGNATURES = {
     "mr_mano_workspace_floats": (_L, [_I]),
     "mr_mano_forward": (_I, [_P] * 12 + [_I, _I] + [_P] * 3 + [_I, _P]),
     "mr_mano_backward": (_I, [_P] * 10 + [_I, _I] + [_P] * 5 + [_I, _P]),
+    # the general MANO call (either pose form, any centre, th_trans, the ground-truth epilogue): additions to ABI 9
+    "mr_mano_full_workspace_floats": (_L, [_I]),
+    "mr_mano_forward_full": (_I, [_P] * 13 + [_I, _I, _I, _F] + [_P] * 6 + [_I, _P]),
+    "mr_mano_backward_full": (_I, [_P] * 10 + [_I, _I, _I] + [_P] * 6 + [_I, _P]),
     "mr_meshreg_post_forward": (_I, [_P] * 6 + [_F] * 5 + [_P] * 5 + [_I, _I, _I, _I, _P]),
     "mr_meshreg_post_backward": (_I, [_P] * 6 + [_F] * 5 + [_P] * 10 + [_I, _I, _I, _I, _P]),
     "mr_warp_forward": (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I, _P]),

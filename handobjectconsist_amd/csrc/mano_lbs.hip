@@ -16,6 +16,9 @@
 //   mano_blend_bwd_kernel d coeff = d v_posed[B,2334] x blend^T on the matrix cores, split-K partials
 //   mano_pre_bwd_kernel   one wave per sample: sums the partials, chain / Rodrigues / PCA adjoints
 // This is the only GEMM-shaped work on the whole path (M = 2334, K = 145, N = batch).
+// The pre / skin kernels and their adjoints are templates: <PCA pose, network call> is mr_mano_forward /
+// mr_mano_backward as ever; the FULL instantiations (mr_mano_forward_full / mr_mano_backward_full) add the 48-value
+// axis-angle pose, a finger-tip centre, manopth's translation rule and the ground-truth epilogue.
 #include "mr_common.hpp"
 
 namespace mr {
@@ -37,8 +40,20 @@ struct ManoConst {
     const int* parents;    // [16], parents[0] = -1
     const int* tips;       // [5] vertex ids
     const int* reorder;    // [21] output joint k = cat(joints, tips)[reorder[k]]
-    int ncomps, center;    // center: index into cat(joints, tips) BEFORE the reorder, < 16 (a joint), or -1
+    int ncomps, center;    // center: index into cat(joints, tips) BEFORE the reorder, or -1; >= 16 (a tip): FULL kernels only
 };
+
+// what the FULL kernels take on top (mr_mano_forward_full / mr_mano_backward_full)
+struct ManoFull {
+    const float* trans;        // [B,3] th_trans, or NULL
+    int ntrans;                // 3 B (0 without a translation): the bound of the all-zero scan
+    float* tflag;              // [B] workspace: 1.0f where the translation is in force (every sample holds the same value)
+    float out_scale;           // the rigid epilogue, applied iff post_rot != NULL: x = v * out_scale; x = x + post_trans[b];
+    const float* post_trans;   //   x = post_rot[b] x; x = x - post_trans2[b]   (either translation may be NULL)
+    const float* post_rot;     // [B,9]
+    const float* post_trans2;  // [B,3]
+};
+constexpr int MN_POSE_PCA = 0, MN_POSE_AXISANG = 1;  // MR_MANO_POSE_*
 
 // ---------------------------------------------------------------------------------------------------
 // small helpers (per-lane serial 3x3 / 3x4 algebra; everything here is a few hundred flops per sample)
@@ -61,7 +76,8 @@ __device__ __forceinline__ void rigid_mul(const float* A, const float* B, float*
 // ---------------------------------------------------------------------------------------------------
 // one wave per sample.  Outputs: coeff[B,MN_KP], G[B,16,12] (chain), G2[B,16,12] (rest-pose corrected),
 // rots[B,16,9], joints[B,16,3]; the 16 joint rows of jtr_out (centred, x1000, reordered).
-__global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, const float* __restrict__ pose,
+template <int FORM, bool FULL>
+__global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, ManoFull mf, const float* __restrict__ pose,
                                                       const float* __restrict__ betas, float* __restrict__ coeff,
                                                       float* __restrict__ G, float* __restrict__ G2,
                                                       float* __restrict__ rots, float* __restrict__ joints,
@@ -69,12 +85,24 @@ __global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, const float*
                                                       int B) {
     __shared__ float s_pose[48], s_R[MN_J * 9], s_J[48], s_G[MN_J * 12];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int np = 3 + mc.ncomps;
+    const int np = FORM == MN_POSE_AXISANG ? 48 : 3 + mc.ncomps;
     if (lane < 3) s_pose[lane] = pose[b * np + lane];
     if (lane < 45) {
-        float acc = 0.0f;
-        for (int c = 0; c < mc.ncomps; c++) acc = fmaf(pose[b * np + 3 + c], mc.comps[c * 45 + lane], acc);
-        s_pose[3 + lane] = mc.mean[lane] + acc;
+        if constexpr (FORM == MN_POSE_AXISANG) {
+            s_pose[3 + lane] = mc.mean[lane] + pose[b * np + 3 + lane];
+        } else {
+            float acc = 0.0f;
+            for (int c = 0; c < mc.ncomps; c++) acc = fmaf(pose[b * np + 3 + c], mc.comps[c * 45 + lane], acc);
+            s_pose[3 + lane] = mc.mean[lane] + acc;
+        }
+    }
+    if constexpr (FULL) {
+        // manopth's rule: a translation whose norm over the WHOLE tensor is zero counts as absent.  Every sample's wave
+        // scans all 3 B values and ORs their magnitude bits: no flag shared between samples, no atomic, no second launch
+        unsigned bits = 0u;
+        for (int i = lane; i < mf.ntrans; i += 64) bits |= __float_as_uint(mf.trans[i]) & 0x7fffffffu;
+        const bool in_force = __ballot(bits != 0u) != 0ull;
+        if (lane == 0) mf.tflag[b] = in_force ? 1.0f : 0.0f;
     }
     if (lane < 48) {
         float acc = 0.0f;
@@ -128,12 +156,14 @@ __global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, const float*
                          fmaf(s_G[j * 12 + 4 * r + 1], s_J[3 * j + 1], s_G[j * 12 + 4 * r] * s_J[3 * j]));
         G2[b * MN_J * 12 + k] = v;
     }
-    // joint rows of the output (tips come from mano_skin_kernel)
-    if (lane < MN_JT * 3) {
-        const int k = lane / 3, r = lane % 3, src = mc.reorder[k];
-        if (src < MN_J) {
-            const float ctr = mc.center >= 0 ? s_G[mc.center * 12 + 4 * r + 3] : 0.0f;
-            jtr_out[(b * MN_JT + k) * 3 + r] = (s_G[src * 12 + 4 * r + 3] - ctr) * 1000.0f;
+    // joint rows of the output (tips come from mano_skin_kernel; FULL: so do these rows, the centre may be a tip)
+    if constexpr (!FULL) {
+        if (lane < MN_JT * 3) {
+            const int k = lane / 3, r = lane % 3, src = mc.reorder[k];
+            if (src < MN_J) {
+                const float ctr = mc.center >= 0 ? s_G[mc.center * 12 + 4 * r + 3] : 0.0f;
+                jtr_out[(b * MN_JT + k) * 3 + r] = (s_G[src * 12 + 4 * r + 3] - ctr) * 1000.0f;
+            }
         }
     }
 }
@@ -165,34 +195,100 @@ __global__ void __launch_bounds__(64) mano_blend_kernel(const float* __restrict_
     }
 }
 
-// one thread per (sample, vertex)
-__global__ void __launch_bounds__(256) mano_skin_kernel(ManoConst mc, const float* __restrict__ v_posed,
-                                                        const float* __restrict__ G, const float* __restrict__ G2,
-                                                        float* __restrict__ verts_out, float* __restrict__ jtr_out,
-                                                        int B) {
-    __shared__ float s_G2[MN_J * 12];
-    const int b = blockIdx.y, v = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int k = threadIdx.x; k < MN_J * 12; k += blockDim.x) s_G2[k] = G2[b * MN_J * 12 + k];
-    __syncthreads();
-    if (v >= MN_V) return;
+// blended 3x4 transform of vertex v applied to its posed position
+__device__ __forceinline__ void skin_vertex(const float* __restrict__ weights, const float* s_G2,
+                                            const float* __restrict__ v_posed, int b, int v, float* o) {
     float T[12];
 #pragma unroll
     for (int e = 0; e < 12; e++) T[e] = 0.0f;
     for (int j = 0; j < MN_J; j++) {
-        const float w = mc.weights[v * MN_J + j];
+        const float w = weights[v * MN_J + j];
 #pragma unroll
         for (int e = 0; e < 12; e++) T[e] = fmaf(w, s_G2[j * 12 + e], T[e]);
     }
     const float* vp = v_posed + ((int64_t)b * MN_V + v) * 3;
     const float p[3] = {vp[0], vp[1], vp[2]};
-    float o[3];
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
-        o[r] = fmaf(T[4 * r + 2], p[2], fmaf(T[4 * r + 1], p[1], T[4 * r] * p[0])) + T[4 * r + 3];
-        const float ctr = mc.center >= 0 ? G[(b * MN_J + mc.center) * 12 + 4 * r + 3] : 0.0f;
-        o[r] = (o[r] - ctr) * 1000.0f;
-        verts_out[((int64_t)b * MN_V + v) * 3 + r] = o[r];
+    for (int r = 0; r < 3; r++) o[r] = fmaf(T[4 * r + 2], p[2], fmaf(T[4 * r + 1], p[1], T[4 * r] * p[0])) + T[4 * r + 3];
+}
+
+// FULL: translation or centre, the millimetre scale, then the rigid epilogue -- separate multiplies and adds in the order
+// of the host code it stands for (scale, translate, rotate, subtract)
+__device__ __forceinline__ void full_finish(const ManoFull& mf, int b, bool in_force, bool centred, const float* off,
+                                            float* o) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) o[r] = (in_force ? o[r] + off[r] : (centred ? o[r] - off[r] : o[r])) * 1000.0f;
+    if (mf.post_rot) {
+        float x[3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            x[r] = o[r] * mf.out_scale;
+            if (mf.post_trans) x[r] = x[r] + mf.post_trans[b * 3 + r];
+        }
+        const float* R = mf.post_rot + b * 9;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            o[r] = R[3 * r] * x[0] + R[3 * r + 1] * x[1] + R[3 * r + 2] * x[2];
+            if (mf.post_trans2) o[r] = o[r] - mf.post_trans2[b * 3 + r];
+        }
     }
+}
+
+// one thread per (sample, vertex)
+template <bool FULL>
+__global__ void __launch_bounds__(256) mano_skin_kernel(ManoConst mc, ManoFull mf, const float* __restrict__ v_posed,
+                                                        const float* __restrict__ G, const float* __restrict__ G2,
+                                                        float* __restrict__ verts_out, float* __restrict__ jtr_out,
+                                                        int B) {
+    __shared__ float s_G2[MN_J * 12];
+    __shared__ float s_off[3];
+    const int b = blockIdx.y, v = blockIdx.x * blockDim.x + threadIdx.x;
+    for (int k = threadIdx.x; k < MN_J * 12; k += blockDim.x) s_G2[k] = G2[b * MN_J * 12 + k];
+    __syncthreads();
+    bool in_force = false;
+    if constexpr (FULL) {
+        in_force = mf.tflag[b] != 0.0f;
+        if (threadIdx.x == 0) {  // what every output of the sample is shifted by: the translation, or the centre
+            float c[3] = {0.0f, 0.0f, 0.0f};
+            if (in_force) {
+#pragma unroll
+                for (int r = 0; r < 3; r++) c[r] = mf.trans[b * 3 + r];
+            } else if (mc.center >= MN_J) {  // a finger tip is a skinned vertex: recomputed here, the same arithmetic
+                skin_vertex(mc.weights, s_G2, v_posed, b, mc.tips[mc.center - MN_J], c);
+            } else if (mc.center >= 0) {
+#pragma unroll
+                for (int r = 0; r < 3; r++) c[r] = G[(b * MN_J + mc.center) * 12 + 4 * r + 3];
+            }
+#pragma unroll
+            for (int r = 0; r < 3; r++) s_off[r] = c[r];
+        }
+        __syncthreads();
+        if (blockIdx.x == 0 && threadIdx.x < MN_JT) {  // the joint rows (mano_pre_kernel writes them for the network call)
+            const int k = threadIdx.x, src = mc.reorder[k];
+            if (src < MN_J) {
+                float o[3];
+#pragma unroll
+                for (int r = 0; r < 3; r++) o[r] = G[(b * MN_J + src) * 12 + 4 * r + 3];
+                full_finish(mf, b, in_force, mc.center >= 0, s_off, o);
+#pragma unroll
+                for (int r = 0; r < 3; r++) jtr_out[(b * MN_JT + k) * 3 + r] = o[r];
+            }
+        }
+    }
+    if (v >= MN_V) return;
+    float o[3];
+    skin_vertex(mc.weights, s_G2, v_posed, b, v, o);
+    if constexpr (FULL) {
+        full_finish(mf, b, in_force, mc.center >= 0, s_off, o);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const float ctr = mc.center >= 0 ? G[(b * MN_J + mc.center) * 12 + 4 * r + 3] : 0.0f;
+            o[r] = (o[r] - ctr) * 1000.0f;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 3; r++) verts_out[((int64_t)b * MN_V + v) * 3 + r] = o[r];
 #pragma unroll
     for (int tpi = 0; tpi < MN_TIPS; tpi++)
         if (mc.tips[tpi] == v) {
@@ -211,7 +307,8 @@ __global__ void __launch_bounds__(256) mano_skin_kernel(ManoConst mc, const floa
 constexpr int MN_CHUNKS = (MN_V + 255) / 256;
 constexpr int MN_PART = MN_J * 12 + 3;
 
-__global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, const float* __restrict__ v_posed,
+template <bool FULL>
+__global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, ManoFull mf, const float* __restrict__ v_posed,
                                                             const float* __restrict__ G2,
                                                             const float* __restrict__ grad_verts,
                                                             const float* __restrict__ grad_jtr,
@@ -223,6 +320,36 @@ __global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, const 
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x, v = chunk * 256 + tid;
     for (int k = tid; k < MN_J * 12; k += 256) s_G2[k] = G2[b * MN_J * 12 + k];
     __syncthreads();
+    // FULL, a finger-tip centre in force: the centre IS vertex cv, so its adjoint -- minus the sum of every incoming
+    // gradient of the sample, 778 vertex rows + 21 joint rows -- joins that vertex's gradient.  Summed by the one chunk
+    // that holds cv, in a fixed order (strided partial sums, then a tree over LDS): deterministic
+    int cv = -1;
+    float gctr[3] = {0.0f, 0.0f, 0.0f};
+    if constexpr (FULL) {
+        if (mc.center >= MN_J && mf.tflag[b] == 0.0f) cv = mc.tips[mc.center - MN_J];
+        if (cv >= 0 && cv / 256 == chunk) {  // (uniform over the block)
+            float a[3] = {0.0f, 0.0f, 0.0f};
+            for (int i = tid; i < MN_V + MN_JT; i += 256) {
+                const float* src = i < MN_V ? (grad_verts ? grad_verts + ((int64_t)b * MN_V + i) * 3 : nullptr)
+                                            : (grad_jtr ? grad_jtr + (b * MN_JT + (i - MN_V)) * 3 : nullptr);
+                if (src)
+#pragma unroll
+                    for (int r = 0; r < 3; r++) a[r] += src[r] * 1000.0f;
+            }
+#pragma unroll
+            for (int r = 0; r < 3; r++) s_gt[tid][r] = a[r];
+            __syncthreads();
+            for (int h = 128; h > 0; h >>= 1) {
+                if (tid < h)
+#pragma unroll
+                    for (int r = 0; r < 3; r++) s_gt[tid][r] += s_gt[tid + h][r];
+                __syncthreads();
+            }
+#pragma unroll
+            for (int r = 0; r < 3; r++) gctr[r] = -s_gt[0][r];
+            __syncthreads();
+        }
+    }
     float g[3] = {0.0f, 0.0f, 0.0f};
     if (v < MN_V) {
         float T[12], w[MN_J];
@@ -243,6 +370,10 @@ __global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, const 
                         if (mc.reorder[k] == MN_J + tpi)
 #pragma unroll
                             for (int r = 0; r < 3; r++) g[r] += grad_jtr[(b * MN_JT + k) * 3 + r] * 1000.0f;
+        if constexpr (FULL)
+            if (v == cv)
+#pragma unroll
+                for (int r = 0; r < 3; r++) g[r] += gctr[r];
         const float* vp = v_posed + ((int64_t)b * MN_V + v) * 3;
         const float p[4] = {vp[0], vp[1], vp[2], 1.0f};
 #pragma unroll
@@ -301,7 +432,9 @@ __global__ void __launch_bounds__(64) mano_blend_bwd_kernel(const float* __restr
 }
 
 // one wave per sample
-__global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, const float* __restrict__ full_pose,
+template <int FORM, bool FULL>
+__global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull mf, float* __restrict__ grad_trans,
+                                                          const float* __restrict__ full_pose,
                                                           const float* __restrict__ rots,
                                                           const float* __restrict__ joints, const float* __restrict__ G,
                                                           const float* __restrict__ part,
@@ -310,9 +443,9 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, const fl
                                                           float* __restrict__ grad_pose, float* __restrict__ grad_betas,
                                                           int B, int Mpad) {
     __shared__ float s_gG2[MN_J * 12], s_gc[3], s_gcoef[MN_KP], s_gG[MN_J * 12], s_gR[MN_J * 9], s_gJ[48], s_gp[48];
-    __shared__ float s_G[MN_J * 12], s_R[MN_J * 9], s_J[48];
+    __shared__ float s_G[MN_J * 12], s_R[MN_J * 9], s_J[48], s_gt[MN_J][3];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int np = 3 + mc.ncomps;
+    const int np = FORM == MN_POSE_AXISANG ? 48 : 3 + mc.ncomps;
     for (int k = lane; k < MN_J * 12; k += 64) {
         float acc = 0.0f;
         for (int c = 0; c < MN_CHUNKS; c++) acc += part[((int64_t)b * MN_CHUNKS + c) * MN_PART + k];
@@ -334,7 +467,7 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, const fl
     __syncthreads();
     // joint rows of jtr: (G[src].t - centre) * 1000 ; centre gradient gathers everything that was centred
     if (lane == 0) {
-        float gt[MN_J][3];
+        float (*gt)[3] = s_gt;  // (indexed by the reorder table: in LDS, not in scratch)
         for (int j = 0; j < MN_J; j++) gt[j][0] = gt[j][1] = gt[j][2] = 0.0f;
         float gc[3] = {s_gc[0], s_gc[1], s_gc[2]};
         if (grad_jtr)
@@ -346,8 +479,19 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, const fl
                     // (tips: their share of the centre gradient is in part[] through the vertex rows)
                 }
             }
-        if (mc.center >= 0)
-            for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
+        if constexpr (FULL) {
+            // verts = (skinned + trans) * 1000, joints likewise: d trans = the sum of every incoming gradient x 1000 = -gc,
+            // and nothing was centred.  A tip centre's adjoint went into its vertex (mano_skin_bwd_kernel); part[]'s sum
+            // then holds that vertex's addend too and is not used
+            const bool in_force = mf.tflag[b] != 0.0f;
+            if (grad_trans)
+                for (int r = 0; r < 3; r++) grad_trans[b * 3 + r] = in_force ? -gc[r] : 0.0f;
+            if (mc.center >= 0 && mc.center < MN_J && !in_force)
+                for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
+        } else {
+            if (mc.center >= 0)
+                for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
+        }
         // G2 = [G.R | G.t - G.R J]  ->  dG.R = dG2.R - dG2.t (x) J ; dG.t = dG2.t ; dJ = - G.R^T dG2.t
         for (int j = 0; j < MN_J; j++) {
             for (int r = 0; r < 3; r++) {
@@ -404,7 +548,9 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, const fl
     }
     __syncthreads();
     if (lane < 3) grad_pose[b * np + lane] = s_gp[lane];
-    if (lane < mc.ncomps) {
+    if constexpr (FORM == MN_POSE_AXISANG) {
+        if (lane < 45) grad_pose[b * np + 3 + lane] = s_gp[3 + lane];
+    } else if (lane < mc.ncomps) {
         float acc = 0.0f;
         for (int l = 0; l < 45; l++) acc = fmaf(mc.comps[lane * 45 + l], s_gp[3 + l], acc);
         grad_pose[b * np + 3 + lane] = acc;
@@ -437,6 +583,7 @@ extern "C" int64_t mr_mano_workspace_floats(int batch_size) {
 
 struct ManoWork {
     float *coeff, *G, *G2, *rots, *joints, *full_pose, *v_posed, *grad_vp, *part, *partial;
+    float* tflag;  // [B], behind the regions of mr_mano_workspace_floats: mr_mano_full_workspace_floats only
     int Mpad;
 };
 static ManoWork mano_work(float* w, int B) {
@@ -451,7 +598,8 @@ static ManoWork mano_work(float* w, int B) {
     m.v_posed = w; w += (int64_t)B * MN_NV3;
     m.grad_vp = w; w += (int64_t)B * MN_NV3;
     m.part = w; w += (int64_t)B * MN_CHUNKS * MN_PART;
-    m.partial = w;
+    m.partial = w; w += (int64_t)MN_SPLITK * m.Mpad * 160;
+    m.tflag = w;
     return m;
 }
 
@@ -470,14 +618,15 @@ extern "C" int mr_mano_forward(const float* pose_coeffs, const float* betas, con
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
     const ManoWork m = mano_work(workspace, batch_size);
-    hipLaunchKernelGGL(mano_pre_kernel, dim3((unsigned)batch_size), dim3(64), 0, s, mc, pose_coeffs, betas, m.coeff, m.G,
-                       m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
+    hipLaunchKernelGGL((mano_pre_kernel<MN_POSE_PCA, false>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, ManoFull{},
+                       pose_coeffs, betas, m.coeff, m.G, m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
     MR_CHECK_LAUNCH();
     hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((batch_size + 31) / 32)), dim3(64), 0, s,
                        (const float*)m.coeff, blend, v_template, m.v_posed, batch_size);
     MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_skin_kernel, dim3((MN_V + 255) / 256, (unsigned)batch_size), dim3(256), 0, s, mc,
-                       (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out, batch_size);
+    hipLaunchKernelGGL(mano_skin_kernel<false>, dim3((MN_V + 255) / 256, (unsigned)batch_size), dim3(256), 0, s, mc,
+                       ManoFull{}, (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out,
+                       batch_size);
     MR_CHECK_LAUNCH();
     return MR_OK;
 }
@@ -497,15 +646,118 @@ extern "C" int mr_mano_backward(const float* comps, const float* hands_mean, con
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
     const ManoWork m = mano_work(workspace, batch_size);
-    hipLaunchKernelGGL(mano_skin_bwd_kernel, dim3(MN_CHUNKS, (unsigned)batch_size), dim3(256), 0, s, mc,
+    hipLaunchKernelGGL(mano_skin_bwd_kernel<false>, dim3(MN_CHUNKS, (unsigned)batch_size), dim3(256), 0, s, mc, ManoFull{},
                        (const float*)m.v_posed, (const float*)m.G2, grad_verts, grad_jtr, m.grad_vp, m.part, batch_size);
     MR_CHECK_LAUNCH();
     hipLaunchKernelGGL(mano_blend_bwd_kernel, dim3(5, (unsigned)(m.Mpad / 32), MN_SPLITK), dim3(64), 0, s,
                        (const float*)m.grad_vp, blend, m.partial, batch_size, m.Mpad);
     MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_pre_bwd_kernel, dim3((unsigned)batch_size), dim3(64), 0, s, mc, (const float*)m.full_pose,
-                       (const float*)m.rots, (const float*)m.joints, (const float*)m.G, (const float*)m.part,
-                       (const float*)m.partial, grad_jtr, grad_pose_coeffs, grad_betas, batch_size, m.Mpad);
+    hipLaunchKernelGGL((mano_pre_bwd_kernel<MN_POSE_PCA, false>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, ManoFull{},
+                       (float*)nullptr, (const float*)m.full_pose, (const float*)m.rots, (const float*)m.joints,
+                       (const float*)m.G, (const float*)m.part, (const float*)m.partial, grad_jtr, grad_pose_coeffs,
+                       grad_betas, batch_size, m.Mpad);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the general call: either pose form, any centre, th_trans, the ground-truth epilogue
+// ---------------------------------------------------------------------------------------------------
+extern "C" int64_t mr_mano_full_workspace_floats(int batch_size) {
+    if (batch_size < 0) return MR_ERR_BADARG;
+    return mr_mano_workspace_floats(batch_size) + batch_size;  // ... | tflag
+}
+
+static bool mano_misaligned(std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & 3u) return true;
+    return false;
+}
+
+// what both general entry points check before anything touches HIP
+static int mano_full_check(const float* comps, const float* hands_mean, const float* js, const float* jt, const float* blend,
+                           const float* v_template, const float* weights, const int32_t* parents, const int32_t* tips,
+                           const int32_t* reorder, int pose_form, int ncomps, int center, const float* workspace,
+                           int batch_size) {
+    if (pose_form != MN_POSE_PCA && pose_form != MN_POSE_AXISANG) return MR_ERR_BADARG;
+    if (ncomps < 1 || ncomps > 45 || center < -1 || center >= MN_JT || batch_size > 65535) return MR_ERR_BADARG;
+    if ((pose_form == MN_POSE_PCA && !comps) || !hands_mean || !js || !jt || !blend || !v_template || !weights || !parents ||
+        !tips || !reorder || !workspace)
+        return MR_ERR_BADARG;
+    if (mano_misaligned({comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, workspace}))
+        return MR_ERR_BADARG;
+    return MR_OK;
+}
+
+extern "C" int mr_mano_forward_full(const float* pose, const float* betas, const float* trans, const float* comps,
+                                    const float* hands_mean, const float* js, const float* jt, const float* blend,
+                                    const float* v_template, const float* weights, const int32_t* parents,
+                                    const int32_t* tips, const int32_t* reorder, int pose_form, int ncomps, int center,
+                                    float out_scale, const float* post_trans, const float* post_rot,
+                                    const float* post_trans2, float* workspace, float* verts_out, float* jtr_out,
+                                    int batch_size, mr_stream_t stream) {
+    if (batch_size < 0) return MR_ERR_BADARG;
+    if (batch_size == 0) return MR_OK;
+    const int rc = mano_full_check(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, pose_form,
+                                   ncomps, center, workspace, batch_size);
+    if (rc != MR_OK) return rc;
+    if (!pose || !betas || !verts_out || !jtr_out || (!post_rot && (post_trans || post_trans2))) return MR_ERR_BADARG;
+    if (mano_misaligned({pose, betas, trans, post_trans, post_rot, post_trans2, verts_out, jtr_out})) return MR_ERR_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
+                                    center);
+    const ManoWork m = mano_work(workspace, batch_size);
+    const ManoFull mf{trans, trans ? 3 * batch_size : 0, m.tflag, out_scale, post_trans, post_rot, post_trans2};
+    if (pose_form == MN_POSE_AXISANG)
+        hipLaunchKernelGGL((mano_pre_kernel<MN_POSE_AXISANG, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf, pose,
+                           betas, m.coeff, m.G, m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
+    else
+        hipLaunchKernelGGL((mano_pre_kernel<MN_POSE_PCA, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf, pose,
+                           betas, m.coeff, m.G, m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
+    MR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((batch_size + 31) / 32)), dim3(64), 0, s,
+                       (const float*)m.coeff, blend, v_template, m.v_posed, batch_size);
+    MR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mano_skin_kernel<true>, dim3((MN_V + 255) / 256, (unsigned)batch_size), dim3(256), 0, s, mc, mf,
+                       (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out, batch_size);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
+
+extern "C" int mr_mano_backward_full(const float* comps, const float* hands_mean, const float* js, const float* jt,
+                                     const float* blend, const float* v_template, const float* weights,
+                                     const int32_t* parents, const int32_t* tips, const int32_t* reorder, int pose_form,
+                                     int ncomps, int center, float* workspace, const float* grad_verts,
+                                     const float* grad_jtr, float* grad_pose, float* grad_betas, float* grad_trans,
+                                     int batch_size, mr_stream_t stream) {
+    if (batch_size < 0) return MR_ERR_BADARG;
+    if (batch_size == 0) return MR_OK;
+    const int rc = mano_full_check(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, pose_form,
+                                   ncomps, center, workspace, batch_size);
+    if (rc != MR_OK) return rc;
+    if (!grad_pose || !grad_betas) return MR_ERR_BADARG;
+    if (mano_misaligned({grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans})) return MR_ERR_BADARG;
+    hipStream_t s = (hipStream_t)stream;
+    const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
+                                    center);
+    const ManoWork m = mano_work(workspace, batch_size);
+    const ManoFull mf{nullptr, 0, m.tflag, 1.0f, nullptr, nullptr, nullptr};  // (the forward call left tflag in the workspace)
+    hipLaunchKernelGGL(mano_skin_bwd_kernel<true>, dim3(MN_CHUNKS, (unsigned)batch_size), dim3(256), 0, s, mc, mf,
+                       (const float*)m.v_posed, (const float*)m.G2, grad_verts, grad_jtr, m.grad_vp, m.part, batch_size);
+    MR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mano_blend_bwd_kernel, dim3(5, (unsigned)(m.Mpad / 32), MN_SPLITK), dim3(64), 0, s,
+                       (const float*)m.grad_vp, blend, m.partial, batch_size, m.Mpad);
+    MR_CHECK_LAUNCH();
+    if (pose_form == MN_POSE_AXISANG)
+        hipLaunchKernelGGL((mano_pre_bwd_kernel<MN_POSE_AXISANG, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf,
+                           grad_trans, (const float*)m.full_pose, (const float*)m.rots, (const float*)m.joints,
+                           (const float*)m.G, (const float*)m.part, (const float*)m.partial, grad_jtr, grad_pose,
+                           grad_betas, batch_size, m.Mpad);
+    else
+        hipLaunchKernelGGL((mano_pre_bwd_kernel<MN_POSE_PCA, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf,
+                           grad_trans, (const float*)m.full_pose, (const float*)m.rots, (const float*)m.joints,
+                           (const float*)m.G, (const float*)m.part, (const float*)m.partial, grad_jtr, grad_pose,
+                           grad_betas, batch_size, m.Mpad);
     MR_CHECK_LAUNCH();
     return MR_OK;
 }

@@ -12,13 +12,18 @@ class SynthPoseDataset:
     has_dist2strong = False
 
     def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",), jpeg_quality=None, jpeg_subsampling=2,
-                 png_compress_level=None):
+                 png_compress_level=None, mano_layer=None):
         """2 * num_pairs frames: frame 2k and 2k + 1 are the two time steps of scene k.
         jpeg_quality (None: frames are arrays, as ever): the frames exist as JPEG files' bytes, encoded by Pillow at this
         quality and ``jpeg_subsampling`` (0 / 1 / 2: 4:4:4 / 4:2:2 / 4:2:0) -- ``get_image_bytes(idx)`` returns them (the
         accessor ``HandObjSet(decode="device")`` needs) and ``get_image(idx)`` Pillow's decode of those same bytes.
         png_compress_level (None, or 0..9; not together with jpeg_quality): the same for PNG files, written by Pillow at this
-        zlib level -- lossless, so ``get_image(idx)`` equals the array."""
+        zlib level -- lossless, so ``get_image(idx)`` equals the array.
+        mano_layer (None: the hand vertices are the scene's, as ever): a CPU ``SynthManoLayer`` as the reference's datasets
+        build it (``use_pca=False, flat_hand_mean=True, center_idx=None``, fhbhands.py:103-108).  Every frame then has a MANO
+        annotation (fullpose [48], trans [3], shape [10]) drawn from a generator seeded with ``seed``: ``get_hand_info(idx)``
+        returns it (the reference's accessor, fhbhands.py:367-370) and ``get_hand_verts3d(idx)`` evaluates the layer on it
+        (``manogt.hand_verts_host``, fhbhands.py:355-359).  Everything else is untouched."""
         if jpeg_quality is not None and png_compress_level is not None:
             raise ValueError("jpeg_quality and png_compress_level: the frames are files of one format")
         self.frame_size = tuple(frame_size)  # (W, H)
@@ -61,6 +66,18 @@ class SynthPoseDataset:
         obj_all = np.concatenate(self.obj)
         self.can_trans = obj_all.mean(0)
         self.can_scale = float(np.linalg.norm(obj_all - self.can_trans, axis=1).max())
+        self.mano_layer, self.mano_infos = mano_layer, None
+        if mano_layer is not None:
+            if mano_layer.use_pca:
+                raise ValueError("mano_layer must take the full axis-angle pose (use_pca=False), as the datasets' layer does")
+            mrng = np.random.default_rng([seed, 48])  # (a generator of its own: the frames above do not move)
+            self.mano_infos = []
+            for k in range(2 * num_pairs):
+                fullpose = np.concatenate([mrng.standard_normal(3) * 0.5, mrng.standard_normal(45) * 0.2])
+                # the annotated translation: where the scene's hand is (in front of the camera, metres)
+                trans = self.hand[k].mean(0) + mrng.standard_normal(3) * 0.01
+                self.mano_infos.append({"fullpose": fullpose.astype(np.float32), "trans": trans.astype(np.float32),
+                                        "shape": (mrng.standard_normal(10) * 0.5).astype(np.float32)})
 
     def __len__(self):
         return len(self.frames)
@@ -99,7 +116,18 @@ class SynthPoseDataset:
         return self.hand[idx][:21].copy()
 
     def get_hand_verts3d(self, idx):
+        if self.mano_layer is not None:
+            from handobjectconsist_amd.datasets import manogt
+
+            pose, trans, shape = self.get_hand_info(idx)
+            return manogt.hand_verts_host(self.mano_layer, pose[None], shape[None], trans[None])[0]
         return self.hand[idx].copy()
+
+    def get_hand_info(self, idx):
+        if self.mano_infos is None:
+            raise RuntimeError("SynthPoseDataset(mano_layer=None) holds no MANO annotations")
+        info = self.mano_infos[idx]
+        return info["fullpose"], info["trans"], info["shape"]
 
     def get_obj_verts_trans(self, idx):
         return self.obj[idx].copy()

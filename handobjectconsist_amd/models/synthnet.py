@@ -202,6 +202,67 @@ class _ManoLBSFunction(torch.autograd.Function):
         return g_pose, g_beta, None
 
 
+def _post_arrays(post, B):
+    """The ground-truth epilogue of ``forward_full`` as (scale, trans[B,3] | None, rot[B,3,3], trans2[B,3] | None); each of
+    ``post``'s entries a host array or a tensor, ``rot`` the identity where absent."""
+    unknown = set(post) - {"scale", "trans", "rot", "trans2"}
+    if unknown:
+        raise ValueError(f"forward_full: post has no entries {sorted(unknown)} (scale, trans, rot, trans2)")
+
+    def arr(name, shape):
+        a = post.get(name)
+        if a is None:
+            return None
+        a = a.detach() if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))
+        if tuple(a.shape) != shape:
+            raise ValueError(f"forward_full: post[{name!r}] must be {list(shape)}, got {list(a.shape)}")
+        return a
+
+    rot = arr("rot", (B, 3, 3))
+    if rot is None:
+        rot = torch.eye(3).expand(B, 3, 3)
+    return float(post.get("scale", 1.0)), arr("trans", (B, 3)), rot, arr("trans2", (B, 3))
+
+
+class _ManoFullFunction(torch.autograd.Function):
+    """mr_mano_forward_full / mr_mano_backward_full: either pose form, any centre, th_trans; with ``post`` (the rigid
+    ground-truth epilogue) the outputs carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, pose, betas, trans, layer, post):
+        ctx.set_materialize_grads(False)
+        pose, beta = _lib.contig(pose.detach()), _lib.contig(betas.detach())
+        tr = _lib.contig(trans.detach()) if trans is not None else None
+        B, dev = pose.shape[0], pose.device
+        c = layer.hip_constants()
+        work = torch.empty((max(int(_lib.load().mr_mano_full_workspace_floats(B)), 1),), dtype=torch.float32, device=dev)
+        verts = torch.empty((B, 778, 3), dtype=torch.float32, device=dev)
+        jtr = torch.empty((B, 21, 3), dtype=torch.float32, device=dev)
+        scale, p_trans, p_rot, p_trans2 = post if post is not None else (1.0, None, None, None)
+        _lib.call("mr_mano_forward_full", _lib.ptr(pose), _lib.ptr(beta), _lib.ptr(tr), *[_lib.ptr(t) for t in c["tensors"]],
+                  c["pose_form"], c["ncomps"], c["center"], scale, _lib.ptr(p_trans), _lib.ptr(p_rot), _lib.ptr(p_trans2),
+                  _lib.ptr(work), _lib.ptr(verts), _lib.ptr(jtr), B, _lib.stream_ptr(dev))
+        if post is not None:
+            ctx.mark_non_differentiable(verts, jtr)
+        ctx.layer, ctx.work, ctx.B, ctx.has_trans = layer, work, B, tr is not None
+        return verts, jtr
+
+    @staticmethod
+    def backward(ctx, g_verts, g_jtr):
+        c = ctx.layer.hip_constants()
+        B, dev = ctx.B, ctx.work.device
+        g_pose = torch.empty((B, 48 if c["pose_form"] == _lib.MANO_POSE_AXISANG else 3 + c["ncomps"]), dtype=torch.float32,
+                             device=dev)
+        g_beta = torch.empty((B, 10), dtype=torch.float32, device=dev)
+        g_trans = torch.empty((B, 3), dtype=torch.float32, device=dev) if ctx.has_trans else None
+        gv = _lib.contig(g_verts) if g_verts is not None else None
+        gj = _lib.contig(g_jtr) if g_jtr is not None else None
+        _lib.call("mr_mano_backward_full", *[_lib.ptr(t) for t in c["tensors"]], c["pose_form"], c["ncomps"], c["center"],
+                  _lib.ptr(ctx.work), _lib.ptr(gv), _lib.ptr(gj), _lib.ptr(g_pose), _lib.ptr(g_beta), _lib.ptr(g_trans), B,
+                  _lib.stream_ptr(dev))
+        return g_pose, g_beta, g_trans, None, None
+
+
 class SynthManoLayer(nn.Module):
     """manopth ManoLayer.forward on synthetic MANO-shaped parameters."""
 
@@ -240,11 +301,12 @@ class SynthManoLayer(nn.Module):
             self.register_buffer(name, torch.tensor(idx, dtype=torch.long), persistent=False)  # indices into rel (joint - 1)
 
     def hip_constants(self):
-        """Model constants in the layout of mr_mano_forward, built once per device."""
+        """Model constants in the layout of mr_mano_forward / mr_mano_forward_full, built once per device.  A layer with
+        ``use_pca=False`` passes no ``th_comps`` slice (the axis-angle form does not read one)."""
         dev = self.th_v_template.device
         sources = (self.th_v_template, self.th_shapedirs, self.th_posedirs, self.th_J_regressor, self.th_weights,
                    self.th_comps, self.th_hands_mean)
-        key = (dev, self.ncomps, self.center_idx) + tuple((b.data_ptr(), b._version) for b in sources)
+        key = (dev, self.ncomps, self.center_idx, self.use_pca) + tuple((b.data_ptr(), b._version) for b in sources)
         cached = getattr(self, "_hip_consts", None)
         if cached is not None and cached["key"] == key:  # rebuilt if the buffers move or are overwritten
             return cached
@@ -256,10 +318,11 @@ class SynthManoLayer(nn.Module):
             jt = torch.matmul(self.th_J_regressor, self.th_v_template[0]).reshape(48).contiguous()
             i32 = lambda values: torch.tensor(values, dtype=torch.int32, device=dev)
             center = -1 if self.center_idx is None else MANO_REORDER[self.center_idx]
-            tensors = [self.th_comps[: self.ncomps].contiguous(), self.th_hands_mean.reshape(45).contiguous(), js, jt,
+            tensors = [self.th_comps[: self.ncomps].contiguous() if self.use_pca else None, self.th_hands_mean.reshape(45).contiguous(), js, jt,
                        blend, self.th_v_template.reshape(2334).contiguous(), self.th_weights.contiguous(),
                        i32(MANO_PARENTS), i32(MANO_TIPS), i32(MANO_REORDER)]
-        self._hip_consts = {"key": key, "tensors": tensors, "ncomps": self.ncomps, "center": center}
+        self._hip_consts = {"key": key, "tensors": tensors, "ncomps": self.ncomps, "center": center,
+                            "pose_form": _lib.MANO_POSE_PCA if self.use_pca else _lib.MANO_POSE_AXISANG}
         return self._hip_consts
 
     def _hip_path(self, th_pose_coeffs, th_betas, th_trans):
@@ -281,6 +344,61 @@ class SynthManoLayer(nn.Module):
                 "centre among the 16 articulated joints); build the layer with torch_variants=True to run the PyTorch "
                 "restatement on the GPU instead")
         return self.forward_torch(th_pose_coeffs, th_betas, th_trans)
+
+    def forward_full(self, pose, betas=None, trans=None, *, post=None):
+        """The general call: PCA coefficients ``[B, 3 + ncomps]`` (``use_pca=True``) or the full axis-angle pose
+        ``[B, 48]`` (``use_pca=False``), any ``center_idx`` (None, a joint, a finger tip), an optional translation
+        ``trans [B,3]`` under manopth's rule (all zero = absent), and optionally the rigid ground-truth epilogue ``post`` =
+        ``{"scale", "trans" [B,3], "rot" [B,3,3], "trans2" [B,3]}`` (host arrays or tensors; any may be left out):
+        ``x = rot @ (v * scale + trans) - trans2`` for every vertex and joint, without gradient.
+        fp32 CUDA tensors: mr_mano_forward_full / mr_mano_backward_full, never PyTorch.  CPU tensors: ``forward_torch`` and the
+        epilogue restated in torch.  Any other dtype on a GPU raises, as ``forward`` does, and so does a CUDA pose on a layer
+        whose buffers are on another device (``manogt.hand_verts_batch`` keeps a device copy of a CPU layer for that)."""
+        if pose.dim() != 2 or pose.shape[1] != (3 + self.ncomps if self.use_pca else 48):
+            raise ValueError(f"forward_full: pose must be [B, {3 + self.ncomps if self.use_pca else 48}] for this layer "
+                             f"(use_pca={self.use_pca}), got {list(pose.shape)}")
+        if self.center_idx is not None and not 0 <= self.center_idx <= 20:
+            raise ValueError(f"forward_full: center_idx must be None or one of the 21 joints, got {self.center_idx}")
+        if not 1 <= self.ncomps <= 45:
+            raise ValueError(f"forward_full: ncomps must be in 1..45, got {self.ncomps}")
+        B = pose.shape[0]
+        if betas is not None and tuple(betas.shape) != (B, 10):
+            raise ValueError(f"forward_full: betas must be [{B}, 10], got {list(betas.shape)}")
+        if trans is not None and tuple(trans.shape) != (B, 3):
+            raise ValueError(f"forward_full: trans must be [{B}, 3], got {list(trans.shape)}")
+        post = _post_arrays(post, B) if post is not None else None
+        if pose.is_cuda:
+            others = [t for t in (betas, trans) if t is not None]
+            if pose.dtype != torch.float32 or any(t.dtype != torch.float32 or t.device != pose.device for t in others):
+                raise RuntimeError("SynthManoLayer.forward_full: the HIP kernels take fp32 tensors on one device; no other "
+                                   "dtype runs on a GPU")
+            if self.th_v_template.device != pose.device:  # (the kernels would read the layer's constants through host pointers)
+                raise RuntimeError(f"SynthManoLayer.forward_full: the layer's buffers are on {self.th_v_template.device}, the pose "
+                                   f"on {pose.device}; move the layer with .to(device) first")
+            if betas is None:
+                betas = pose.new_zeros((B, 10))
+            if post is not None:
+                dev_arr = lambda a: None if a is None else a.to(pose.device, torch.float32).contiguous()
+                post = (post[0], dev_arr(post[1]), dev_arr(post[2]), dev_arr(post[3]))
+            return _ManoFullFunction.apply(pose, betas, trans, self, post)
+        # manopth's rule lives in forward_torch's caller: a translation of zero norm counts as absent
+        if trans is not None and float(torch.norm(trans.detach())) == 0.0:
+            trans = None
+        verts, jtr = self.forward_torch(pose, betas, trans)
+        if post is None:
+            return verts, jtr
+        scale, p_trans, p_rot, p_trans2 = post
+        with torch.no_grad():
+            outs = []
+            for x in (verts, jtr):
+                x = x * scale
+                if p_trans is not None:
+                    x = x + p_trans.to(x.dtype).unsqueeze(1)
+                x = torch.matmul(x, p_rot.to(x.dtype).transpose(1, 2))
+                if p_trans2 is not None:
+                    x = x - p_trans2.to(x.dtype).unsqueeze(1)
+                outs.append(x)
+        return outs[0], outs[1]
 
     def forward_torch(self, th_pose_coeffs, th_betas=None, th_trans=None):
         """PyTorch restatement (CPU tensors; GPU only on request, see ``forward``), checked against oracle/mano_ref.py.

@@ -405,6 +405,45 @@ MR_API int mr_mano_backward(const float* comps, const float* hands_mean, const f
                             float* grad_pose_coeffs, float* grad_betas, int batch_size,
                             mr_stream_t stream);
 
+/* The general call of the same layer: what manopth's ManoLayer.forward computes for the
+ * calls made OUTSIDE the network -- the datasets' ground-truth meshes (fhbhands.py:355-359,
+ * ho3dv2.py:341-348: 48 axis-angle values, flat mean, no centre), a translation th_trans
+ * (manobranch.py:130-136) and a finger-tip centre.  Same constants, same workspace scheme
+ * (mr_mano_full_workspace_floats(B) floats), same kernels where the arithmetic is the same.
+ *   pose_form  MR_MANO_POSE_PCA: pose[B, 3 + ncomps] as above.  MR_MANO_POSE_AXISANG: pose[B,48],
+ *              hand part = hands_mean + pose[:, 3:48]; comps is not read and may be NULL.
+ *   center     -1 (none), 0..15 (a chain joint) or 16..20 (a finger tip: a skinned vertex), as an
+ *              index into cat(joints, tips) BEFORE the reorder.
+ *   trans      th_trans[B,3] or NULL.  manopth's rule, evaluated on the device: a translation whose
+ *              values are ALL zero counts as absent and the centre applies; otherwise every sample
+ *              is translated and none is centred: verts = (skinned + trans) * 1000.
+ *   epilogue   applied to the final vertices and joints iff post_rot != NULL, forward only:
+ *              x = v * out_scale; x = x + post_trans[b]; x = post_rot[b] x; x = x - post_trans2[b]
+ *              (post_rot[B,9] row-major; post_trans / post_trans2 [B,3], either may be NULL);
+ *              separate multiplies and adds.  A caller that used it must not call the backward.
+ * mr_mano_backward_full: gradients of pose (in its form), betas and -- grad_trans != NULL -- of
+ * th_trans (zero where the translation counted as absent), from the workspace its forward filled.
+ * B == 0: MR_OK.  NULL or misaligned pointers, ncomps outside 1..45, center outside -1..20, another
+ * pose form, B > 65535: MR_ERR_BADARG before any launch. */
+#define MR_MANO_POSE_PCA 0
+#define MR_MANO_POSE_AXISANG 1
+MR_API int64_t mr_mano_full_workspace_floats(int batch_size);
+MR_API int mr_mano_forward_full(const float* pose, const float* betas, const float* trans,
+                                const float* comps, const float* hands_mean, const float* js,
+                                const float* jt, const float* blend, const float* v_template,
+                                const float* weights, const int32_t* parents, const int32_t* tips,
+                                const int32_t* reorder, int pose_form, int ncomps, int center,
+                                float out_scale, const float* post_trans, const float* post_rot,
+                                const float* post_trans2, float* workspace, float* verts_out,
+                                float* jtr_out, int batch_size, mr_stream_t stream);
+MR_API int mr_mano_backward_full(const float* comps, const float* hands_mean, const float* js,
+                                 const float* jt, const float* blend, const float* v_template,
+                                 const float* weights, const int32_t* parents, const int32_t* tips,
+                                 const int32_t* reorder, int pose_form, int ncomps, int center,
+                                 float* workspace, const float* grad_verts, const float* grad_jtr,
+                                 float* grad_pose, float* grad_betas, float* grad_trans,
+                                 int batch_size, mr_stream_t stream);
+
 /* The parameter-free geometry between MeshRegNet's regression heads and the render path
  * (recover_3d_proj, project.py:5-24; meshregnet.py:206-245, 274-323; objbranch.py:28-84; libyana
  * batch_proj2d), one launch:
