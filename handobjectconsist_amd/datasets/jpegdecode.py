@@ -8,21 +8,14 @@ Baseline / extended-sequential Huffman streams, grey or YCbCr 4:4:4 / 4:2:2 / 4:
 default.  Anything else (progressive, arithmetic, CMYK, ...) raises NotImplementedError -- ``decode_batch`` can hand exactly
 those files to Pillow on request, never silently."""
 import ctypes
-import io
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 from handobjectconsist_amd import _lib
+from handobjectconsist_amd.datasets import framecodec
 
 INFO_FIELDS = ("width", "height", "components", "luma_h", "luma_v", "restart_interval")
-
-
-def _as_bytes(data):
-    if isinstance(data, np.ndarray):
-        data = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
-    return bytes(data)
 
 
 def _raise(rc, what):
@@ -35,7 +28,7 @@ def _raise(rc, what):
 def jpeg_info(data):
     """Geometry of a JPEG stream from its headers: dict of ``INFO_FIELDS``.  ValueError for malformed streams,
     NotImplementedError for streams ``entropy_decode`` does not support."""
-    data = _as_bytes(data)
+    data = framecodec.as_bytes(data)
     info = (ctypes.c_int * 6)()
     rc = _lib.load().mr_jpeg_info(data, len(data), info)
     if rc != 0:
@@ -53,7 +46,7 @@ def packed_bytes(width, height, components, luma_h, luma_v):
 def entropy_decode(data):
     """bytes of one JPEG file -> its packed frame, np.uint8 [packed_bytes(geometry)] (the layout: include/meshraster_hip.h).
     Runs without the GIL; needs no device."""
-    data = _as_bytes(data)
+    data = framecodec.as_bytes(data)
     lib = _lib.load()
     info = (ctypes.c_int * 6)()
     rc = lib.mr_jpeg_info(data, len(data), info)
@@ -92,31 +85,19 @@ def batch_geometry(packed_batch):
     return geom
 
 
+def _device_stage(packed_d, n, geom, out, dev):
+    wbytes = int(_lib.load().mr_jpeg_reconstruct_workspace_bytes(n, *geom))
+    work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
+    _lib.call("mr_jpeg_reconstruct", _lib.ptr(packed_d), n, *geom, _lib.ptr(out), _lib.ptr(work), wbytes, _lib.stream_ptr(dev))
+
+
+# (24 bytes: magic and geometry;  prepare: the library is loaded once, before the pool's threads could race to be the first)
+CODEC = framecodec.Codec("frame_jpeg", entropy_decode, packed_info, batch_geometry, 24, _device_stage, prepare=_lib.load)
+
+
 def reconstruct(packed_batch, device):
     """[N, bytes] packed frames of ONE geometry (numpy or CPU tensor) -> uint8 CUDA [N,H,W,3].  One upload, two launches."""
-    if torch.is_tensor(packed_batch):
-        if packed_batch.is_cuda:
-            raise ValueError("packed_batch lives on the host (its headers are checked there)")
-        packed_batch = packed_batch.numpy()
-    packed_batch = np.ascontiguousarray(packed_batch)
-    if packed_batch.ndim == 2 and packed_batch.shape[0] == 0:
-        raise ValueError("an empty packed_batch has no geometry")
-    width, height, comps, lh, lv = geom = batch_geometry(packed_batch)
-    N = packed_batch.shape[0]
-    dev = torch.device(device)
-    packed_d = torch.from_numpy(packed_batch).to(dev, non_blocking=True)
-    out = torch.empty((N, height, width, 3), dtype=torch.uint8, device=dev)
-    wbytes = int(_lib.load().mr_jpeg_reconstruct_workspace_bytes(N, *geom))
-    work = torch.empty((max(wbytes, 16),), dtype=torch.uint8, device=dev)
-    _lib.call("mr_jpeg_reconstruct", _lib.ptr(packed_d), N, width, height, comps, lh, lv, _lib.ptr(out), _lib.ptr(work), wbytes,
-              _lib.stream_ptr(dev))
-    return out
-
-
-def _pillow_rgb(data):
-    from PIL import Image
-
-    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+    return framecodec.decode_packed(CODEC, packed_batch, device)
 
 
 def decode_batch(files, device, threads=None, unsupported="raise"):
@@ -124,41 +105,4 @@ def decode_batch(files, device, threads=None, unsupported="raise"):
     (default min(16, N)); files of one geometry share one upload and one ``reconstruct`` call.
     unsupported="raise": a stream the host stage does not support raises NotImplementedError; "pillow": exactly those files
     are decoded by Pillow on the host and their pixels uploaded."""
-    if unsupported not in ("raise", "pillow"):
-        raise ValueError("unsupported must be 'raise' or 'pillow'")
-    files = [_as_bytes(f) for f in files]
-    if not files:
-        raise ValueError("decode_batch needs at least one file")
-
-    def one(data):
-        try:
-            return entropy_decode(data)
-        except NotImplementedError:
-            if unsupported == "raise":
-                raise
-            return _pillow_rgb(data)  # [H, W, 3]: told apart from a packed frame by its rank
-
-    threads = min(16, len(files)) if threads is None else max(1, int(threads))
-    _lib.load()  # (once, before the pool's threads could race to be the first)
-    if threads == 1:
-        staged = [one(f) for f in files]
-    else:
-        with ThreadPoolExecutor(threads) as pool:
-            staged = list(pool.map(one, files))
-    dev = torch.device(device)
-    first = staged[0]
-    if all(s.ndim == 1 and s.size == first.size and np.array_equal(s[:24], first[:24]) for s in staged):
-        return reconstruct(np.stack(staged), dev)  # the usual case: one geometry
-    groups, frames = {}, [None] * len(files)
-    for i, s in enumerate(staged):
-        if s.ndim == 3:
-            frames[i] = torch.from_numpy(np.ascontiguousarray(s)).to(dev, non_blocking=True)
-        else:
-            groups.setdefault(s[:24].tobytes() + s.size.to_bytes(8, "little"), []).append(i)
-    for idxs in groups.values():
-        decoded = reconstruct(np.stack([staged[i] for i in idxs]), dev)
-        for k, i in enumerate(idxs):
-            frames[i] = decoded[k]
-    if len({tuple(f.shape) for f in frames}) != 1:
-        raise ValueError("decode_batch: the files have different frame sizes")
-    return frames[0][None] if len(frames) == 1 else torch.stack(frames)
+    return framecodec.decode_batch(CODEC, files, device, threads, unsupported)

@@ -10,27 +10,19 @@ ancillary chunks are skipped -- tRNS among them: ``convert("RGB")`` ignores it f
 (tests/test_oracle_png.py holds that against the installed Pillow).  Palette, other bit depths, Adam7 and APNG raise
 NotImplementedError from the headers alone -- ``decode_batch`` can hand exactly those files to Pillow on request, never
 silently; malformed streams raise ValueError.  Plain Python and the standard library's zlib, which releases the GIL."""
-import io
 import struct
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
-import torch
 
 from handobjectconsist_amd import _lib
+from handobjectconsist_amd.datasets import framecodec
 
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 INFO_FIELDS = ("width", "height", "channels", "color_type")
 CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}  # colour type -> bytes per pixel at bit depth 8
 _DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}  # the specification's combinations
 _CRITICAL = (b"IHDR", b"PLTE", b"IDAT", b"IEND")
-
-
-def _as_bytes(data):
-    if isinstance(data, np.ndarray):
-        data = np.ascontiguousarray(data, dtype=np.uint8).tobytes()
-    return bytes(data)
 
 
 def _chunk(data, pos):
@@ -70,7 +62,7 @@ def _header(data):
 def png_info(data):
     """Geometry of a PNG stream from its signature and IHDR: dict of ``INFO_FIELDS``.  ValueError for malformed headers,
     NotImplementedError for streams ``inflate`` does not support."""
-    return dict(zip(INFO_FIELDS, _header(_as_bytes(data))[:4]))
+    return dict(zip(INFO_FIELDS, _header(framecodec.as_bytes(data))[:4]))
 
 
 def packed_bytes(width, height, channels):
@@ -83,7 +75,7 @@ def packed_bytes(width, height, channels):
 def inflate(data):
     """bytes of one PNG file -> its packed frame, np.uint8 [packed_bytes(geometry)] (the layout: include/meshraster_hip.h).
     Needs no device and no compiled code."""
-    data = _as_bytes(data)
+    data = framecodec.as_bytes(data)
     width, height, channels, color, pos = _header(data)
     idat, ended = [], False
     while pos < len(data):
@@ -148,28 +140,16 @@ def batch_geometry(packed_batch):
     return width, height, channels
 
 
+def _device_stage(packed_d, n, geom, out, dev):
+    _lib.call("mr_png_unfilter", _lib.ptr(packed_d), n, *geom, _lib.ptr(out), None, _lib.stream_ptr(dev))
+
+
+CODEC = framecodec.Codec("frame_png", inflate, packed_info, batch_geometry, 16, _device_stage)  # (16 bytes: magic and geometry)
+
+
 def unfilter(packed_batch, device):
     """[N, bytes] packed frames of ONE geometry (numpy or CPU tensor) -> uint8 CUDA [N,H,W,3].  One upload, one launch."""
-    if torch.is_tensor(packed_batch):
-        if packed_batch.is_cuda:
-            raise ValueError("packed_batch lives on the host (its headers are checked there)")
-        packed_batch = packed_batch.numpy()
-    packed_batch = np.ascontiguousarray(packed_batch)
-    if packed_batch.ndim == 2 and packed_batch.shape[0] == 0:
-        raise ValueError("an empty packed_batch has no geometry")
-    width, height, channels = batch_geometry(packed_batch)
-    N = packed_batch.shape[0]
-    dev = torch.device(device)
-    packed_d = torch.from_numpy(packed_batch).to(dev, non_blocking=True)
-    out = torch.empty((N, height, width, 3), dtype=torch.uint8, device=dev)
-    _lib.call("mr_png_unfilter", _lib.ptr(packed_d), N, width, height, channels, _lib.ptr(out), None, _lib.stream_ptr(dev))
-    return out
-
-
-def _pillow_rgb(data):
-    from PIL import Image
-
-    return np.array(Image.open(io.BytesIO(data)).convert("RGB"))  # (a writable copy: it becomes a tensor)
+    return framecodec.decode_packed(CODEC, packed_batch, device)
 
 
 def decode_batch(files, device, threads=None, unsupported="raise"):
@@ -177,40 +157,4 @@ def decode_batch(files, device, threads=None, unsupported="raise"):
     min(16, N)); files of one geometry share one upload and one ``unfilter`` call.
     unsupported="raise": a stream the host stage does not support raises NotImplementedError; "pillow": exactly those files
     are decoded by Pillow on the host and their pixels uploaded."""
-    if unsupported not in ("raise", "pillow"):
-        raise ValueError("unsupported must be 'raise' or 'pillow'")
-    files = [_as_bytes(f) for f in files]
-    if not files:
-        raise ValueError("decode_batch needs at least one file")
-
-    def one(data):
-        try:
-            return inflate(data)
-        except NotImplementedError:
-            if unsupported == "raise":
-                raise
-            return _pillow_rgb(data)  # [H, W, 3]: told apart from a packed frame by its rank
-
-    threads = min(16, len(files)) if threads is None else max(1, int(threads))
-    if threads == 1:
-        staged = [one(f) for f in files]
-    else:
-        with ThreadPoolExecutor(threads) as pool:
-            staged = list(pool.map(one, files))
-    dev = torch.device(device)
-    first = staged[0]
-    if all(s.ndim == 1 and s.size == first.size and np.array_equal(s[:16], first[:16]) for s in staged):
-        return unfilter(np.stack(staged), dev)  # the usual case: one geometry
-    groups, frames = {}, [None] * len(files)
-    for i, s in enumerate(staged):
-        if s.ndim == 3:
-            frames[i] = torch.from_numpy(np.ascontiguousarray(s)).to(dev, non_blocking=True)
-        else:
-            groups.setdefault(s[:16].tobytes(), []).append(i)
-    for idxs in groups.values():
-        decoded = unfilter(np.stack([staged[i] for i in idxs]), dev)
-        for k, i in enumerate(idxs):
-            frames[i] = decoded[k]
-    if len({tuple(f.shape) for f in frames}) != 1:
-        raise ValueError("decode_batch: the files have different frame sizes")
-    return frames[0][None] if len(frames) == 1 else torch.stack(frames)
+    return framecodec.decode_batch(CODEC, files, device, threads, unsupported)

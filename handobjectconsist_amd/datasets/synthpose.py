@@ -3,8 +3,11 @@
 the synthetic hand + object scene as 'consecutive video frames' of a camera with a larger sensor than the
 network input, so that the crop / augmentation path has real work to do.  Stands in for FPHAB / HO3D,
 which cannot be shipped."""
+import io
+
 import numpy as np
 
+from handobjectconsist_amd.datasets import framecodec
 from handobjectconsist_amd.utils import synth
 
 
@@ -42,27 +45,20 @@ class SynthPoseDataset:
         self.obj_faces = scene["obj_faces"]
         self.frames = rng.integers(0, 256, (2 * num_pairs, H, W, 3), dtype=np.uint8)
         self.sides = [sides[i % len(sides)] for i in range(2 * num_pairs)]
-        self.jpeg = None
+        self.files = None  # the frames as files' bytes, where a format is chosen
+        save = None
         if jpeg_quality is not None:
-            import io
-
-            from PIL import Image
-
-            self.jpeg = []
-            for frame in self.frames:
-                buf = io.BytesIO()
-                Image.fromarray(frame).save(buf, "JPEG", quality=int(jpeg_quality), subsampling=int(jpeg_subsampling))
-                self.jpeg.append(buf.getvalue())
+            save = dict(format="JPEG", quality=int(jpeg_quality), subsampling=int(jpeg_subsampling))
         if png_compress_level is not None:
-            import io
-
+            save = dict(format="PNG", compress_level=int(png_compress_level))
+        if save is not None:
             from PIL import Image
 
-            self.jpeg = []  # (the files' bytes, whatever their format)
+            self.files = []
             for frame in self.frames:
                 buf = io.BytesIO()
-                Image.fromarray(frame).save(buf, "PNG", compress_level=int(png_compress_level))
-                self.jpeg.append(buf.getvalue())
+                Image.fromarray(frame).save(buf, **save)
+                self.files.append(buf.getvalue())
         obj_all = np.concatenate(self.obj)
         self.can_trans = obj_all.mean(0)
         self.can_scale = float(np.linalg.norm(obj_all - self.can_trans, axis=1).max())
@@ -83,18 +79,14 @@ class SynthPoseDataset:
         return len(self.frames)
 
     def get_image(self, idx):
-        if self.jpeg is not None:
-            import io
-
-            from PIL import Image
-
-            return np.asarray(Image.open(io.BytesIO(self.jpeg[idx])).convert("RGB"))
+        if self.files is not None:
+            return framecodec.pillow_rgb(self.files[idx])
         return self.frames[idx]
 
     def get_image_bytes(self, idx):
-        if self.jpeg is None:
+        if self.files is None:
             raise RuntimeError("SynthPoseDataset(jpeg_quality=None, png_compress_level=None) holds arrays, not files")
-        return self.jpeg[idx]
+        return self.files[idx]
 
     def get_sides(self, idx):
         return self.sides[idx]

@@ -103,6 +103,21 @@ def test_decode_batch_hands_unsupported_files_to_pillow_on_request(cuda):
         pngdecode.decode_batch(files[:1] + [GOLD["pil48x40_c3_stream"].tobytes()], cuda)  # two frame sizes
 
 
+
+def test_decode_batch_groups_interleaved_geometries_of_one_frame_size(cuda):
+    """Five 48 x 40 files of 3, 4, 1, 3 and 2 channels: four geometries of one frame size, so ``decode_batch`` unfilters four
+    groups of packed frames (one of them of two files that are not neighbours) and puts the frames back in the files' order."""
+    from handobjectconsist_amd.datasets import pngdecode
+
+    names = ("pil48x40_c3", "pil48x40_c4", "pil48x40_c1", "pil48x40_c3", "pil48x40_c2")
+    files = [GOLD[n + "_stream"].tobytes() for n in names]
+    assert len({pngdecode.inflate(f)[:16].tobytes() for f in files}) == 4
+    want = np.stack([GOLD[n + "_rgb"] for n in names])
+    got = pngdecode.decode_batch(files, cuda)
+    assert got.is_cuda and got.dtype == torch.uint8 and got.shape == (5, 40, 48, 3) and np.array_equal(got.cpu().numpy(), want)
+    assert np.array_equal(pngdecode.decode_batch(files, cuda, threads=1).cpu().numpy(), want)
+
+
 @pytest.fixture(scope="module")
 def dataset_batches():
     """B = 2 sequences of 2 frames of ``SynthPoseDataset(png_compress_level=1)`` (272 x 248: four bands, the last partial),
