@@ -264,6 +264,132 @@ static inline int bn_nhwc_blocks(int64_t pixels, int C) {
     return (int)(need < BN_NHWC_BLOCKS ? (need < 1 ? 1 : need) : BN_NHWC_BLOCKS);
 }
 
+// ---- a block's tail with its downsample branch: relu(bn(x) + bn_d(xd)), NHWC ------------------------------------------
+// The first block of layers 2 - 4 ends in  r = bn_d(conv_d(..));  y = relu(bn2(conv2(..)) + r).  As two bn_act launches
+// r is written, read back, its gradient written and read back again; here both affine maps run in one pass each way
+// (5 tensor streams and a launch + a finish launch less per block).  Same expression shape as the two kernels it
+// replaces -- r = dd * ad + bd;  z = d * a + b;  z = z + r -- so fp32 results have the same bits; for bf16
+// activations r is no longer rounded to bf16 in between.  Backward: g = z > 0 ? grad_y [+ grad_y2] : 0;
+// grad_x = g * a, grad_xd = g * ad; sums g (both biases), g * d, g * dd.  Same pixel walk, workgroup count and
+// summation order as bn_act_nhwc_kernel, so the parameter gradients keep their bits too.
+struct BnAddParams {
+    const void* x;          // [N,HW,C] main branch (conv2's output)
+    const void* xd;         // [N,HW,C] downsample branch (conv_d's output)
+    const float* weight;  const float* bias;  const float* mean;  const float* var;
+    const float* weight_d; const float* bias_d; const float* mean_d; const float* var_d;
+    float eps, eps_d;
+    int N, C, HW;
+    void* y;
+    const void* grad_y;
+    const void* grad_y2;    // optional second gradient of y: summed on load
+    void* grad_x;
+    void* grad_xd;
+    float* partial;         // [3][C][workgroups]: sum g, sum g * (x - mean), sum g * (xd - mean_d)
+};
+
+template <typename T, bool BACKWARD>
+__global__ __launch_bounds__(256) void bn_add_bn_act_nhwc_kernel(BnAddParams p) {
+    __shared__ float red[256][13];
+    const int groups = p.C >> 2;
+    const int cg = threadIdx.x % groups, prow = threadIdx.x / groups, rows = 256 / groups;
+    const int c0 = 4 * cg;
+    float mean[4], a[4], b[4], mean_d[4], ad[4], bd[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        mean[i] = p.mean[c0 + i];
+        a[i] = p.weight[c0 + i] * (1.0f / sqrtf(p.var[c0 + i] + p.eps));
+        b[i] = p.bias[c0 + i];
+        mean_d[i] = p.mean_d[c0 + i];
+        ad[i] = p.weight_d[c0 + i] * (1.0f / sqrtf(p.var_d[c0 + i] + p.eps_d));
+        bd[i] = p.bias_d[c0 + i];
+    }
+    const int64_t pixels = (int64_t)p.N * p.HW;
+    float sg[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sgx[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sgd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t px = (int64_t)blockIdx.x * rows + prow; px < pixels; px += (int64_t)gridDim.x * rows) {
+        const int64_t o = px * p.C + c0;
+        float xv[4], dv[4], gv[4], out[4], outd[4];
+        load4<T>(p.x, o, xv);
+        load4<T>(p.xd, o, dv);
+        if (BACKWARD) {
+            load4<T>(p.grad_y, o, gv);
+            if (p.grad_y2) {
+                float g2[4];
+                load4<T>(p.grad_y2, o, g2);
+#pragma unroll
+                for (int i = 0; i < 4; i++) gv[i] += g2[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float dd = dv[i] - mean_d[i];
+            const float r = dd * ad[i] + bd[i];
+            const float d = xv[i] - mean[i];
+            float z = d * a[i] + b[i];
+            z = z + r;
+            if (!BACKWARD) {
+                out[i] = relu_nan(z);
+            } else {
+                const float g = !(z > 0.0f) ? 0.0f : gv[i];
+                out[i] = g * a[i];
+                outd[i] = g * ad[i];
+                sg[i] += g;
+                sgx[i] += g * d;
+                sgd[i] += g * dd;
+            }
+        }
+        store4<T>(BACKWARD ? p.grad_x : p.y, o, out);
+        if (BACKWARD) store4<T>(p.grad_xd, o, outd);
+    }
+    if (BACKWARD && p.partial) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) { red[threadIdx.x][i] = sg[i]; red[threadIdx.x][4 + i] = sgx[i]; red[threadIdx.x][8 + i] = sgd[i]; }
+        __syncthreads();
+        if (threadIdx.x < groups) {
+            float t[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int r = 0; r < rows; r++)
+#pragma unroll
+                for (int i = 0; i < 12; i++) t[i] += red[r * groups + threadIdx.x][i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                p.partial[(int64_t)(c0 + i) * gridDim.x + blockIdx.x] = t[i];
+                p.partial[(int64_t)(p.C + c0 + i) * gridDim.x + blockIdx.x] = t[4 + i];
+                p.partial[(int64_t)(2 * p.C + c0 + i) * gridDim.x + blockIdx.x] = t[8 + i];
+            }
+        }
+    }
+}
+
+// one workgroup per channel, bn_finish_kernel's summation order: grad_bias = grad_bias_d = sum partial[0][c][:],
+// grad_weight = invstd * sum partial[1][c][:], grad_weight_d = invstd_d * sum partial[2][c][:]
+__global__ __launch_bounds__(256) void bn_add_finish_kernel(const float* __restrict__ partial, const float* __restrict__ var,
+                                                            float eps, const float* __restrict__ var_d, float eps_d,
+                                                            float* grad_weight, float* grad_bias, float* grad_weight_d,
+                                                            float* grad_bias_d, int C, int slots) {
+    __shared__ float red[3][4];
+    const int c = blockIdx.x;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    for (int k = threadIdx.x; k < slots; k += 256) {
+        s0 += partial[(int64_t)c * slots + k];
+        s1 += partial[(int64_t)(C + c) * slots + k];
+        s2 += partial[(int64_t)(2 * C + c) * slots + k];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        s0 += __shfl_down(s0, off);
+        s1 += __shfl_down(s1, off);
+        s2 += __shfl_down(s2, off);
+    }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s0; red[1][threadIdx.x >> 6] = s1; red[2][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float sum_g = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        if (grad_bias) grad_bias[c] = sum_g;
+        if (grad_bias_d) grad_bias_d[c] = sum_g;
+        if (grad_weight) grad_weight[c] = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * (1.0f / sqrtf(var[c] + eps));
+        if (grad_weight_d) grad_weight_d[c] = ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) * (1.0f / sqrtf(var_d[c] + eps_d));
+    }
+}
+
 // sample ranges per channel: enough workgroups to fill the chip (>= ~4096), never more than N
 static inline int bn_split(int N, int C) {
     int s = (4096 + C - 1) / C;
@@ -372,6 +498,87 @@ extern "C" int mr_bn_act_backward(const void* grad_y, const void* grad_y2, const
     if (want_params) {
         hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)channels), dim3(256), 0, (hipStream_t)stream, p.partial,
                            running_var, eps, grad_weight, grad_bias, channels, slots);
+        MR_CHECK_LAUNCH();
+    }
+    return MR_OK;
+}
+
+extern "C" int mr_bn_add_bn_act_forward(const void* x, const void* xd, const float* weight, const float* bias,
+                                        const float* running_mean, const float* running_var, float eps,
+                                        const float* weight_d, const float* bias_d, const float* running_mean_d,
+                                        const float* running_var_d, float eps_d, int act_dtype, void* y, int batch_size,
+                                        int channels, int plane, mr_stream_t stream) {
+    using namespace mr;
+    if (batch_size < 0 || channels < 0 || plane < 0 || (act_dtype != 0 && act_dtype != 1)) return MR_ERR_BADARG;
+    if (channels > 0 && !bn_nhwc_ok(channels)) return MR_ERR_BADARG;
+    if (batch_size == 0 || channels == 0 || plane == 0) return MR_OK;
+    if (!x || !xd || !weight || !bias || !running_mean || !running_var || !weight_d || !bias_d || !running_mean_d ||
+        !running_var_d || !y)
+        return MR_ERR_BADARG;
+    const int vb = act_dtype == 0 ? 16 : 8;
+    if (!bn_aligned(x, vb) || !bn_aligned(xd, vb) || !bn_aligned(y, vb)) return MR_ERR_BADARG;
+    BnAddParams p{};
+    p.x = x; p.xd = xd; p.weight = weight; p.bias = bias; p.mean = running_mean; p.var = running_var; p.eps = eps;
+    p.weight_d = weight_d; p.bias_d = bias_d; p.mean_d = running_mean_d; p.var_d = running_var_d; p.eps_d = eps_d;
+    p.N = batch_size; p.C = channels; p.HW = plane; p.y = y;
+    const dim3 grid((unsigned)bn_nhwc_blocks((int64_t)batch_size * plane, channels));
+    if (act_dtype == 0) hipLaunchKernelGGL((bn_add_bn_act_nhwc_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((bn_add_bn_act_nhwc_kernel<bf16_t, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
+
+extern "C" int64_t mr_bn_add_bn_act_backward_workspace_bytes(int batch_size, int channels) {
+    if (batch_size < 0 || channels < 0) return -1;
+    return (int64_t)3 * channels * mr::BN_NHWC_BLOCKS * 4 + 16;
+}
+
+extern "C" int mr_bn_add_bn_act_backward(const void* grad_y, const void* grad_y2, const void* x, const void* xd,
+                                         const float* weight, const float* bias, const float* running_mean,
+                                         const float* running_var, float eps, const float* weight_d, const float* bias_d,
+                                         const float* running_mean_d, const float* running_var_d, float eps_d,
+                                         int act_dtype, void* grad_x, void* grad_xd, float* grad_weight, float* grad_bias,
+                                         float* grad_weight_d, float* grad_bias_d, void* workspace,
+                                         int64_t workspace_bytes, int batch_size, int channels, int plane,
+                                         mr_stream_t stream) {
+    using namespace mr;
+    if (batch_size < 0 || channels < 0 || plane < 0 || (act_dtype != 0 && act_dtype != 1)) return MR_ERR_BADARG;
+    if (channels > 0 && !bn_nhwc_ok(channels)) return MR_ERR_BADARG;
+    if (channels == 0) return MR_OK;
+    if (!weight || !bias || !running_mean || !running_var || !weight_d || !bias_d || !running_mean_d || !running_var_d)
+        return MR_ERR_BADARG;
+    const bool want_params = grad_weight || grad_bias || grad_weight_d || grad_bias_d;
+    if (batch_size == 0 || plane == 0) {
+        float* const outs[4] = {grad_weight, grad_bias, grad_weight_d, grad_bias_d};
+        for (float* o : outs)
+            if (o) {
+                const hipError_t e = hipMemsetAsync(o, 0, (size_t)channels * 4, (hipStream_t)stream);
+                if (e != hipSuccess) return (int)e;
+            }
+        return MR_OK;
+    }
+    if (!grad_y || !x || !xd || !grad_x || !grad_xd) return MR_ERR_BADARG;
+    if (want_params && (!workspace || workspace_bytes < mr_bn_add_bn_act_backward_workspace_bytes(batch_size, channels)))
+        return MR_ERR_BADARG;
+    const int vb = act_dtype == 0 ? 16 : 8;
+    if (!bn_aligned(x, vb) || !bn_aligned(xd, vb) || !bn_aligned(grad_y, vb) || !bn_aligned(grad_y2, vb) ||
+        !bn_aligned(grad_x, vb) || !bn_aligned(grad_xd, vb))
+        return MR_ERR_BADARG;
+    BnAddParams p{};
+    p.x = x; p.xd = xd; p.weight = weight; p.bias = bias; p.mean = running_mean; p.var = running_var; p.eps = eps;
+    p.weight_d = weight_d; p.bias_d = bias_d; p.mean_d = running_mean_d; p.var_d = running_var_d; p.eps_d = eps_d;
+    p.N = batch_size; p.C = channels; p.HW = plane;
+    p.grad_y = grad_y; p.grad_y2 = grad_y2; p.grad_x = grad_x; p.grad_xd = grad_xd;
+    p.partial = want_params ? static_cast<float*>(workspace) : nullptr;
+    const int slots = bn_nhwc_blocks((int64_t)batch_size * plane, channels);
+    const dim3 grid((unsigned)slots);
+    if (act_dtype == 0) hipLaunchKernelGGL((bn_add_bn_act_nhwc_kernel<float, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((bn_add_bn_act_nhwc_kernel<bf16_t, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    MR_CHECK_LAUNCH();
+    if (want_params) {
+        hipLaunchKernelGGL(bn_add_finish_kernel, dim3((unsigned)channels), dim3(256), 0, (hipStream_t)stream, p.partial,
+                           running_var, eps, running_var_d, eps_d, grad_weight, grad_bias, grad_weight_d, grad_bias_d,
+                           channels, slots);
         MR_CHECK_LAUNCH();
     }
     return MR_OK;

@@ -376,6 +376,184 @@ __global__ __launch_bounds__(256) void stem_pool_nhwc_backward_kernel(StemParams
     }
 }
 
+// ---- channels-last with pooled records (layout code 2) ------------------------------------------------------
+// A gradient reaches at most one pixel per pooling window, so the ReLU mask and x - mean matter only there.  The
+// forward leaves d = x - mean of every window's arg-max pixel (fp32, also for bf16 activations: the channel sums must
+// see the same d as the layouts above) next to its arg-max code; the backward then never touches x:
+//   per window    g = grad_y + grad_y2,  s = (d * a + b > 0) ? g : 0        (the expression of the kernels above, same d)
+//   per pixel     grad_x = a * sum of the s of the <= 4 windows whose code names the pixel, (dy, dx) order as above
+//   per channel   sum s and sum s * d, taken once per window by the thread that owns it
+// y and grad_x have the same bits as layouts 0 / 1; grad_weight / grad_bias sum the same terms window by window instead
+// of pixel by pixel.  One stated difference: a NaN at a pixel that no window selects used to poison grad_weight through
+// 0 * NaN.  Max-pooling propagates NaN, so the windows of a NaN pixel do select a NaN pixel, and the record form sees it
+// unless the incoming gradient there is exactly zero.
+// Record buffer: d[N,OH,OW,C] fp32, then the codes [N,OH,OW,C] u8 (both planes 16-byte aligned; C % 4 == 0).
+__device__ __forceinline__ unsigned char* sp_rec_codes(const StemParams& p) {
+    return p.argmax + (int64_t)p.N * p.OH * p.OW * p.C * 4;
+}
+
+// A thread produces the 2 x 2 pooled values of its four channels from the 5 x 5 input pixels they share: 25 loads of
+// 16 bytes instead of 36.  The pixels are visited row by row, so every window still sees its own in (kh, kw) order.
+template <typename T>
+__global__ __launch_bounds__(256) void stem_pool_rec_forward_kernel(StemParams p) {
+    const int groups = p.C >> 2, cg = threadIdx.x % groups, prow = threadIdx.x / groups, rows = 256 / groups;
+    const int c0 = 4 * cg;
+    float mean[4], a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) stem_consts(p, c0 + i, mean[i], a[i], b[i]);
+    const T* x = static_cast<const T*>(p.x);
+    float* rec_d = reinterpret_cast<float*>(p.argmax);
+    unsigned char* rec_code = sp_rec_codes(p);
+    const int QH = (p.OH + 1) >> 1, QW = (p.OW + 1) >> 1;
+    const int64_t total = (int64_t)p.N * QH * QW;
+    for (int64_t q = (int64_t)blockIdx.x * rows + prow; q < total; q += (int64_t)gridDim.x * rows) {
+        const int qx = (int)(q % QW), qy = (int)((q / QW) % QH), n = (int)(q / ((int64_t)QW * QH));
+        const int oy0 = 2 * qy, ox0 = 2 * qx;
+        float best[2][2][4], bd[2][2][4];
+        unsigned bi[2][2][4];
+#pragma unroll
+        for (int w = 0; w < 4; w++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) { best[w >> 1][w & 1][i] = -__builtin_inff(); bd[w >> 1][w & 1][i] = 0.0f; bi[w >> 1][w & 1][i] = 0; }
+#pragma unroll
+        for (int r = 0; r < 5; r++) {
+            const int iy = 2 * oy0 - 1 + r;
+            if (iy < 0 || iy >= p.H) continue;
+#pragma unroll
+            for (int c = 0; c < 5; c++) {
+                const int ix = 2 * ox0 - 1 + c;
+                if (ix < 0 || ix >= p.W) continue;
+                float xv[4];
+                sp_load4<T>(x, (((int64_t)n * p.H + iy) * p.W + ix) * p.C + c0, xv);
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const float d = xv[i] - mean[i];
+                    const float v = sp_relu_nan(d * a[i] + b[i]);
+#pragma unroll
+                    for (int wy = 0; wy < 2; wy++) {
+                        const int kh = r - 2 * wy;
+                        if (kh < 0 || kh > 2) continue;
+#pragma unroll
+                        for (int wx = 0; wx < 2; wx++) {
+                            const int kw = c - 2 * wx;
+                            if (kw < 0 || kw > 2) continue;
+                            if (v > best[wy][wx][i] || v != v) { best[wy][wx][i] = v; bd[wy][wx][i] = d; bi[wy][wx][i] = (unsigned)(kh * 3 + kw); }
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int wy = 0; wy < 2; wy++)
+#pragma unroll
+            for (int wx = 0; wx < 2; wx++) {
+                const int oy = oy0 + wy, ox = ox0 + wx;
+                if (oy >= p.OH || ox >= p.OW) continue;
+                const int64_t o = (((int64_t)n * p.OH + oy) * p.OW + ox) * p.C + c0;
+                sp_store4<T>(static_cast<T*>(p.y), o, best[wy][wx]);
+                *reinterpret_cast<float4*>(rec_d + o) = make_float4(bd[wy][wx][0], bd[wy][wx][1], bd[wy][wx][2], bd[wy][wx][3]);
+                *reinterpret_cast<uchar4*>(rec_code + o) = make_uchar4((unsigned char)bi[wy][wx][0], (unsigned char)bi[wy][wx][1],
+                                                                       (unsigned char)bi[wy][wx][2], (unsigned char)bi[wy][wx][3]);
+            }
+    }
+}
+
+// A thread owns the 2 x 2 input pixels (rows 2 qy - 1, 2 qy; columns 2 qx - 1, 2 qx) that lie in the same four windows
+// (qy - 1, qy) x (qx - 1, qx): 4 record loads for 4 pixels instead of 9.  Window (qy, qx) is the thread's own and is the
+// only one it counts in the channel sums; the other three are halo.  x is not read.
+template <typename T>
+__global__ __launch_bounds__(256) void stem_pool_rec_backward_kernel(StemParams p) {
+    __shared__ float red[256][9];
+    const int groups = p.C >> 2, cg = threadIdx.x % groups, prow = threadIdx.x / groups, rows = 256 / groups;
+    const int c0 = 4 * cg;
+    float mean[4], a[4], b[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) stem_consts(p, c0 + i, mean[i], a[i], b[i]);
+    const T* gy = static_cast<const T*>(p.grad_y);
+    const T* gy2 = static_cast<const T*>(p.grad_y2);
+    const float* rec_d = reinterpret_cast<const float*>(p.argmax);
+    const unsigned char* rec_code = sp_rec_codes(p);
+    const int QH = (p.H >> 1) + 1, QW = (p.W >> 1) + 1;
+    const int64_t total = (int64_t)p.N * QH * QW;
+    float sg[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sgx[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t q = (int64_t)blockIdx.x * rows + prow; q < total; q += (int64_t)gridDim.x * rows) {
+        const int qx = (int)(q % QW), qy = (int)((q / QW) % QH), n = (int)(q / ((int64_t)QW * QH));
+        float s[2][2][4];
+        unsigned code[2][2][4];
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int wy = qy - 1 + j, wx = qx - 1 + k;
+#pragma unroll
+                for (int i = 0; i < 4; i++) { s[j][k][i] = 0.0f; code[j][k][i] = 255u; }  // no window: names no pixel
+                if (wy < 0 || wy >= p.OH || wx < 0 || wx >= p.OW) continue;
+                const int64_t o = (((int64_t)n * p.OH + wy) * p.OW + wx) * p.C + c0;
+                const uchar4 id = *reinterpret_cast<const uchar4*>(rec_code + o);
+                const float4 dv = *reinterpret_cast<const float4*>(rec_d + o);
+                const float d[4] = {dv.x, dv.y, dv.z, dv.w};
+                float gv[4];
+                sp_load4<T>(gy, o, gv);
+                if (gy2) {
+                    float g2[4];
+                    sp_load4<T>(gy2, o, g2);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) gv[i] += g2[i];
+                }
+                code[j][k][0] = id.x; code[j][k][1] = id.y; code[j][k][2] = id.z; code[j][k][3] = id.w;
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const float sv = (d[i] * a[i] + b[i] > 0.0f) ? gv[i] : 0.0f;  // ReLU
+                    s[j][k][i] = sv;
+                    if (j == 1 && k == 1) { sg[i] += sv; sgx[i] += sv * d[i]; }
+                }
+            }
+#pragma unroll
+        for (int pr = 0; pr < 2; pr++) {
+            const int iy = 2 * qy - 1 + pr;
+            if (iy < 0 || iy >= p.H) continue;
+#pragma unroll
+            for (int pc = 0; pc < 2; pc++) {
+                const int ix = 2 * qx - 1 + pc;
+                if (ix < 0 || ix >= p.W) continue;
+                float g[4] = {0.0f, 0.0f, 0.0f, 0.0f}, out[4];
+#pragma unroll
+                for (int dy = 0; dy < 2; dy++) {  // window row qy first (dy = 0), then qy - 1: the order of the kernels above
+                    const int kh = pr + 2 * dy;
+                    if (kh > 2) continue;
+#pragma unroll
+                    for (int dx = 0; dx < 2; dx++) {
+                        const int kw = pc + 2 * dx;
+                        if (kw > 2) continue;
+                        const unsigned want = (unsigned)(kh * 3 + kw);
+#pragma unroll
+                        for (int i = 0; i < 4; i++) g[i] += code[1 - dy][1 - dx][i] == want ? s[1 - dy][1 - dx][i] : 0.0f;
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) out[i] = g[i] * a[i];
+                sp_store4<T>(static_cast<T*>(p.grad_x), (((int64_t)n * p.H + iy) * p.W + ix) * p.C + c0, out);
+            }
+        }
+    }
+    if (p.partial) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) { red[threadIdx.x][i] = sg[i]; red[threadIdx.x][4 + i] = sgx[i]; }
+        __syncthreads();
+        if (threadIdx.x < groups) {
+            float t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int r = 0; r < rows; r++)
+#pragma unroll
+                for (int i = 0; i < 8; i++) t[i] += red[r * groups + threadIdx.x][i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                p.partial[(int64_t)(c0 + i) * gridDim.x + blockIdx.x] = t[i];
+                p.partial[(int64_t)(p.C + c0 + i) * gridDim.x + blockIdx.x] = t[4 + i];
+            }
+        }
+    }
+}
+
 static inline bool sp_nhwc_ok(int C) { return C >= 4 && C <= 1024 && (1024 % C) == 0; }
 static inline int sp_nhwc_blocks(int64_t pixels, int C) {
     const int rows = 256 / (C / 4);
@@ -411,6 +589,19 @@ extern "C" int mr_stem_pool_forward(const void* x, const float* weight, const fl
     if (batch_size == 0 || channels == 0 || height == 0 || width == 0) return MR_OK;
     if (!x || !weight || !bias || !running_mean || !running_var || !y) return MR_ERR_BADARG;
     p.y = y;
+    if (channels_last == 2) {  // pooled records: argmax is the record buffer
+        const uintptr_t am = (uintptr_t)(act_dtype == 0 ? 15 : 7);
+        if (!argmax || (reinterpret_cast<uintptr_t>(x) & am) || (reinterpret_cast<uintptr_t>(y) & am) ||
+            (reinterpret_cast<uintptr_t>(argmax) & 15))
+            return MR_ERR_BADARG;
+        p.argmax = argmax;
+        const int64_t quads = (int64_t)batch_size * ((p.OH + 1) / 2) * ((p.OW + 1) / 2);
+        const dim3 g((unsigned)sp_nhwc_blocks(quads, channels));
+        if (act_dtype == 0) hipLaunchKernelGGL(stem_pool_rec_forward_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(stem_pool_rec_forward_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, p);
+        MR_CHECK_LAUNCH();
+        return MR_OK;
+    }
     if (channels_last) {
         const uintptr_t am = (uintptr_t)(act_dtype == 0 ? 15 : 7);
         if (!argmax || (reinterpret_cast<uintptr_t>(x) & am) || (reinterpret_cast<uintptr_t>(y) & am) ||
@@ -428,6 +619,15 @@ extern "C" int mr_stem_pool_forward(const void* x, const float* weight, const fl
     else hipLaunchKernelGGL(stem_pool_forward_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
     return MR_OK;
+}
+
+extern "C" int64_t mr_stem_pool_records_bytes(int batch_size, int channels, int height, int width) {
+    using namespace mr;
+    StemParams p{};
+    if (stem_fill(p, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0f, batch_size, channels, height, width) != MR_OK) return -1;
+    if (channels > 0 && !sp_nhwc_ok(channels)) return -1;
+    const int64_t values = (int64_t)batch_size * p.OH * p.OW * channels;  // a multiple of 4
+    return values * 4 + (values + 15) / 16 * 16;
 }
 
 extern "C" int64_t mr_stem_pool_backward_workspace_bytes(int batch_size, int channels, int height, int width) {
@@ -457,7 +657,7 @@ extern "C" int mr_stem_pool_backward(const void* grad_y, const void* grad_y2, co
         if (e == hipSuccess && grad_bias) e = hipMemsetAsync(grad_bias, 0, (size_t)channels * 4, (hipStream_t)stream);
         return e == hipSuccess ? MR_OK : (int)e;
     }
-    if (!grad_y || !x || !weight || !bias || !running_mean || !running_var || !grad_x) return MR_ERR_BADARG;
+    if (!grad_y || (!x && channels_last != 2) || !weight || !bias || !running_mean || !running_var || !grad_x) return MR_ERR_BADARG;
     if (want_params &&
         (!workspace || workspace_bytes < mr_stem_pool_backward_workspace_bytes(batch_size, channels, height, width)))
         return MR_ERR_BADARG;
@@ -465,7 +665,17 @@ extern "C" int mr_stem_pool_backward(const void* grad_y, const void* grad_y2, co
     p.partial = want_params ? static_cast<float*>(workspace) : nullptr;
     const int tiles = p.tiles_x * p.tiles_y;
     int64_t slots = (int64_t)batch_size * tiles;
-    if (channels_last) {
+    if (channels_last == 2) {  // pooled records: x is not read and may be NULL
+        const uintptr_t am = (uintptr_t)(act_dtype == 0 ? 15 : 7);
+        if (!argmax || (reinterpret_cast<uintptr_t>(grad_y) & am) || (reinterpret_cast<uintptr_t>(grad_y2) & am) ||
+            (reinterpret_cast<uintptr_t>(grad_x) & am) || (reinterpret_cast<uintptr_t>(argmax) & 15))
+            return MR_ERR_BADARG;
+        p.argmax = const_cast<unsigned char*>(argmax);
+        slots = sp_nhwc_blocks((int64_t)batch_size * (height / 2 + 1) * (width / 2 + 1), channels);
+        const dim3 g((unsigned)slots);
+        if (act_dtype == 0) hipLaunchKernelGGL(stem_pool_rec_backward_kernel<float>, g, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(stem_pool_rec_backward_kernel<bf16_t>, g, dim3(256), 0, (hipStream_t)stream, p);
+    } else if (channels_last) {
         const uintptr_t am = (uintptr_t)(act_dtype == 0 ? 15 : 7);
         if (!argmax || (reinterpret_cast<uintptr_t>(x) & am) || (reinterpret_cast<uintptr_t>(grad_y) & am) ||
             (reinterpret_cast<uintptr_t>(grad_y2) & am) ||

@@ -71,10 +71,12 @@ class BasicBlock(nn.Module):
     def forward_fused(self, x, x_identity, dup=False):
         """The block on this build's kernels.  x / x_identity: the block input as the two autograd outputs of its
         producer (one for the convolution, one for the identity branch; the same tensor twice is fine too)."""
-        residual = x_identity if self.downsample is None else frozen_bn.bn_act(
-            self.downsample[0](x_identity), self.downsample[1], relu=False)
+        if self.downsample is not None:  # the downsample branch's BatchNorm runs inside the tail kernel
+            xd = self.downsample[0](x_identity)
+            out = frozen_bn.bn_act(self.conv1(x), self.bn1)
+            return frozen_bn.bn_add_bn_act(self.conv2(out), self.bn2, xd, self.downsample[1], dup=dup)
         out = frozen_bn.bn_act(self.conv1(x), self.bn1)
-        return frozen_bn.bn_act(self.conv2(out), self.bn2, residual=residual, dup=dup)
+        return frozen_bn.bn_act(self.conv2(out), self.bn2, residual=x_identity, dup=dup)
 
     def forward(self, x):
         if _fused_bn(self.bn1, x):

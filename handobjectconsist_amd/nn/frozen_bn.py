@@ -1,5 +1,6 @@
 """BatchNorm2d with frozen statistics fused with the residual add and ReLU that follow it
-(``mr_bn_act_forward`` / ``mr_bn_act_backward``).  The reference trains with ``--freeze_batchnorm``
+(``mr_bn_act_forward`` / ``mr_bn_act_backward``; with a downsample branch's BatchNorm on top:
+``mr_bn_add_bn_act_forward`` / ``_backward``).  The reference trains with ``--freeze_batchnorm``
 (trainmeshwarp.py:205-206, 237-240): BatchNorm layers in eval mode, affine parameters trainable, so
 ``relu(bn(x))`` / ``relu(bn(x) + identity)`` / ``bn(x)`` of resnet.py:46-58 are per-channel affine maps."""
 import torch
@@ -99,6 +100,73 @@ def bn_act(x, bn, residual=None, relu=True, dup=False):
     return _BnActFunction.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu, dup)
 
 
+class _BnAddBnActFunction(torch.autograd.Function):
+    """relu(bn(x) + bn_d(xd)) on channels-last activations (``mr_bn_add_bn_act_forward`` / ``_backward``)"""
+
+    @staticmethod
+    def forward(ctx, x, xd, weight, bias, running_mean, running_var, eps, weight_d, bias_d, running_mean_d,
+                running_var_d, eps_d, dup):
+        ctx.set_materialize_grads(False)
+        _lib.check_cuda(x, xd, weight, bias, running_mean, running_var, weight_d, bias_d, running_mean_d, running_var_d)
+        xc, xdc = _aligned(x, 1), _aligned(xd, 1)
+        N, C = xc.shape[:2]
+        plane = xc[0, 0].numel() if N and C else 0
+        f = lambda t: t.detach().float().contiguous()
+        chan = [f(t) for t in (weight, bias, running_mean, running_var, weight_d, bias_d, running_mean_d, running_var_d)]
+        if not all(t.shape == (C,) for t in chan):
+            raise ValueError("channel arrays must be [C]")
+        y = torch.empty_like(xc)
+        _lib.call("mr_bn_add_bn_act_forward", _lib.ptr(xc), _lib.ptr(xdc), *[_lib.ptr(t) for t in chan[:4]], float(eps),
+                  *[_lib.ptr(t) for t in chan[4:]], float(eps_d), _ACT_DTYPES[xc.dtype], _lib.ptr(y), N, C, plane,
+                  _lib.stream_ptr(xc.device))
+        ctx.save_for_backward(xc, xdc, *chan)
+        ctx.cfg = (float(eps), float(eps_d), N, C, plane)
+        return (y, y.view_as(y)) if dup else y
+
+    @staticmethod
+    def backward(ctx, grad_y, grad_y2=None):
+        xc, xdc, *chan = ctx.saved_tensors
+        eps, eps_d, N, C, plane = ctx.cfg
+        need = ctx.needs_input_grad
+        need_x, need_xd, need_w, need_b, need_wd, need_bd = need[0], need[1], need[2], need[3], need[7], need[8]
+        if grad_y is None:
+            grad_y, grad_y2 = grad_y2, None
+        if grad_y is None:
+            return (None,) * 13
+        fmt = torch.channels_last
+        g = _aligned(grad_y.to(xc.dtype).contiguous(memory_format=fmt), 1)
+        g2 = _aligned(grad_y2.to(xc.dtype).contiguous(memory_format=fmt), 1) if grad_y2 is not None else None
+        dev = xc.device
+        grad_x, grad_xd = torch.empty_like(xc), torch.empty_like(xdc)
+        grads = [torch.empty_like(chan[0]) if n else None for n in (need_w, need_b, need_wd, need_bd)]
+        wbytes = int(_lib.load().mr_bn_add_bn_act_backward_workspace_bytes(N, C))
+        work = torch.empty((wbytes,), dtype=torch.uint8, device=dev) if any(t is not None for t in grads) else None
+        _lib.call("mr_bn_add_bn_act_backward", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(xc), _lib.ptr(xdc),
+                  *[_lib.ptr(t) for t in chan[:4]], eps, *[_lib.ptr(t) for t in chan[4:]], eps_d, _ACT_DTYPES[xc.dtype],
+                  _lib.ptr(grad_x), _lib.ptr(grad_xd), *[_lib.ptr(t) for t in grads], _lib.ptr(work), wbytes, N, C, plane,
+                  _lib.stream_ptr(dev))
+        return ((grad_x if need_x else None), (grad_xd if need_xd else None), grads[0], grads[1], None, None, None,
+                grads[2], grads[3], None, None, None, None)
+
+
+def bn_add_bn_act(x, bn, xd, bn_d, dup=False):
+    """``relu(bn(x) + bn_d(xd))`` for two ``nn.BatchNorm2d`` in eval mode: a residual block's tail with its downsample
+    branch, one kernel each way instead of ``bn_act(xd, bn_d, relu=False)`` followed by ``bn_act(x, bn, residual=...)``
+    -- the normalised downsample branch and its gradient are never written (``dup``: see ``bn_act``).  The fused kernels
+    take channels-last activations; any other layout runs as those two ``bn_act`` calls."""
+    for m in (bn, bn_d):
+        if m.training or not m.track_running_stats:
+            raise RuntimeError("bn_add_bn_act needs frozen BatchNorm statistics (module.eval())")
+    if xd.shape != x.shape or xd.dtype != x.dtype:
+        raise ValueError("xd must match x")
+    if x.dim() < 2 or x.dtype not in _ACT_DTYPES:
+        raise ValueError("expected fp32 or bf16 [N, C, ...] tensors")
+    if _layout(x)[1] and _layout(xd)[1]:
+        return _BnAddBnActFunction.apply(x, xd, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn_d.weight,
+                                         bn_d.bias, bn_d.running_mean, bn_d.running_var, bn_d.eps, dup)
+    return bn_act(x, bn, residual=bn_act(xd, bn_d, relu=False), dup=dup)
+
+
 class _StemPoolFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, eps, dup):
@@ -114,37 +182,43 @@ class _StemPoolFunction(torch.autograd.Function):
         oshape = (N, C, (H - 1) // 2 + 1 if H else 0, (W - 1) // 2 + 1 if W else 0)
         fmt = torch.channels_last if cl else torch.contiguous_format
         y = torch.empty(oshape, dtype=xc.dtype, device=xc.device, memory_format=fmt)
-        # channels-last: the forward keeps every pooled value's arg-max position (1 byte) for the backward
-        argmax = torch.empty(oshape, dtype=torch.uint8, device=xc.device, memory_format=fmt) if cl else None
+        # channels-last runs as layout 2, pooled records: the forward leaves every pooled value's arg-max position (1 byte)
+        # and x - mean of that pixel (fp32) for the backward, which then needs neither x nor a pass over it
+        layout = 2 if cl else 0
+        records = None
+        if cl:
+            rbytes = int(_lib.load().mr_stem_pool_records_bytes(N, C, H, W))
+            records = torch.empty((rbytes,), dtype=torch.uint8, device=xc.device)
         _lib.call("mr_stem_pool_forward", _lib.ptr(xc), _lib.ptr(w), _lib.ptr(b), _lib.ptr(m), _lib.ptr(v), float(eps),
-                  _ACT_DTYPES[xc.dtype], cl, _lib.ptr(y), _lib.ptr(argmax), N, C, H, W, _lib.stream_ptr(xc.device))
-        ctx.save_for_backward(xc, w, b, m, v, argmax)
-        ctx.cfg = (float(eps), cl)
+                  _ACT_DTYPES[xc.dtype], layout, _lib.ptr(y), _lib.ptr(records), N, C, H, W, _lib.stream_ptr(xc.device))
+        # NCHW: the backward recomputes bn(x) and needs x; layout 2: the records stand in for it
+        ctx.save_for_backward(None if cl else xc, w, b, m, v, records)
+        ctx.cfg = (float(eps), layout, tuple(xc.shape), xc.dtype, xc.device)
         return (y, y.view_as(y)) if dup else y
 
     @staticmethod
     def backward(ctx, grad_y, grad_y2=None):
-        xc, w, b, m, v, argmax = ctx.saved_tensors
-        eps, cl = ctx.cfg
-        N, C, H, W = xc.shape
+        xc, w, b, m, v, records = ctx.saved_tensors
+        eps, layout, shape, dtype, dev = ctx.cfg
+        N, C, H, W = shape
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         if grad_y is None:
             grad_y, grad_y2 = grad_y2, None
         if grad_y is None:
             return (None,) * 7
-        fmt = torch.channels_last if cl else torch.contiguous_format
-        g = _aligned(grad_y.to(xc.dtype).contiguous(memory_format=fmt), cl)
-        g2 = _aligned(grad_y2.to(xc.dtype).contiguous(memory_format=fmt), cl) if grad_y2 is not None else None
-        grad_x = torch.empty_like(xc)
+        fmt = torch.channels_last if layout else torch.contiguous_format
+        g = _aligned(grad_y.to(dtype).contiguous(memory_format=fmt), layout)
+        g2 = _aligned(grad_y2.to(dtype).contiguous(memory_format=fmt), layout) if grad_y2 is not None else None
+        grad_x = torch.empty(shape, dtype=dtype, device=dev, memory_format=fmt)
         grad_w = torch.empty_like(w) if need_w else None
         grad_b = torch.empty_like(b) if need_b else None
         wbytes = int(_lib.load().mr_stem_pool_backward_workspace_bytes(N, C, H, W))
-        work = torch.empty((wbytes,), dtype=torch.uint8, device=xc.device) if (need_w or need_b) else None
-        _lib.call("mr_stem_pool_backward", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(xc), _lib.ptr(argmax), _lib.ptr(w), _lib.ptr(b),
+        work = torch.empty((wbytes,), dtype=torch.uint8, device=dev) if (need_w or need_b) else None
+        _lib.call("mr_stem_pool_backward", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(xc), _lib.ptr(records), _lib.ptr(w), _lib.ptr(b),
                   _lib.ptr(m),
-                  _lib.ptr(v), eps, _ACT_DTYPES[xc.dtype], cl, _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b),
+                  _lib.ptr(v), eps, _ACT_DTYPES[dtype], layout, _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b),
                   _lib.ptr(work), wbytes, N, C, H, W,
-                  _lib.stream_ptr(xc.device))
+                  _lib.stream_ptr(dev))
         return (grad_x if need_x else None), grad_w, grad_b, None, None, None, None
 
 

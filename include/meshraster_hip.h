@@ -1048,6 +1048,30 @@ MR_API int mr_bn_act_backward(const void* grad_y, const void* grad_y2, const voi
                               void* workspace, int64_t workspace_bytes, int batch_size, int channels,
                               int plane, mr_stream_t stream);
 
+/* A residual block's tail with its downsample branch, one pass each way (the first block of ResNet layers 2 - 4):
+ *   y = relu(((x - mean) * a + bias) + ((xd - mean_d) * a_d + bias_d)),   a = weight / sqrt(var + eps), likewise a_d
+ * instead of mr_bn_act_forward(xd, relu = 0) -> r and mr_bn_act_forward(x, residual = r, relu = 1): r and its gradient
+ * are never written.  NHWC only ([batch_size, plane, channels]), act_dtype 0 = fp32 / 1 = bf16, channels and alignment
+ * as for channels_last = 1 above.  Same expression shape, pixel walk and summation order as the two calls it replaces:
+ * fp32 results, parameter gradients included, have the same bits; for bf16 r is no longer rounded to bf16 in between.
+ * Backward: g = z > 0 ? grad_y [+ grad_y2] : 0;  grad_x = g * a;  grad_xd = g * a_d (both required);  grad_bias =
+ * grad_bias_d = sum g;  grad_weight = sum g * (x - mean) / sqrt(var + eps);  grad_weight_d likewise from xd (each of the
+ * four may be NULL; deterministic two-stage reduction through the workspace, one finish launch). */
+MR_API int mr_bn_add_bn_act_forward(const void* x, const void* xd, const float* weight, const float* bias,
+                                    const float* running_mean, const float* running_var, float eps,
+                                    const float* weight_d, const float* bias_d, const float* running_mean_d,
+                                    const float* running_var_d, float eps_d, int act_dtype, void* y,
+                                    int batch_size, int channels, int plane, mr_stream_t stream);
+MR_API int64_t mr_bn_add_bn_act_backward_workspace_bytes(int batch_size, int channels);
+MR_API int mr_bn_add_bn_act_backward(const void* grad_y, const void* grad_y2, const void* x, const void* xd,
+                                     const float* weight, const float* bias, const float* running_mean,
+                                     const float* running_var, float eps, const float* weight_d,
+                                     const float* bias_d, const float* running_mean_d, const float* running_var_d,
+                                     float eps_d, int act_dtype, void* grad_x, void* grad_xd, float* grad_weight,
+                                     float* grad_bias, float* grad_weight_d, float* grad_bias_d, void* workspace,
+                                     int64_t workspace_bytes, int batch_size, int channels, int plane,
+                                     mr_stream_t stream);
+
 /* The ResNet stem after its 7x7 convolution as one kernel each way (resnet.py:140-147 with frozen statistics):
  *   y = MaxPool2d(kernel 3, stride 2, padding 1)(relu(bn(x)))     x[N,C,H,W] -> y[N,C,(H-1)/2+1,(W-1)/2+1]
  * The full-resolution activation is never written; the backward recomputes it per tile, re-derives every
@@ -1055,11 +1079,22 @@ MR_API int mr_bn_act_backward(const void* grad_y, const void* grad_y2, const voi
  * pooled gradient per input pixel (no atomics).  x, y, grad_x, grad_y are of act_dtype (0 = fp32, 1 = bf16);
  * grad_weight / grad_bias (fp32) may be NULL.  channels_last = 1: NHWC memory order; the forward then also writes
  * argmax[N,OH,OW,C] (u8, position kh * 3 + kw of every pooled value) which the backward reads instead of
- * re-deriving it (argmax is unused and may be NULL for NCHW); channels must be a power of two in [4, 1024]. */
+ * re-deriving it (argmax is unused and may be NULL for NCHW); channels must be a power of two in [4, 1024].
+ * channels_last = 2: NHWC with pooled records.  argmax then points to a record buffer of
+ * mr_stem_pool_records_bytes(N, C, H, W) bytes, 16-byte aligned: d[N,OH,OW,C] (fp32 for either act_dtype: x - mean of every
+ * window's arg-max pixel) followed by the codes [N,OH,OW,C] (u8).  The forward writes both; the backward reads them
+ * and never x, which may be NULL: a gradient reaches at most one pixel per window, so the ReLU mask (d * a + b > 0, the
+ * same expression on the same d) and x - mean matter only there.  y and grad_x have the same bits as with
+ * channels_last = 1; grad_weight / grad_bias sum the same terms once per window instead of once per pixel (fp32
+ * summation order differs).  One difference: with channels_last = 0 / 1 a NaN at a pixel that no window selects
+ * poisons grad_weight through 0 * NaN; max-pooling propagates NaN, so the windows of such a pixel select a NaN pixel
+ * and the record form sees it unless the incoming gradient there is exactly zero.
+ * mr_stem_pool_records_bytes: -1 for negative sizes or channels the NHWC kernels do not take. */
 MR_API int mr_stem_pool_forward(const void* x, const float* weight, const float* bias,
                                 const float* running_mean, const float* running_var, float eps,
                                 int act_dtype, int channels_last, void* y, unsigned char* argmax,
                                 int batch_size, int channels, int height, int width, mr_stream_t stream);
+MR_API int64_t mr_stem_pool_records_bytes(int batch_size, int channels, int height, int width);
 MR_API int64_t mr_stem_pool_backward_workspace_bytes(int batch_size, int channels, int height, int width);
 MR_API int mr_stem_pool_backward(const void* grad_y, const void* grad_y2, const void* x,
                                  const unsigned char* argmax,
