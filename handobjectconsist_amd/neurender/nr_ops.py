@@ -15,6 +15,8 @@ import torch.nn.functional as F
 def projection(vertices, K, R, t, dist_coeffs, orig_size, eps=1e-9):
     """Pinhole + 5-coefficient distortion projection to NDC x,y in [-1,1] with metric z
     (called at renderer.py:187).  K [B,3,3], R [B|1,3,3], t [B|1,(1,)3], dist_coeffs [B|1,5]."""
+    if t.dim() == 2:  # one translation per SAMPLE: [B,3] must not broadcast against [B,V,3] as if it were [V,3]
+        t = t.unsqueeze(1)
     vertices = torch.matmul(vertices, R.transpose(2, 1)) + t
     x, y, z = vertices[:, :, 0], vertices[:, :, 1], vertices[:, :, 2]
     x_ = x / (z + eps)

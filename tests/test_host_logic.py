@@ -628,3 +628,26 @@ def test_bench_uses_the_recorded_solver_choices_only_where_they_apply(monkeypatc
     monkeypatch.delenv("HOC_TUNING_DIR")
     monkeypatch.setenv("MIOPEN_USER_DB_PATH", os.path.join(bench.TUNING_DIR, "miopen"))
     assert bench.recorded_solver_choices(args(), 0) is True
+
+
+def test_projection_takes_one_translation_per_sample():
+    """nr_ops.projection with t [B,3] (the renderer's per-sample camera, or a batch-1 camera expanded to the batch): the
+    translation of sample b goes to every vertex of sample b -- also when V == B, where [B,3] + [B,V,3] would broadcast
+    without an error as one translation per VERTEX.  [1,3] and [B,1,3] keep their bits."""
+    import torch
+
+    from handobjectconsist_amd.neurender import nr_ops
+
+    g = torch.Generator().manual_seed(4)
+    for B, V in ((3, 3), (2, 5), (1, 4)):
+        verts = torch.randn(B, V, 3, generator=g) * 0.05 + torch.tensor([0.0, 0.0, 0.5])
+        K = torch.tensor([[350.0, 0.0, 120.0], [0.0, 350.0, 131.0], [0.0, 0.0, 1.0]]).repeat(B, 1, 1)
+        R, dist = torch.eye(3).repeat(B, 1, 1), torch.randn(B, 5, generator=g) * 0.01
+        t = torch.randn(B, 3, generator=g) * 0.02
+        want = torch.stack([nr_ops.projection(verts[b:b + 1], K[b:b + 1], R[b:b + 1], t[b:b + 1, None], dist[b:b + 1], 256)[0]
+                            for b in range(B)])
+        assert torch.equal(nr_ops.projection(verts, K, R, t, dist, 256), want), (B, V)
+        assert torch.equal(nr_ops.projection(verts, K, R, t[:, None], dist, 256), want)
+        one = nr_ops.projection(verts, K, R[:1], t[:1], dist[:1], 256)
+        assert torch.equal(one, nr_ops.projection(verts, K, R[:1], t[:1].expand(B, 3), dist[:1], 256))
+        assert torch.equal(one, nr_ops.projection(verts, K, R[:1], t[:1, None], dist[:1], 256))
