@@ -34,6 +34,34 @@ def _aligned(t, cl):
     return t
 
 
+def _channel_arrays(C, *tensors):
+    """The per-channel operands as the kernels read them: fp32, contiguous, detached, each of shape [C]"""
+    chan = [t.detach().float().contiguous() for t in tensors]
+    if not all(t.shape == (C,) for t in chan):
+        raise ValueError("channel arrays must be [C]")
+    return chan
+
+
+def _incoming(grad_y, grad_y2, dtype, cl):
+    """The one or two gradients of a ``dup`` output as the backward kernels take them.  Arrival rule: with one consumer
+    unused only one of the two arrives, and it goes first -- ``(g, None)``; ``(None, None)`` when neither did.  Each is
+    cast to the activation type and brought to the forward's memory format and alignment."""
+    if grad_y is None:
+        grad_y, grad_y2 = grad_y2, None
+    if grad_y is None:
+        return None, None
+    fmt = torch.channels_last if cl else torch.contiguous_format
+    prep = lambda t: _aligned(t.to(dtype).contiguous(memory_format=fmt), cl)
+    return prep(grad_y), (prep(grad_y2) if grad_y2 is not None else None)
+
+
+def _workspace(sizer, dims, device, wanted):
+    """(buffer for the partial sums of the parameter gradients or None when none is wanted, its size in bytes) from the
+    entry point ``sizer`` (``mr_*_backward_workspace_bytes``)"""
+    wbytes = int(getattr(_lib.load(), sizer)(*dims))
+    return (torch.empty((wbytes,), dtype=torch.uint8, device=device) if wanted else None), wbytes
+
+
 class _BnActFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, eps, relu, dup):
@@ -51,10 +79,7 @@ class _BnActFunction(torch.autograd.Function):
             rc = _aligned(rc, cl)
         N, C = xc.shape[:2]
         plane = xc[0, 0].numel() if N and C else 0
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-        m, v = running_mean.float().contiguous(), running_var.float().contiguous()
-        if not (w.shape == b.shape == m.shape == v.shape == (C,)):
-            raise ValueError("channel arrays must be [C]")
+        w, b, m, v = _channel_arrays(C, weight, bias, running_mean, running_var)
         y = torch.empty_like(xc)
         _lib.call("mr_bn_act_forward", _lib.ptr(xc), _lib.ptr(rc), _lib.ptr(w), _lib.ptr(b), _lib.ptr(m), _lib.ptr(v),
                   float(eps), int(bool(relu)), _ACT_DTYPES[xc.dtype], cl, _lib.ptr(y), N, C, plane,
@@ -70,20 +95,15 @@ class _BnActFunction(torch.autograd.Function):
         xc, rc, w, b, m, v = ctx.saved_tensors
         eps, relu, N, C, plane, cl = ctx.cfg
         need_x, need_r, need_w, need_b = ctx.needs_input_grad[:4]
-        if grad_y is None:
-            grad_y, grad_y2 = grad_y2, None
-        if grad_y is None:
+        g, g2 = _incoming(grad_y, grad_y2, xc.dtype, cl)
+        if g is None:
             return (None,) * 9
-        fmt = torch.channels_last if cl else torch.contiguous_format
-        g = _aligned(grad_y.to(xc.dtype).contiguous(memory_format=fmt), cl)
-        g2 = _aligned(grad_y2.to(xc.dtype).contiguous(memory_format=fmt), cl) if grad_y2 is not None else None
         dev = xc.device
         grad_x = torch.empty_like(xc)
         grad_r = torch.empty_like(xc) if (rc is not None and need_r) else None
         grad_w = torch.empty_like(w) if need_w else None
         grad_b = torch.empty_like(b) if need_b else None
-        wbytes = int(_lib.load().mr_bn_act_backward_workspace_bytes(N, C))
-        work = torch.empty((wbytes,), dtype=torch.uint8, device=dev) if (need_w or need_b) else None
+        work, wbytes = _workspace("mr_bn_act_backward_workspace_bytes", (N, C), dev, need_w or need_b)
         _lib.call("mr_bn_act_backward", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(xc), _lib.ptr(rc), _lib.ptr(w), _lib.ptr(b), _lib.ptr(m),
                   _lib.ptr(v), eps, int(relu), _ACT_DTYPES[xc.dtype], cl, _lib.ptr(grad_x), _lib.ptr(grad_r), _lib.ptr(grad_w),
                   _lib.ptr(grad_b),
@@ -111,10 +131,7 @@ class _BnAddBnActFunction(torch.autograd.Function):
         xc, xdc = _aligned(x, 1), _aligned(xd, 1)
         N, C = xc.shape[:2]
         plane = xc[0, 0].numel() if N and C else 0
-        f = lambda t: t.detach().float().contiguous()
-        chan = [f(t) for t in (weight, bias, running_mean, running_var, weight_d, bias_d, running_mean_d, running_var_d)]
-        if not all(t.shape == (C,) for t in chan):
-            raise ValueError("channel arrays must be [C]")
+        chan = _channel_arrays(C, weight, bias, running_mean, running_var, weight_d, bias_d, running_mean_d, running_var_d)
         y = torch.empty_like(xc)
         _lib.call("mr_bn_add_bn_act_forward", _lib.ptr(xc), _lib.ptr(xdc), *[_lib.ptr(t) for t in chan[:4]], float(eps),
                   *[_lib.ptr(t) for t in chan[4:]], float(eps_d), _ACT_DTYPES[xc.dtype], _lib.ptr(y), N, C, plane,
@@ -129,18 +146,13 @@ class _BnAddBnActFunction(torch.autograd.Function):
         eps, eps_d, N, C, plane = ctx.cfg
         need = ctx.needs_input_grad
         need_x, need_xd, need_w, need_b, need_wd, need_bd = need[0], need[1], need[2], need[3], need[7], need[8]
-        if grad_y is None:
-            grad_y, grad_y2 = grad_y2, None
-        if grad_y is None:
+        g, g2 = _incoming(grad_y, grad_y2, xc.dtype, 1)
+        if g is None:
             return (None,) * 13
-        fmt = torch.channels_last
-        g = _aligned(grad_y.to(xc.dtype).contiguous(memory_format=fmt), 1)
-        g2 = _aligned(grad_y2.to(xc.dtype).contiguous(memory_format=fmt), 1) if grad_y2 is not None else None
         dev = xc.device
         grad_x, grad_xd = torch.empty_like(xc), torch.empty_like(xdc)
         grads = [torch.empty_like(chan[0]) if n else None for n in (need_w, need_b, need_wd, need_bd)]
-        wbytes = int(_lib.load().mr_bn_add_bn_act_backward_workspace_bytes(N, C))
-        work = torch.empty((wbytes,), dtype=torch.uint8, device=dev) if any(t is not None for t in grads) else None
+        work, wbytes = _workspace("mr_bn_add_bn_act_backward_workspace_bytes", (N, C), dev, any(t is not None for t in grads))
         _lib.call("mr_bn_add_bn_act_backward", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(xc), _lib.ptr(xdc),
                   *[_lib.ptr(t) for t in chan[:4]], eps, *[_lib.ptr(t) for t in chan[4:]], eps_d, _ACT_DTYPES[xc.dtype],
                   _lib.ptr(grad_x), _lib.ptr(grad_xd), *[_lib.ptr(t) for t in grads], _lib.ptr(work), wbytes, N, C, plane,
@@ -177,8 +189,7 @@ class _StemPoolFunction(torch.autograd.Function):
         xc, cl = _layout(x)
         xc = _aligned(xc, cl)
         N, C, H, W = xc.shape
-        w, b = weight.detach().float().contiguous(), bias.detach().float().contiguous()
-        m, v = running_mean.float().contiguous(), running_var.float().contiguous()
+        w, b, m, v = _channel_arrays(C, weight, bias, running_mean, running_var)
         oshape = (N, C, (H - 1) // 2 + 1 if H else 0, (W - 1) // 2 + 1 if W else 0)
         fmt = torch.channels_last if cl else torch.contiguous_format
         y = torch.empty(oshape, dtype=xc.dtype, device=xc.device, memory_format=fmt)
@@ -202,18 +213,14 @@ class _StemPoolFunction(torch.autograd.Function):
         eps, layout, shape, dtype, dev = ctx.cfg
         N, C, H, W = shape
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        if grad_y is None:
-            grad_y, grad_y2 = grad_y2, None
-        if grad_y is None:
+        g, g2 = _incoming(grad_y, grad_y2, dtype, layout)
+        if g is None:
             return (None,) * 7
         fmt = torch.channels_last if layout else torch.contiguous_format
-        g = _aligned(grad_y.to(dtype).contiguous(memory_format=fmt), layout)
-        g2 = _aligned(grad_y2.to(dtype).contiguous(memory_format=fmt), layout) if grad_y2 is not None else None
         grad_x = torch.empty(shape, dtype=dtype, device=dev, memory_format=fmt)
         grad_w = torch.empty_like(w) if need_w else None
         grad_b = torch.empty_like(b) if need_b else None
-        wbytes = int(_lib.load().mr_stem_pool_backward_workspace_bytes(N, C, H, W))
-        work = torch.empty((wbytes,), dtype=torch.uint8, device=dev) if (need_w or need_b) else None
+        work, wbytes = _workspace("mr_stem_pool_backward_workspace_bytes", (N, C, H, W), dev, need_w or need_b)
         _lib.call("mr_stem_pool_backward", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(xc), _lib.ptr(records), _lib.ptr(w), _lib.ptr(b),
                   _lib.ptr(m),
                   _lib.ptr(v), eps, _ACT_DTYPES[dtype], layout, _lib.ptr(grad_x), _lib.ptr(grad_w), _lib.ptr(grad_b),

@@ -156,6 +156,25 @@ def test_argument_validation_needs_no_device():
     full = lib.mr_render_backward_workspace_bytes(64, 3076, 256)
     assert w + 2 * 64 * 128 * 4 <= full <= w + 2 * 64 * 128 * 4 + 3 * 256
     assert lib.mr_render_backward_workspace_bytes(-1, 1, 8) == -1
+    # trunk glue kernels: 4 bytes x sums per channel (2; bn_add_bn_act 3) x channels x partial-sum slots, + 16.  Slots: the
+    # channels-last workgroup cap (2048; stem 4096) or, where larger, the NCHW count -- bn_split = min(ceil(4096 / C), N)
+    # sample ranges (1024 at C = 4: the cap holds; 4096 at C = 1: above it), the stem's (sample, 32 x 16 tile) pairs
+    # (300 x 5 x 9 = 13500 > 4096).  The launchers take their slot count from the same function, so these numbers also pin
+    # the grids of the backward kernels.
+    assert lib.mr_bn_act_backward_workspace_bytes(192, 64) == 1048592
+    assert lib.mr_bn_act_backward_workspace_bytes(8192, 4) == 2 * 4 * 2048 * 4 + 16 == 65552
+    assert lib.mr_bn_act_backward_workspace_bytes(8192, 1) == 2 * 1 * 4096 * 4 + 16
+    assert lib.mr_bn_add_bn_act_backward_workspace_bytes(192, 64) == 1572880
+    assert lib.mr_stem_pool_backward_workspace_bytes(192, 64, 128, 128) == 2097168
+    assert lib.mr_stem_pool_backward_workspace_bytes(300, 4, 257, 257) == 2 * 4 * 13500 * 4 + 16 == 432016
+    assert lib.mr_stem_pool_records_bytes(192, 64, 128, 128) == 251658240
+    for bad in ((-1, 64), (192, -1)):
+        assert lib.mr_bn_act_backward_workspace_bytes(*bad) == -1
+        assert lib.mr_bn_add_bn_act_backward_workspace_bytes(*bad) == -1
+    for bad in ((-1, 64, 128, 128), (192, -1, 128, 128), (192, 64, -1, 128), (192, 64, 128, -1)):
+        assert lib.mr_stem_pool_backward_workspace_bytes(*bad) == -1
+        assert lib.mr_stem_pool_records_bytes(*bad) == -1
+    assert lib.mr_stem_pool_records_bytes(192, 6, 128, 128) == -1
     null = ctypes.c_void_p(None)
     # NULL pointers / bad sizes are rejected with MR_ERR_BADARG before anything touches HIP
     assert lib.mr_warp_forward(null, null, null, null, 1, 3, 8, 8, 0.99999, 0, null) == -1

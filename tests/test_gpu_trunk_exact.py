@@ -31,7 +31,7 @@ BN_NCHW = [
     (3, 8, 4, 4),        # vector path
     (3, 5, 3, 5),        # scalar path (HW % 4 != 0)
     (6, 1024, 2, 2),     # split = 4 < N: sample ranges 1 / 2 / 1 / 2
-    (300, 4, 1, 4),      # split = 300 > 256: second trip of bn_finish_kernel
+    (300, 4, 1, 4),      # split = 300 > 256: second trip of bn_finish_kernel<2>
 ]
 BN_CL_FALLBACK = (5, 2048, 1, 4)   # channels-last input with C > 1024: NCHW kernels through _layout
 BN_CL = [
@@ -46,7 +46,7 @@ BN_CL = [
 STEM_NCHW = [
     (2, 3, 35, 70),      # two tiles each way, W % 4 != 0, odd H
     (2, 4, 36, 72),      # vector path across tile seams
-    (70, 2, 33, 65),     # N * tiles = 280 > 256 slots: second trip of stem_finish_kernel
+    (70, 2, 33, 65),     # N * tiles = 280 > 256 slots: second trip of bn_finish_kernel<2> (the stem's slots)
     (2, 3, 1, 1),
     (1, 2, 2, 3),
 ]
