@@ -138,6 +138,10 @@ SIGNATURES = {
     "mr_stem_pool_records_bytes": (_L, [_I, _I, _I, _I]),
     "mr_stem_pool_backward_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "mr_stem_pool_backward": (_I, [_P] * 8 + [_F, _I, _I] + [_P] * 4 + [_L, _I, _I, _I, _I, _P]),
+    "mr_stem_pool_param_grads": (_I, [_P] * 7 + [_F, _I] + [_P] * 3 + [_L, _I, _I, _I, _I, _P]),
+    "mr_stem_conv_wrw_tiling": (_I, [_P] * 3),
+    "mr_stem_conv_wrw_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "mr_stem_conv_wrw": (_I, [_P] * 7 + [_F, _P, _P, _I, _P, _L] + [_I] * 8 + [_P]),
 }
 
 _lib = None

@@ -414,6 +414,35 @@ __global__ __launch_bounds__(256) void stem_pool_rec_backward_kernel(StemParams 
     if (p.partial) nhwc_block_sums<2>(l, sums, p.partial, p.C);
 }
 
+// The channel sums of the kernel above without its grad_x: for a stem whose input gradient nobody wants (the convolution
+// in front of it reads an image, and its weight gradient comes from stem_wrw.hip).  Same walk, same grid, and per thread
+// the same additions in the same order -- only a quad's own window (qy, qx) enters the sums -- so grad_weight / grad_bias
+// have the bits of the full backward.  Reads d and the gradients; the codes are not needed.
+template <typename T>
+__global__ __launch_bounds__(256) void stem_pool_rec_sums_kernel(StemParams p) {
+    const NhwcLane l = nhwc_lane(p.bn, p.C);
+    const float* rec_d = reinterpret_cast<const float*>(p.argmax);
+    const int QH = (p.H >> 1) + 1, QW = (p.W >> 1) + 1;
+    const int64_t total = (int64_t)p.N * QH * QW;
+    float sums[2][4] = {};  // sum s, sum s * d
+    for (int64_t q = l.first(); q < total; q += l.stride()) {
+        const int qx = (int)(q % QW), qy = (int)((q / QW) % QH), n = (int)(q / ((int64_t)QW * QH));
+        if (qy >= p.OH || qx >= p.OW) continue;
+        const int64_t o = (((int64_t)n * p.OH + qy) * p.OW + qx) * p.C + l.c0;
+        const float4 dv = *reinterpret_cast<const float4*>(rec_d + o);
+        const float d[4] = {dv.x, dv.y, dv.z, dv.w};
+        float gv[4];
+        load4_grad<T>(p.grad_y, p.grad_y2, o, gv);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float sv = (d[i] * l.a[i] + l.b[i] > 0.0f) ? gv[i] : 0.0f;  // ReLU
+            sums[0][i] += sv;
+            sums[1][i] += sv * d[i];
+        }
+    }
+    nhwc_block_sums<2>(l, sums, p.partial, p.C);
+}
+
 static int stem_fill(StemParams& p, const void* x, const float* weight, const float* bias, const float* mean,
                      const float* var, float eps, int N, int C, int H, int W) {
     if (N < 0 || C < 0 || H < 0 || W < 0) return MR_ERR_BADARG;
@@ -543,5 +572,37 @@ extern "C" int mr_stem_pool_backward(const void* grad_y, const void* grad_y2, co
     stem_launch<true>(p, act_dtype, layout, layout ? slots : slots * channels, (hipStream_t)stream);
     MR_CHECK_LAUNCH();
     if (!want_params) return MR_OK;
+    return launch_bn_finish<2>(p.partial, slots, channels, BnFinishOut{running_var, eps, grad_weight, grad_bias}, (hipStream_t)stream);
+}
+
+// grad_weight / grad_bias of the layout-2 backward alone (stem_pool_rec_sums_kernel): no x, no grad_x.  Workspace as for
+// mr_stem_pool_backward; at least one of the two outputs must be asked for.
+extern "C" int mr_stem_pool_param_grads(const void* grad_y, const void* grad_y2, const unsigned char* records, const float* weight,
+                                        const float* bias, const float* running_mean, const float* running_var, float eps,
+                                        int act_dtype, float* grad_weight, float* grad_bias, void* workspace,
+                                        int64_t workspace_bytes, int batch_size, int channels, int height, int width,
+                                        mr_stream_t stream) {
+    using namespace mr;
+    if (act_dtype != 0 && act_dtype != 1) return MR_ERR_BADARG;
+    if (channels > 0 && !nhwc_channels_ok(channels)) return MR_ERR_BADARG;
+    if (!grad_weight && !grad_bias) return MR_ERR_BADARG;
+    StemParams p{};
+    const int rc = stem_fill(p, nullptr, weight, bias, running_mean, running_var, eps, batch_size, channels, height, width);
+    if (rc != MR_OK) return rc;
+    if (channels == 0) return MR_OK;
+    if (batch_size == 0 || height == 0 || width == 0) return zero_param_grads({grad_weight, grad_bias}, channels, (hipStream_t)stream);
+    if (!grad_y || !weight || !bias || !running_mean || !running_var) return MR_ERR_BADARG;
+    if (!workspace || workspace_bytes < mr_stem_pool_backward_workspace_bytes(batch_size, channels, height, width)) return MR_ERR_BADARG;
+    if (!stem_records_ok(records, 2) || !aligned4(grad_y, act_dtype) || !aligned4(grad_y2, act_dtype)) return MR_ERR_BADARG;
+    p.grad_y = grad_y; p.grad_y2 = grad_y2;
+    p.partial = static_cast<float*>(workspace);
+    p.argmax = const_cast<unsigned char*>(records);
+    const int64_t slots = stem_slots(p, 2);
+    const dim3 grid((unsigned)slots), block(256);
+    dispatch_act(act_dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(stem_pool_rec_sums_kernel<T>, grid, block, 0, (hipStream_t)stream, p);
+    });
+    MR_CHECK_LAUNCH();
     return launch_bn_finish<2>(p.partial, slots, channels, BnFinishOut{running_var, eps, grad_weight, grad_bias}, (hipStream_t)stream);
 }

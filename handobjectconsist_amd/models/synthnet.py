@@ -46,6 +46,12 @@ USE_HIP_BN = os.environ.get("HOC_HIP_BN", "1") == "1"
 USE_CHANNELS_LAST = os.environ.get("HOC_CHANNELS_LAST", "1") == "1"
 
 
+# The stem's convolution and BatchNorm / ReLU / max-pool as one autograd node when the image wants no gradient: the
+# convolution's weight gradient then comes straight from the pooled gradient and the stem's records (csrc/stem_wrw.hip)
+# and the 805 MB gradient of the convolution's output is neither written nor read.  False: the composed path.
+USE_STEM_WRW = True
+
+
 def _fused_bn(bn, x):
     """x is the convolution's INPUT; the kernels see its output (the BN input), whose dtype is the autocast dtype
     when autocast is on and x's own otherwise.  fp32 and bf16 take the kernels, anything else (fp16 autocast, fp64)
@@ -124,7 +130,10 @@ class ResNet18Features(nn.Module):
             # every activation with two consumers (the next block's convolution and its identity branch) leaves its
             # producer as two autograd outputs, so that the producer's backward kernel sums the two gradients on load
             blocks = [b for layer in (self.layer1, self.layer2, self.layer3, self.layer4) for b in layer]
-            pair = frozen_bn.stem_pool(self.conv1(x), self.bn1, dup=True)  # bn1 + relu + maxpool(3, 2, 1)
+            if USE_STEM_WRW and frozen_bn.conv_stem_applies(x, self.conv1, self.bn1):
+                pair = frozen_bn.conv_stem_pool(x, self.conv1, self.bn1, dup=True)  # conv1 + bn1 + relu + maxpool(3, 2, 1)
+            else:
+                pair = frozen_bn.stem_pool(self.conv1(x), self.bn1, dup=True)  # bn1 + relu + maxpool(3, 2, 1)
             for block in blocks[:-1]:
                 pair = block.forward_fused(pair[0], pair[1], dup=True)
             x = blocks[-1].forward_fused(pair[0], pair[1])

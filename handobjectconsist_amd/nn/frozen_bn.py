@@ -4,6 +4,7 @@
 (trainmeshwarp.py:205-206, 237-240): BatchNorm layers in eval mode, affine parameters trainable, so
 ``relu(bn(x))`` / ``relu(bn(x) + identity)`` / ``bn(x)`` of resnet.py:46-58 are per-channel affine maps."""
 import torch
+import torch.nn.functional as F
 
 from handobjectconsist_amd import _lib
 
@@ -235,3 +236,77 @@ def stem_pool(x, bn, dup=False):
     if bn.training or not bn.track_running_stats:
         raise RuntimeError("stem_pool needs frozen BatchNorm statistics (module.eval())")
     return _StemPoolFunction.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, dup)
+
+
+class _ConvStemFunction(torch.autograd.Function):
+    """The stem's convolution and ``stem_pool`` as one node for an image that wants no gradient: the backward forms the
+    convolution's weight gradient straight from the pooled gradient and the records (``mr_stem_conv_wrw``) and the
+    BatchNorm's from ``mr_stem_pool_param_grads``; the gradient of the convolution's output is never written."""
+
+    @staticmethod
+    def forward(ctx, image, conv_weight, weight, bias, running_mean, running_var, eps, dup):
+        ctx.set_materialize_grads(False)
+        _lib.check_cuda(image, conv_weight, weight, bias, running_mean, running_var)
+        x = F.conv2d(image, conv_weight, None, 2, 3)  # the convolution of the composed path, not recorded
+        x = _aligned(x.contiguous(memory_format=torch.channels_last), 1)
+        N, C, H, W = x.shape
+        w, b, m, v = _channel_arrays(C, weight, bias, running_mean, running_var)
+        y = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=x.dtype, device=x.device,
+                        memory_format=torch.channels_last)
+        records = torch.empty((int(_lib.load().mr_stem_pool_records_bytes(N, C, H, W)),), dtype=torch.uint8, device=x.device)
+        _lib.call("mr_stem_pool_forward", _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(m), _lib.ptr(v), float(eps),
+                  0, 2, _lib.ptr(y), _lib.ptr(records), N, C, H, W, _lib.stream_ptr(x.device))
+        ctx.save_for_backward(image, w, b, m, v, records)
+        ctx.cfg = (float(eps), (N, C, H, W), conv_weight.is_contiguous(memory_format=torch.channels_last), conv_weight.dtype)
+        return (y, y.view_as(y)) if dup else y
+
+    @staticmethod
+    def backward(ctx, grad_y, grad_y2=None):
+        image, w, b, m, v, records = ctx.saved_tensors
+        eps, (N, C, H, W), w_cl, w_dtype = ctx.cfg
+        _, need_cw, need_w, need_b = ctx.needs_input_grad[:4]
+        g, g2 = _incoming(grad_y, grad_y2, torch.float32, 2)
+        if g is None:
+            return (None,) * 8
+        dev = image.device
+        lib = _lib.load()
+        grad_cw = grad_w = grad_b = None
+        if need_w or need_b:
+            grad_w = torch.empty_like(w) if need_w else None
+            grad_b = torch.empty_like(b) if need_b else None
+            work, wbytes = _workspace("mr_stem_pool_backward_workspace_bytes", (N, C, H, W), dev, True)
+            _lib.call("mr_stem_pool_param_grads", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(records), _lib.ptr(w), _lib.ptr(b),
+                      _lib.ptr(m), _lib.ptr(v), eps, 0, _lib.ptr(grad_w), _lib.ptr(grad_b), _lib.ptr(work), wbytes, N, C, H, W,
+                      _lib.stream_ptr(dev))
+        if need_cw:
+            Hin, Win = image.shape[2:]
+            grad_cw = torch.empty((C, 3, 7, 7), dtype=torch.float32, device=dev,
+                                  memory_format=torch.channels_last if w_cl else torch.contiguous_format)
+            work, wbytes = _workspace("mr_stem_conv_wrw_workspace_bytes", (N, C, Hin, Win), dev, True)
+            _lib.call("mr_stem_conv_wrw", _lib.ptr(g), _lib.ptr(g2), _lib.ptr(records), _lib.ptr(w), _lib.ptr(b), _lib.ptr(m),
+                      _lib.ptr(v), eps, _lib.ptr(image), _lib.ptr(grad_cw), int(w_cl), _lib.ptr(work), wbytes, N, C, Hin, Win,
+                      3, 7, 2, 3, _lib.stream_ptr(dev))
+        return None, grad_cw, grad_w, grad_b, None, None, None, None
+
+
+def conv_stem_applies(image, conv, bn):
+    """Does ``conv_stem_pool`` take this stem?  fp32 channels-last image that wants no gradient, no autocast, the ResNet
+    stem's convolution (7 x 7, stride 2, padding 3, 3 -> 64 channels, no bias), frozen BatchNorm statistics."""
+    w = conv.weight
+    return (image.is_cuda and image.dim() == 4 and image.dtype == torch.float32 and not image.requires_grad
+            and not torch.is_autocast_enabled("cuda")
+            and image.numel() > 0 and image.is_contiguous(memory_format=torch.channels_last)
+            and image.data_ptr() % 4 == 0
+            and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros" and conv.in_channels == 3
+            and conv.out_channels == 64 and w.dtype == torch.float32
+            and (w.is_contiguous(memory_format=torch.channels_last) or w.is_contiguous())
+            and not bn.training and bn.track_running_stats and bn.weight.dtype == torch.float32)
+
+
+def conv_stem_pool(image, conv, bn, dup=False):
+    """``stem_pool(conv(image), bn)`` where ``conv_stem_applies``: the same values, and in the backward no gradient map of
+    the convolution's output (``dup``: see ``bn_act``)."""
+    if not conv_stem_applies(image, conv, bn):
+        raise RuntimeError("conv_stem_pool does not take this stem (see conv_stem_applies)")
+    return _ConvStemFunction.apply(image, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, dup)

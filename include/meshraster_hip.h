@@ -1104,6 +1104,36 @@ MR_API int mr_stem_pool_backward(const void* grad_y, const void* grad_y2, const 
                                  int64_t workspace_bytes, int batch_size, int channels, int height,
                                  int width, mr_stream_t stream);
 
+/* grad_weight / grad_bias of mr_stem_pool_backward with channels_last = 2 alone: the same kernel walk, grid, partial sums
+ * and finish, without grad_x (and without reading the codes), so both have the bits of the full backward.  For a stem whose
+ * input gradient nobody needs.  records: the layout-2 record buffer; workspace: mr_stem_pool_backward_workspace_bytes.
+ * One of grad_weight / grad_bias may be NULL. */
+MR_API int mr_stem_pool_param_grads(const void* grad_y, const void* grad_y2, const unsigned char* records,
+                                    const float* weight, const float* bias, const float* running_mean,
+                                    const float* running_var, float eps, int act_dtype, float* grad_weight,
+                                    float* grad_bias, void* workspace, int64_t workspace_bytes, int batch_size,
+                                    int channels, int height, int width, mr_stream_t stream);
+
+/* Weight gradient of the stem's convolution (kernel 7, stride 2, padding 3, 3 -> 64 channels, no bias) straight from the
+ * stem's pooled gradient and layout-2 records: the gradient of the convolution's output is built per tile in LDS with the
+ * arithmetic of mr_stem_pool_backward (channels_last = 2) and contracted with the image on fp32 MFMA; it is never written
+ * to memory.  grad_y / grad_y2 (optional, summed on load) [N,OH,OW,C] fp32 channels-last, records as written by
+ * mr_stem_pool_forward for the convolution's [N,C,H,W] output, H = (in_height - 1) / 2 + 1; image [N,in_height,in_width,3]
+ * fp32 (channels-last).  grad_conv_weight [C,3,7,7] fp32 in the weight's memory format: weight_channels_last = 1 writes
+ * [C][kh][kw][ci], 0 writes [C][ci][kh][kw].  Deterministic: persistent workgroups walk fixed tile lists, each leaves one
+ * partial result in the workspace, a finish kernel adds them in a fixed order; no atomics.
+ * MR_ERR_BADARG (nothing launched) unless kernel_size = 7, stride = 2, padding = 3, in_channels = 3, channels = 64, the
+ * records and gradients are 16-byte aligned and the workspace holds mr_stem_conv_wrw_workspace_bytes (-1 for sizes it
+ * refuses).  mr_stem_conv_wrw_tiling: the conv-output tile a workgroup takes at a time and the number of workgroups. */
+MR_API int mr_stem_conv_wrw_tiling(int* tile_height, int* tile_width, int* workgroups);
+MR_API int64_t mr_stem_conv_wrw_workspace_bytes(int batch_size, int channels, int in_height, int in_width);
+MR_API int mr_stem_conv_wrw(const float* grad_y, const float* grad_y2, const unsigned char* records,
+                            const float* weight, const float* bias, const float* running_mean,
+                            const float* running_var, float eps, const float* image, float* grad_conv_weight,
+                            int weight_channels_last, void* workspace, int64_t workspace_bytes, int batch_size,
+                            int channels, int in_height, int in_width, int in_channels, int kernel_size, int stride,
+                            int padding, mr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
