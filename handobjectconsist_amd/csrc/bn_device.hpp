@@ -196,7 +196,7 @@ static inline int nhwc_blocks(int64_t items, int C, int cap) {
 
 // may `p` be the base of 4-element accesses of this activation type (16 bytes fp32, 8 bytes bf16)?  NULL may.
 static inline bool aligned4(const void* p, int act_dtype) {
-    return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(act_dtype == 0 ? 15 : 7)) == 0;
+    return !misaligned({p}, act_dtype == 0 ? 15 : 7);
 }
 
 // bytes of a workspace for K sums per channel in `slots` slots

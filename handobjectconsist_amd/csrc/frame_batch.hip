@@ -279,15 +279,23 @@ __global__ __launch_bounds__(256) void frames_to_batch_kernel(FrameBatchParams p
     }
 }
 
-static inline int64_t fb_align(int64_t v) { return (v + 15) & ~(int64_t)15; }
+// workspace: the colour LUT | frame headers | two double tables per output row | the x and y tap tables (16-byte regions):
+// places them in `p`, returns the bytes
+static int64_t batch_work(void* ws, int64_t n, int64_t H, int64_t W, FrameBatchParams& p) {
+    Carve c;
+    p.lut = at_offset<float>(ws, c.take(768 * 4, 16));
+    p.hdr = at_offset<FrameHdr>(ws, c.take(n * (int64_t)sizeof(FrameHdr), 16));
+    p.rowx = at_offset<double>(ws, c.take(n * H * 8, 16)); p.rowy = at_offset<double>(ws, c.take(n * H * 8, 16));
+    p.xtab = at_offset<int>(ws, c.take(n * W * 4, 16)); p.ytab = at_offset<int>(ws, c.take(n * H * 4, 16));
+    return c.total();
+}
 
 }  // namespace mr
 
 extern "C" int64_t mr_frames_to_batch_workspace_bytes(int num_frames, int height, int width) {
     if (num_frames < 0 || height < 0 || width < 0) return -1;
-    const int64_t n = num_frames, H = height, W = width;
-    return mr::fb_align(768 * 4) + mr::fb_align(n * (int64_t)sizeof(mr::FrameHdr)) + 2 * mr::fb_align(n * H * 8) + mr::fb_align(n * W * 4) +
-           mr::fb_align(n * H * 4);
+    mr::FrameBatchParams p;
+    return mr::batch_work(nullptr, num_frames, height, width, p);
 }
 
 extern "C" int mr_frames_to_batch_typed(const uint8_t* frames, const double* coeffs, const uint8_t* flip, float mean0,
@@ -304,22 +312,12 @@ extern "C" int mr_frames_to_batch_typed(const uint8_t* frames, const double* coe
     if (!coeffs || !image || !workspace) return MR_ERR_BADARG;
     if (num_frames > 65535 || height > 32767 || width > 32767 || src_height > 32767 || src_width > 32767)
         return MR_ERR_BADARG;
-    if (workspace_bytes < mr_frames_to_batch_workspace_bytes(num_frames, height, width)) return MR_ERR_BADARG;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(image) & 15) ||
-        (reinterpret_cast<uintptr_t>(jittermask) & 15))
-        return MR_ERR_BADARG;
     FrameBatchParams p;
+    if (workspace_bytes < batch_work(workspace, num_frames, height, width, p)) return MR_ERR_BADARG;
+    if (misaligned({workspace, image, jittermask}, 15)) return MR_ERR_BADARG;
     p.frames = frames; p.coeffs = coeffs; p.flip = flip;
     p.mean[0] = mean0; p.mean[1] = mean1; p.mean[2] = mean2;
     p.stdv[0] = std0; p.stdv[1] = std1; p.stdv[2] = std2;
-    char* w = static_cast<char*>(workspace);
-    const int64_t n = num_frames;
-    p.lut = reinterpret_cast<float*>(w);    w += fb_align(768 * 4);
-    p.hdr = reinterpret_cast<FrameHdr*>(w); w += fb_align(n * (int64_t)sizeof(FrameHdr));
-    p.rowx = reinterpret_cast<double*>(w);  w += fb_align(n * height * 8);
-    p.rowy = reinterpret_cast<double*>(w);  w += fb_align(n * height * 8);
-    p.xtab = reinterpret_cast<int*>(w);     w += fb_align(n * width * 4);
-    p.ytab = reinterpret_cast<int*>(w);
     p.image = image; p.mask = jittermask; p.mask_channels = jittermask ? mask_channels : 0;
     p.N = num_frames; p.Hs = src_height; p.Ws = src_width; p.H = height; p.W = width;
     p.Hs_ld = src_height > 0 ? src_height : 1;

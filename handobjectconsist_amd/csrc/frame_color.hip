@@ -269,7 +269,14 @@ __global__ __launch_bounds__(FC_THREADS) void color_tail_kernel(ColorParams p) {
     }
 }
 
-static inline int64_t fc_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
+// workspace: the frames' plans | their luma sums | the row-blurred frames: places them in `p`, returns the bytes
+static int64_t color_work(void* ws, int64_t n, int src_height, int src_width, ColorParams& p) {
+    Carve c;
+    p.plans = at_offset<ColorPlan>(ws, c.take(n * (int64_t)sizeof(ColorPlan)));
+    p.lsum = at_offset<unsigned long long>(ws, c.take(n * 8));
+    p.tmp = at_offset<uint8_t>(ws, c.take(n * src_height * src_width * 3));
+    return c.total();
+}
 
 // Pillow's _gaussian_blur_radius + the weights of ImagingHorizontalBoxBlur: float variables, float32 operations
 static void box_weights(float radius, ColorPlan& pl) {
@@ -288,8 +295,8 @@ static void box_weights(float radius, ColorPlan& pl) {
 
 extern "C" int64_t mr_frames_color_augment_workspace_bytes(int num_frames, int src_height, int src_width) {
     if (num_frames < 0 || src_height < 0 || src_width < 0) return -1;
-    const int64_t n = num_frames;
-    return mr::fc_align(n * (int64_t)sizeof(mr::ColorPlan)) + mr::fc_align(n * 8) + mr::fc_align(n * src_height * src_width * 3);
+    mr::ColorParams p;
+    return mr::color_work(nullptr, num_frames, src_height, src_width, p);
 }
 
 extern "C" int mr_frames_color_augment(const uint8_t* frames_in, uint8_t* frames_out, const uint8_t* flip,
@@ -301,10 +308,9 @@ extern "C" int mr_frames_color_augment(const uint8_t* frames_in, uint8_t* frames
     if (num_frames < 0 || src_height < 0 || src_width < 0) return MR_ERR_BADARG;
     if (num_frames == 0 || src_height == 0 || src_width == 0) return MR_OK;
     if (!frames_in || !frames_out || !blur_radius || !op_codes || !op_values || !workspace) return MR_ERR_BADARG;
-    if ((reinterpret_cast<uintptr_t>(frames_in) & 3) || (reinterpret_cast<uintptr_t>(frames_out) & 3) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return MR_ERR_BADARG;
-    if (workspace_bytes < mr_frames_color_augment_workspace_bytes(num_frames, src_height, src_width)) return MR_ERR_BADARG;
+    if (misaligned({frames_in, frames_out}, 3) || misaligned({workspace}, 15)) return MR_ERR_BADARG;
+    ColorParams p;
+    if (workspace_bytes < color_work(workspace, num_frames, src_height, src_width, p)) return MR_ERR_BADARG;
     if (num_frames > 65535) return MR_ERR_NOTIMPL;  // a frame is a grid row (gridDim.y)
     std::vector<ColorPlan> plans((size_t)num_frames);
     bool any_contrast = false;
@@ -337,11 +343,6 @@ extern "C" int mr_frames_color_augment(const uint8_t* frames_in, uint8_t* frames
         any_contrast = any_contrast || pl.split < pl.nops;
     }
     if (src_height > FC_MAX_DIM || src_width > FC_MAX_DIM) return MR_ERR_NOTIMPL;  // a line no longer fits a workgroup's LDS
-    ColorParams p;
-    char* w = static_cast<char*>(workspace);
-    p.plans = reinterpret_cast<ColorPlan*>(w);          w += fc_align((int64_t)num_frames * (int64_t)sizeof(ColorPlan));
-    p.lsum = reinterpret_cast<unsigned long long*>(w);  w += fc_align((int64_t)num_frames * 8);
-    p.tmp = reinterpret_cast<uint8_t*>(w);
     p.in = frames_in; p.out = frames_out;
     p.N = num_frames; p.Hs = src_height; p.Ws = src_width;
     p.rows_per_block = FC_LDS / (src_width * 3);

@@ -212,18 +212,21 @@ extern "C" int64_t mr_jpeg_packed_bytes(int width, int height, int components, i
 }
 
 extern "C" int mr_jpeg_entropy_decode(const unsigned char* data, int64_t len, unsigned char* packed, int64_t packed_bytes) {
-    if (!data || !packed || len < 0 || (reinterpret_cast<uintptr_t>(packed) & 3)) return MR_ERR_BADARG;
+    if (!data || !packed || len < 0 || mr::misaligned({packed}, 3)) return MR_ERR_BADARG;
     mrjpeg::JeStream s;
     const int rc = mrjpeg::je_parse(data, len, s);
     if (rc != mrjpeg::JE_OK) return rc;
     return mrjpeg::je_decode(data, len, s, packed, packed_bytes);
 }
 
+// workspace: ONE region at the base, the frames' planes after the IDCT, 64 bytes per block
+static int64_t jpeg_work_bytes(int num_frames, const mrjpeg::JeGeometry& g) { return (int64_t)num_frames * 64 * g.blocks; }
+
 extern "C" int64_t mr_jpeg_reconstruct_workspace_bytes(int num_frames, int width, int height, int components, int luma_h,
                                                        int luma_v) {
     mrjpeg::JeGeometry g;
     if (num_frames < 0 || !mrjpeg::je_geometry(width, height, components, luma_h, luma_v, g)) return -1;
-    return (int64_t)num_frames * 64 * g.blocks;
+    return jpeg_work_bytes(num_frames, g);
 }
 
 extern "C" int mr_jpeg_reconstruct(const unsigned char* packed, int num_frames, int width, int height, int components,
@@ -234,10 +237,8 @@ extern "C" int mr_jpeg_reconstruct(const unsigned char* packed, int num_frames, 
     if (num_frames < 0 || !mrjpeg::je_geometry(width, height, components, luma_h, luma_v, g)) return MR_ERR_BADARG;
     if (num_frames == 0) return MR_OK;
     if (!packed || !frames_out || !workspace) return MR_ERR_BADARG;
-    if ((reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(frames_out) & 3) ||
-        (reinterpret_cast<uintptr_t>(workspace) & 15))
-        return MR_ERR_BADARG;
-    if (workspace_bytes < (int64_t)num_frames * 64 * g.blocks) return MR_ERR_BADARG;
+    if (misaligned({packed, workspace}, 15) || misaligned({frames_out}, 3)) return MR_ERR_BADARG;
+    if (workspace_bytes < jpeg_work_bytes(num_frames, g)) return MR_ERR_BADARG;
     JpegParams p;
     p.packed = packed;
     p.planes = static_cast<uint8_t*>(workspace);

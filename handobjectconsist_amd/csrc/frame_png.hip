@@ -182,7 +182,7 @@ extern "C" int mr_png_unfilter(const unsigned char* packed, int num_frames, int 
     if (num_frames < 0 || !png_geometry_ok(width, height, channels)) return MR_ERR_BADARG;
     if (num_frames == 0) return MR_OK;
     if (!packed || !frames_out) return MR_ERR_BADARG;
-    if ((reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(frames_out) & 3)) return MR_ERR_BADARG;
+    if (misaligned({packed}, 15) || misaligned({frames_out}, 3)) return MR_ERR_BADARG;
     // a frame's byte offsets are 32-bit and a reconstructed row lives in LDS: 4 * 10752 bytes at most
     if (width > MR_PNG_MAX_SIDE || height > MR_PNG_MAX_SIDE) return MR_ERR_NOTIMPL;
     PngParams p;

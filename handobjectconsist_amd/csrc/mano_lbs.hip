@@ -573,34 +573,30 @@ static ManoConst mano_const(const float* comps, const float* mean, const float* 
                      ncomps, center};
 }
 
-extern "C" int64_t mr_mano_workspace_floats(int batch_size) {
-    if (batch_size < 0) return MR_ERR_BADARG;
-    const int64_t B = batch_size, Mpad = (B + 31) / 32 * 32;
-    // coeff | G | G2 | rots | joints | full_pose | v_posed | grad_vp | part | partial
-    return B * MN_KP + 2 * B * MN_J * 12 + B * MN_J * 9 + 2 * B * 48 + 2 * B * MN_NV3 + B * MN_CHUNKS * MN_PART +
-           (int64_t)MN_SPLITK * Mpad * 160;
-}
-
+// coeff | G | G2 | rots | joints | full_pose | v_posed | grad_vp | part | partial ( | tflag): float arrays, packed
 struct ManoWork {
     float *coeff, *G, *G2, *rots, *joints, *full_pose, *v_posed, *grad_vp, *part, *partial;
     float* tflag;  // [B], behind the regions of mr_mano_workspace_floats: mr_mano_full_workspace_floats only
     int Mpad;
+    int64_t floats, full_floats;  // without / with tflag
 };
-static ManoWork mano_work(float* w, int B) {
+static ManoWork mano_work(float* w, int64_t B) {
     ManoWork m;
-    m.Mpad = (B + 31) / 32 * 32;
-    m.coeff = w; w += (int64_t)B * MN_KP;
-    m.G = w; w += (int64_t)B * MN_J * 12;
-    m.G2 = w; w += (int64_t)B * MN_J * 12;
-    m.rots = w; w += (int64_t)B * MN_J * 9;
-    m.joints = w; w += (int64_t)B * 48;
-    m.full_pose = w; w += (int64_t)B * 48;
-    m.v_posed = w; w += (int64_t)B * MN_NV3;
-    m.grad_vp = w; w += (int64_t)B * MN_NV3;
-    m.part = w; w += (int64_t)B * MN_CHUNKS * MN_PART;
-    m.partial = w; w += (int64_t)MN_SPLITK * m.Mpad * 160;
-    m.tflag = w;
+    m.Mpad = (int)((B + 31) / 32 * 32);
+    Carve c;
+    auto take = [&](int64_t floats) { return at_offset<float>(w, c.take(floats * 4, 4)); };
+    m.coeff = take(B * MN_KP); m.G = take(B * MN_J * 12); m.G2 = take(B * MN_J * 12); m.rots = take(B * MN_J * 9);
+    m.joints = take(B * 48); m.full_pose = take(B * 48); m.v_posed = take(B * MN_NV3); m.grad_vp = take(B * MN_NV3);
+    m.part = take(B * MN_CHUNKS * MN_PART); m.partial = take((int64_t)MN_SPLITK * m.Mpad * 160);
+    m.floats = c.total() / 4;
+    m.tflag = take(B);
+    m.full_floats = c.total() / 4;
     return m;
+}
+
+extern "C" int64_t mr_mano_workspace_floats(int batch_size) {
+    if (batch_size < 0) return MR_ERR_BADARG;
+    return mano_work(nullptr, batch_size).floats;
 }
 
 extern "C" int mr_mano_forward(const float* pose_coeffs, const float* betas, const float* comps, const float* hands_mean,
@@ -624,7 +620,7 @@ extern "C" int mr_mano_forward(const float* pose_coeffs, const float* betas, con
     hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((batch_size + 31) / 32)), dim3(64), 0, s,
                        (const float*)m.coeff, blend, v_template, m.v_posed, batch_size);
     MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_skin_kernel<false>, dim3((MN_V + 255) / 256, (unsigned)batch_size), dim3(256), 0, s, mc,
+    hipLaunchKernelGGL(mano_skin_kernel<false>, dim3(blocks1d(MN_V), (unsigned)batch_size), dim3(256), 0, s, mc,
                        ManoFull{}, (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out,
                        batch_size);
     MR_CHECK_LAUNCH();
@@ -665,13 +661,7 @@ extern "C" int mr_mano_backward(const float* comps, const float* hands_mean, con
 // ---------------------------------------------------------------------------------------------------
 extern "C" int64_t mr_mano_full_workspace_floats(int batch_size) {
     if (batch_size < 0) return MR_ERR_BADARG;
-    return mr_mano_workspace_floats(batch_size) + batch_size;  // ... | tflag
-}
-
-static bool mano_misaligned(std::initializer_list<const void*> ptrs) {
-    for (const void* p : ptrs)
-        if ((uintptr_t)p & 3u) return true;
-    return false;
+    return mano_work(nullptr, batch_size).full_floats;
 }
 
 // what both general entry points check before anything touches HIP
@@ -684,7 +674,7 @@ static int mano_full_check(const float* comps, const float* hands_mean, const fl
     if ((pose_form == MN_POSE_PCA && !comps) || !hands_mean || !js || !jt || !blend || !v_template || !weights || !parents ||
         !tips || !reorder || !workspace)
         return MR_ERR_BADARG;
-    if (mano_misaligned({comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, workspace}))
+    if (misaligned({comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, workspace}, 3))
         return MR_ERR_BADARG;
     return MR_OK;
 }
@@ -702,7 +692,7 @@ extern "C" int mr_mano_forward_full(const float* pose, const float* betas, const
                                    ncomps, center, workspace, batch_size);
     if (rc != MR_OK) return rc;
     if (!pose || !betas || !verts_out || !jtr_out || (!post_rot && (post_trans || post_trans2))) return MR_ERR_BADARG;
-    if (mano_misaligned({pose, betas, trans, post_trans, post_rot, post_trans2, verts_out, jtr_out})) return MR_ERR_BADARG;
+    if (misaligned({pose, betas, trans, post_trans, post_rot, post_trans2, verts_out, jtr_out}, 3)) return MR_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
@@ -718,7 +708,7 @@ extern "C" int mr_mano_forward_full(const float* pose, const float* betas, const
     hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((batch_size + 31) / 32)), dim3(64), 0, s,
                        (const float*)m.coeff, blend, v_template, m.v_posed, batch_size);
     MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_skin_kernel<true>, dim3((MN_V + 255) / 256, (unsigned)batch_size), dim3(256), 0, s, mc, mf,
+    hipLaunchKernelGGL(mano_skin_kernel<true>, dim3(blocks1d(MN_V), (unsigned)batch_size), dim3(256), 0, s, mc, mf,
                        (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out, batch_size);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -736,7 +726,7 @@ extern "C" int mr_mano_backward_full(const float* comps, const float* hands_mean
                                    ncomps, center, workspace, batch_size);
     if (rc != MR_OK) return rc;
     if (!grad_pose || !grad_betas) return MR_ERR_BADARG;
-    if (mano_misaligned({grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans})) return MR_ERR_BADARG;
+    if (misaligned({grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans}, 3)) return MR_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);

@@ -237,7 +237,7 @@ extern "C" int mr_meshreg_post_forward(const float* verts_mm, const float* joint
         return MR_ERR_BADARG;
     const int n = max(num_hand_verts + num_joints, num_obj_verts);
     if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(post_forward_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch_size), dim3(256), 0,
+    hipLaunchKernelGGL(post_forward_kernel, dim3(blocks1d(n), (unsigned)batch_size), dim3(256), 0,
                        (hipStream_t)stream, p, handverts3d, joints3d, joints2d, objverts3d, objverts2d);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -264,7 +264,7 @@ extern "C" int mr_meshreg_post_backward(const float* verts_mm, const float* join
     if (e != hipSuccess) return (int)e;
     const int n = max(num_hand_verts + num_joints, num_obj_verts);
     if (n > 0) {
-        hipLaunchKernelGGL(post_backward_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch_size), dim3(256), 0, s, p,
+        hipLaunchKernelGGL(post_backward_kernel, dim3(blocks1d(n), (unsigned)batch_size), dim3(256), 0, s, p,
                            grad_handverts3d, grad_joints3d, grad_joints2d, grad_objverts3d, grad_objverts2d,
                            grad_verts_mm, grad_joints_mm, workspace);
         MR_CHECK_LAUNCH();

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/meshraster_hip.h"
+#include "host_layout.hpp"
 
 #define MR_WAVE 64
 
@@ -18,6 +19,21 @@
     } while (0)
 
 namespace mr {
+
+// base + a carved offset, typed
+template <typename T>
+static inline T* at_offset(void* base, int64_t off) { return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + (uintptr_t)off); }
+
+// The 1-D launch: one thread per item in workgroups of 256.  Nothing to do for n <= 0; a grid past the limit is refused.
+static inline unsigned blocks1d(int64_t n) { return (unsigned)((n + 255) / 256); }
+template <typename K, typename... A>
+static int launch1d(K kernel, int64_t n, hipStream_t s, A... args) {
+    if (n <= 0) return MR_OK;
+    if (!grid_ok((n + 255) / 256)) return MR_ERR_BADARG;
+    hipLaunchKernelGGL(kernel, dim3(blocks1d(n)), dim3(256), 0, s, args...);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
 
 // Element types of an image batch (MR_DTYPE_*): float, bf16 as its bit pattern, uint8_t.  bf16 -> fp32 is exact; fp32 -> bf16
 // rounds to nearest-even (NaN -> the quiet NaN 0x7fc0), which is what torch's cast does.
@@ -30,6 +46,7 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float v) {
 }
 static inline bool image_dtype_ok(int d) { return d == MR_DTYPE_F32 || d == MR_DTYPE_BF16; }
 static inline bool mask_dtype_ok(int d) { return d == MR_DTYPE_F32 || d == MR_DTYPE_U8; }
+static inline bool criterion_ok(int c) { return c == MR_CRITERION_L1 || c == MR_CRITERION_L2; }
 
 // Pixel-space bounding box of a face (inclusive); empty when x0 > x1.
 struct __attribute__((aligned(8))) FaceBox {
@@ -454,9 +471,9 @@ struct ScatterWork {
     int* n_cov;
     unsigned short* cov;
 };
-__host__ __device__ inline int64_t scatter_work_cov_offset(int images) { return ((int64_t)images * 4 + 255) & ~(int64_t)255; }
+__host__ __device__ inline int64_t scatter_work_cov_offset(int images) { return round_up((int64_t)images * 4); }
 __host__ __device__ inline int64_t scatter_work_bytes(int images, int tiles) {
-    return scatter_work_cov_offset(images) + (((int64_t)images * tiles * 2 + 255) & ~(int64_t)255);
+    return scatter_work_cov_offset(images) + round_up((int64_t)images * tiles * 2);
 }
 __host__ __device__ inline ScatterWork scatter_work_at(void* buf, int images) {
     ScatterWork w;

@@ -16,8 +16,6 @@
 
 namespace mr {
 
-static inline int64_t ps_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 // where everything sits inside the two buffers (byte offsets, 256-byte aligned)
 struct PairStepLayout {
     // scratch
@@ -33,7 +31,7 @@ static int pair_step_layout(const MrPairStep& a, PairStepLayout& L) {
     if (a.batch_size < 0 || a.num_verts_a < 0 || a.num_verts_b <= 0 || a.num_hand_faces < 0 || a.num_obj_faces < 0 ||
         a.image_size <= 0 || a.height <= 0 || a.width < 2 || a.height > a.image_size || a.width > a.image_size ||
         (a.jitter_channels != 1 && a.jitter_channels != 3) || a.batch_size > (1 << 20) ||
-        (a.criterion != MR_CRITERION_L1 && a.criterion != MR_CRITERION_L2))
+        !criterion_ok(a.criterion))
         return MR_ERR_BADARG;
     // the image batch's element types ride in `reserved`: image dtype in bits 0-7, mask dtype in bits 8-15, zero = fp32 / fp32
     const int idt = a.reserved & 0xff, mdt = (a.reserved >> 8) & 0xff;
@@ -53,19 +51,19 @@ static int pair_step_layout(const MrPairStep& a, PairStepLayout& L) {
     L.pair_work_bytes = mr_pair_consist_tiles_workspace_bytes(a.batch_size, (int)is);
     L.scatter_work_bytes = mr_flow_pair_scatter_work_bytes(a.batch_size, (int)is);
     if (L.render_work_bytes < 0 || L.pair_work_bytes < 0 || L.scatter_work_bytes < 0) return MR_ERR_BADARG;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += ps_align(bytes > 16 ? bytes : 16); return at; };
+    Carve c;
+    auto take = [&](int64_t bytes) { return c.take(bytes, 256, 16); };  // (an empty region still gets a slot of its own)
     L.ndc = take(B2 * V * 12); L.cols = take(B2 * V * 12); L.faces2 = take(B2 * F0 * 12);
     L.rgb = take(B2 * 3 * px * 4); L.alpha = take(B2 * px * 4); L.mask = take(B2 * px * 4); L.occl = take(B2 * px * 4);
     L.rec = take(B2 * px * 16);  // (round 6: the render's 16-byte pixel records; the planes above serve MR_PAIR_STEP_SEPARATE_LAUNCHES)
     L.render_work = take(L.render_work_bytes); L.pair_work = take(L.pair_work_bytes);
-    L.scratch_total = o;
-    o = 0;
+    L.scratch_total = c.total();
+    c = Carve{};
     const int64_t tiles = ((is + 7) / 8) * ((is + 31) / 32);
     L.fim = take(B2 * px * 4); L.tile_hit = take(B2 * tiles * 4); L.wmap = take(B2 * px * 12); L.vid = take(B2 * px * 12);
     L.unit_grad = take(B2 * (int64_t)a.height * a.width * 8); L.unit_max = take(B2 * 4); L.sums = take((int64_t)a.batch_size * 16);
     L.scatter_work = take(L.scatter_work_bytes); L.grad_buf = take(B2 * V * 12);
-    L.saved_total = o;
+    L.saved_total = c.total();
     return MR_OK;
 }
 
@@ -114,7 +112,7 @@ extern "C" int mr_pair_step_forward(const MrPairStep* step, mr_stream_t stream) 
     if (!a.verts1a || !a.verts1b || !a.verts2a || !a.verts2b || !a.K1 || !a.K2 || !a.R || !a.t || !a.dist_coeffs || !a.hand_faces ||
         !a.obj_faces || !a.background || !a.image_ref || !a.image || !a.jitter_ref || !a.jitter || !a.scratch || !a.saved ||
         !a.flows || !a.losses || a.scratch_bytes < L.scratch_total || a.saved_bytes < L.saved_total ||
-        ((uintptr_t)a.scratch & 15) || ((uintptr_t)a.saved & 15) || !(a.eps >= 1e-6f))
+        misaligned({a.scratch, a.saved}, 15) || !(a.eps >= 1e-6f))
         return MR_ERR_BADARG;
     char* sc = (char*)a.scratch;
     char* sv = (char*)a.saved;

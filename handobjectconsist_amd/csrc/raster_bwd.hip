@@ -2199,16 +2199,6 @@ __global__ void __launch_bounds__(PS_T) strip_gather_kernel(PixelMapParams p, co
 }
 
 
-template <typename K, typename... A>
-static int launch1d(K kernel, int64_t n, hipStream_t s, A... args) {
-    if (n <= 0) return MR_OK;
-    const int64_t blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, args...);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
-}
-
 // backward workspace: per-face "owns a pixel" flags | owner count | per-image counts and line ranges | owner list |
 // per-image owner records (the gather needs the flags, the count and the list)
 struct OwnerList {
@@ -2217,21 +2207,19 @@ struct OwnerList {
     unsigned* img_count;  // [B] owners per image, then [B][4] their line ranges (behind the counter: one memset clears all)
     uint32_t* list;
     float4* img_recs;     // [B][F][2] the front-facing owners image by image (compact_owners_kernel)
-    size_t owns_bytes, clear_bytes;
+    int64_t clear_bytes;  // flags, counter and counts: what a call clears
+    int64_t bytes;
 };
-static int64_t round256(int64_t n) { return (n + 255) & ~255LL; }
-static int64_t owner_list_bytes(int B, int F) {
-    return round256((int64_t)B * F) + 256 + round256(20LL * B) + round256((int64_t)B * F * 4) + round256((int64_t)B * F * 32);
-}
 static OwnerList owner_list(void* workspace, int B, int F) {
+    Carve c;
     OwnerList o;
-    o.owns = (uint8_t*)workspace;
-    o.owns_bytes = (size_t)round256((int64_t)B * F);
-    o.counter = (unsigned*)(o.owns + o.owns_bytes);
-    o.img_count = (unsigned*)(o.owns + o.owns_bytes + 256);
-    o.clear_bytes = o.owns_bytes + 256 + (size_t)round256(20LL * B);
-    o.list = (uint32_t*)(o.owns + o.clear_bytes);
-    o.img_recs = (float4*)(o.owns + o.clear_bytes + round256((int64_t)B * F * 4));
+    o.owns = at_offset<uint8_t>(workspace, c.take((int64_t)B * F));
+    o.counter = at_offset<unsigned>(workspace, c.take(256));
+    o.img_count = at_offset<unsigned>(workspace, c.take(20LL * B));
+    o.clear_bytes = c.total();
+    o.list = at_offset<uint32_t>(workspace, c.take((int64_t)B * F * 4));
+    o.img_recs = at_offset<float4>(workspace, c.take((int64_t)B * F * 32));
+    o.bytes = c.total();
     return o;
 }
 // flags -> lists (+ zero rows); the workspace's flags and counts must have been cleared (ol.clear_bytes) and marked
@@ -2239,7 +2227,7 @@ static int launch_compact(const PixelMapParams& q, const OwnerList& ol, bool per
                           unsigned* strip_w = nullptr, int strip_l = 1, int strips_axis = 0) {
     const int chunks = (q.F + CO_TPB * CO_PER - 1) / (CO_TPB * CO_PER);
     const int64_t blocks = (int64_t)q.B * chunks;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (!grid_ok(blocks)) return MR_ERR_BADARG;
     if (blocks == 0) return MR_OK;
     hipLaunchKernelGGL(compact_owners_kernel, dim3((unsigned)blocks), dim3(CO_TPB), 0, s, q, (const uint8_t*)ol.owns, ol.counter,
                        ol.list, per_image ? ol.img_count : (unsigned*)nullptr, per_image ? ol.img_recs : (float4*)nullptr, chunks,
@@ -2254,30 +2242,27 @@ struct StripLists {
     unsigned* lists;
     unsigned* counts;
     int strips_axis, cap;
-    int64_t n_weights;
+    int64_t n_weights, bytes;
 };
 static int strip_lines(int is);
-static int64_t strip_list_bytes(int B, int is) {
-    const int L = strip_lines(is);
-    if (L == 0) return 0;
-    const int64_t sa = (is + L - 1) / L, S = 2 * sa, cap = (int64_t)((B + 7) / 8) * S;
-    return round256((int64_t)B * S * 4) + round256(8 * cap * 4) + 256;
-}
 static StripLists strip_lists(void* workspace, int B, int F, int is) {
     StripLists sl{};
     const int L = strip_lines(is);
+    if (L == 0) return sl;  // (a raster whose lines do not fit LDS: no strips, no bytes)
     sl.strips_axis = (is + L - 1) / L;
     const int64_t S = 2LL * sl.strips_axis;
     sl.cap = (int)(((B + 7) / 8) * S);
     sl.n_weights = (int64_t)B * S;
-    char* base = (char*)workspace + owner_list_bytes(B, F);
-    sl.weights = (unsigned*)base;
-    sl.lists = (unsigned*)(base + round256(sl.n_weights * 4));
-    sl.counts = (unsigned*)(base + round256(sl.n_weights * 4) + round256(8LL * sl.cap * 4));
+    void* base = at_offset<char>(workspace, owner_list(workspace, B, F).bytes);
+    Carve c;
+    sl.weights = at_offset<unsigned>(base, c.take(sl.n_weights * 4));
+    sl.lists = at_offset<unsigned>(base, c.take(8LL * sl.cap * 4));
+    sl.counts = at_offset<unsigned>(base, c.take(256));
+    sl.bytes = c.total();
     return sl;
 }
 static int64_t pixel_map_workspace_bytes(int B, int F, int is) {
-    return owner_list_bytes(B, F) + strip_list_bytes(B, is);
+    return owner_list(nullptr, B, F).bytes + strip_lists(nullptr, B, F, is).bytes;
 }
 
 // kernel D by strips needs the workspace, a raster whose lines fit LDS and 24-bit owner numbers
@@ -2328,12 +2313,12 @@ static int launch_pixel_map(const PixelMapParams& p, void* workspace, int64_t wo
                        2 * strips_axis, sl.cap);
     MR_CHECK_LAUNCH();
     const int64_t grid = 8LL * sl.cap;
-    if (grid > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (!grid_ok(grid)) return MR_ERR_BADARG;
     const size_t lds = (size_t)strip_lds_bytes(p.is, strip_l);
     if (fused && (fused->tex || fused->depth)) {
         const int64_t gblocks = (fused->threads + PS_T - 1) / PS_T;
         const int64_t ggroups = (gblocks + 7) / 8, total = (ggroups + sl.cap) * 8;
-        if (total <= 0x7fffffffLL && ggroups <= 0x0fffffffLL) {
+        if (grid_ok(total) && ggroups <= 0x0fffffffLL) {
             const GatherParams g = fused->g;
 #define MR_SG_LAUNCH(L_, T_, D_)                                                                                          \
             hipLaunchKernelGGL((strip_gather_kernel<IMG, L_, T_, D_>), dim3((unsigned)total), dim3(PS_T), lds, s, p,      \
@@ -2368,7 +2353,7 @@ using namespace mr;
 
 extern "C" int64_t mr_render_backward_list_workspace_bytes(int batch_size, int num_faces) {
     if (batch_size < 0 || num_faces < 0) return MR_ERR_BADARG;
-    return owner_list_bytes(batch_size, num_faces);
+    return owner_list(nullptr, batch_size, num_faces).bytes;
 }
 
 extern "C" int64_t mr_render_backward_workspace_bytes(int batch_size, int num_faces, int image_size) {
@@ -2459,7 +2444,7 @@ extern "C" int mr_render_backward(const float* faces, const float* textures,
     // walks only those: the others -- four fifths of a hand + object mesh -- get their zero rows when the list is built
     const bool strips_d = strips_apply(batch_size, num_faces, image_size, workspace, workspace_bytes, flags);
     const bool use_list = want_d ? strips_d
-                                 : (workspace && workspace_bytes >= owner_list_bytes(batch_size, num_faces) &&
+                                 : (workspace && workspace_bytes >= owner_list(nullptr, batch_size, num_faces).bytes &&
                                     !(flags & MR_FLAG_REFERENCE_ALGO) && nfaces <= 0xffffffffLL);
     // the E / F gather of the faces that own a pixel (or of all of them without a list)
     GatherParams g{};
@@ -2537,7 +2522,7 @@ extern "C" int mr_render_vc_backward(const float* verts, const int32_t* faces_id
     if (table_bytes <= SV_MAX_TABLE_BYTES && !(flags & MR_FLAG_FORCE_GATHER)) {
         ScatterVCParams sp{g, weight_map, depth_img, (image_size + SV_W - 1) / SV_W, (image_size + SV_H - 1) / SV_H};
         const int64_t blocks = (int64_t)batch_size * sp.rx_n * sp.ry_n;
-        if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
+        if (!grid_ok(blocks)) return MR_ERR_BADARG;
         const bool stored = weight_map && depth_img;
         hipLaunchKernelGGL(stored ? scatter_vc_kernel<true> : scatter_vc_kernel<false>, dim3((unsigned)blocks),
                            dim3(SV_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
@@ -2580,7 +2565,7 @@ static int launch_scatter_tiles(ScatterTilesParams& sp, int flags, bool pairs, b
     sp.groups = ST_G;
     while (pairs && sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
     const int64_t blocks = (int64_t)g.B * sp.groups;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (!grid_ok(blocks)) return MR_ERR_BADARG;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -2619,7 +2604,7 @@ extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, c
                                                 int width, float* grad_vcolors, int batch_size, int num_verts, int num_faces,
                                                 int fill_back, int image_size, float eps, float pair_thresh, int flags,
                                                 int texel_layout, mr_stream_t stream, int criterion) {
-    if (criterion != MR_CRITERION_L1 && criterion != MR_CRITERION_L2) return MR_ERR_BADARG;
+    if (!criterion_ok(criterion)) return MR_ERR_BADARG;
     ScatterTilesParams sp{};
     sp.g = GatherVCParams{nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces,
                           fill_back, image_size, eps, texel_layout};

@@ -1444,8 +1444,6 @@ static int bin_parts(int B, int F, int cus, int per_cu = 2) {
     return k;
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static WorkLayout work_layout(int B, int F, int is) {
     WorkLayout w;
     const int tiles_x = (is + TILE_W - 1) / TILE_W, tiles_y = (is + TILE_H - 1) / TILE_H;
@@ -1453,19 +1451,21 @@ static WorkLayout work_layout(int B, int F, int is) {
     w.ysh = 0;
     while ((int64_t)tiles_x * ((tiles_y + (1 << w.ysh) - 1) >> w.ysh) > MAX_BINS) w.ysh++;
     w.nby = (tiles_y + (1 << w.ysh) - 1) >> w.ysh;
-    w.off_bins = align256((size_t)B * sizeof(ImageHdr));
-    w.off_boxes = w.off_bins + align256((size_t)B * w.nbx * w.nby * sizeof(BinHdr));
-    w.off_recs = w.off_boxes + align256((size_t)B * F * sizeof(FaceBox));
-    w.off_rverts = w.off_recs + align256((size_t)B * REC_CAP * F * sizeof(FaceRec));
-    w.off_tlist = w.off_rverts + align256((size_t)B * F * sizeof(RecVerts));  // (VC needs F / 2 of it with fill-back)
+    Carve c;
+    c.take((size_t)B * sizeof(ImageHdr));  // the image headers, at the base
+    w.off_bins = c.take((size_t)B * w.nbx * w.nby * sizeof(BinHdr));
+    w.off_boxes = c.take((size_t)B * F * sizeof(FaceBox));
+    w.off_recs = c.take((size_t)B * REC_CAP * F * sizeof(FaceRec));
+    w.off_rverts = c.take((size_t)B * F * sizeof(RecVerts));  // (VC needs F / 2 of it with fill-back)
     // (the images' arrival counters sit right behind the list header: ONE region for the caller of MR_FLAG_TILE_LIST_CLEARED to clear)
-    w.off_arrive = w.off_tlist + align256(sizeof(TileList));
-    w.off_tile_ids = w.off_arrive + align256((size_t)B * ARRIVE_STRIDE * sizeof(unsigned));
-    w.off_bg = w.off_tile_ids + align256((size_t)2 * B * tiles_x * tiles_y * sizeof(uint4));  // heavy part | light part
-    w.off_part_cnt = w.off_bg + align256((size_t)B * tiles_x * tiles_y * sizeof(uint32_t));  // dense listed launches: ids of the tiles off the list
+    w.off_tlist = c.take(sizeof(TileList));
+    w.off_arrive = c.take((size_t)B * ARRIVE_STRIDE * sizeof(unsigned));
+    w.off_tile_ids = c.take((size_t)2 * B * tiles_x * tiles_y * sizeof(uint4));  // heavy part | light part
+    w.off_bg = c.take((size_t)B * tiles_x * tiles_y * sizeof(uint32_t));  // dense listed launches: ids of the tiles off the list
     // (sized for a 256-CU device, the most launch_bins assumes: the layout must not depend on the device at hand)
     w.parts = bin_parts(B, F, MAX_PART_CUS);
-    w.total = w.off_part_cnt + (w.parts > 1 ? align256((size_t)B * w.parts * ((w.nbx * w.nby + 4 + 31) & ~31) * sizeof(int)) : 0);
+    w.off_part_cnt = c.take(w.parts > 1 ? (size_t)B * w.parts * ((w.nbx * w.nby + 4 + 31) & ~31) * sizeof(int) : 0);
+    w.total = c.total();
     return w;
 }
 
@@ -1488,7 +1488,7 @@ static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int 
         fp.bg_ids = bp.bg_ids;
         tile_hit = (uint8_t*)bp.bg_ids;  // (not written in this mode: any non-null value asks for the list)
     }
-    if (tile_hit && w.ysh == 0 && (int64_t)B * w.nbx * w.nby <= 0x7fffffffLL) {
+    if (tile_hit && w.ysh == 0 && grid_ok((int64_t)B * w.nbx * w.nby)) {
         bp.tlist = (TileList*)(base + w.off_tlist);
         bp.tile_ids = (uint4*)(base + w.off_tile_ids);
         bp.tile_hit = tile_hit;
@@ -1554,7 +1554,7 @@ static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int 
     if (fused_records_ok) {
         // nothing: the per-face pass runs inside the binning kernel
     } else if (bp.F0 > 0) {
-        hipLaunchKernelGGL((face_records_kernel<VC>), dim3((unsigned)((bp.F0 + 255) / 256), (unsigned)B), dim3(256), 0, s,
+        hipLaunchKernelGGL((face_records_kernel<VC>), dim3(blocks1d(bp.F0), (unsigned)B), dim3(256), 0, s,
                            bp);
         MR_CHECK_LAUNCH();
     } else if (bp.tlist) {
@@ -1610,7 +1610,7 @@ static int launch_tiles(FwdParams& p, hipStream_t s, int64_t tile_bound = 0) {
     p.tiles_y = (p.is + TILE_H - 1) / TILE_H;
     int64_t nblocks = (int64_t)p.B * p.tiles_x * p.tiles_y;
     if (nblocks == 0) return MR_OK;
-    if (nblocks > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (!grid_ok(nblocks)) return MR_ERR_BADARG;
     if (p.tlist) {
         // Listed launch: `bound` workgroups take one list entry each; whatever the list holds beyond the caller's guess
         // is walked afterwards by the same workgroups (raster_overflow_tiles).
@@ -1648,7 +1648,7 @@ static bool dense_list_ok(int B, int F, int is, const float* face_inv_map, int f
     if ((flags & (MR_FLAG_REFERENCE_ALGO | MR_FLAG_TILE_PER_WORKGROUP)) || face_inv_map) return false;
     if ((is % TILE_W) != 0 || (is % TILE_H) != 0) return false;
     const WorkLayout w = work_layout(B, F, is);
-    return w.ysh == 0 && (int64_t)B * w.nbx * w.nby <= 0x7fffffffLL;
+    return w.ysh == 0 && grid_ok((int64_t)B * w.nbx * w.nby);
 }
 
 // ... over the tile list: a quarter of the screen as the grid (a longer list is walked in rounds, surplus workgroups leave
@@ -1662,12 +1662,7 @@ static int launch_dense_listed(FwdParams& p, hipStream_t s) {
 extern "C" int mr_selftest_division(const float* a, const float* b, float* refined, float* plain, int64_t n,
                                     mr_stream_t stream) {
     if (n < 0 || (n > 0 && (!a || !b || !refined || !plain))) return MR_ERR_BADARG;
-    if (n == 0) return MR_OK;
-    const int64_t blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BADARG;
-    hipLaunchKernelGGL(selftest_division_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, refined, plain, n);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(selftest_division_kernel, n, (hipStream_t)stream, a, b, refined, plain, n);
 }
 
 extern "C" int64_t mr_render_workspace_bytes(int batch_size, int num_faces, int image_size) {
@@ -1687,7 +1682,7 @@ extern "C" int mr_render_tile_list(const void* workspace, int batch_size, int nu
     if (batch_size < 0 || num_faces < 0 || image_size <= 0 || image_size > 16384) return MR_ERR_BADARG;
     const WorkLayout w = work_layout(batch_size, num_faces, image_size);
     // (a list is built when a bin is a tile and the global tile ids fit 31 bits: launch_bins)
-    if (w.ysh != 0 || (int64_t)batch_size * w.nbx * w.nby > 0x7fffffffLL) return MR_ERR_NOTIMPL;
+    if (w.ysh != 0 || !grid_ok((int64_t)batch_size * w.nbx * w.nby)) return MR_ERR_NOTIMPL;
     const char* base = (const char*)workspace;
     *list_header = base + w.off_tlist;
     *list_entries = base + w.off_tile_ids;
@@ -1738,13 +1733,8 @@ extern "C" int mr_forward_texture_sampling(const float* faces, const float* text
         return MR_ERR_BADARG;
     if (batch_size < 0 || num_faces < 0 || image_size <= 0 || texture_size < 2) return MR_ERR_BADARG;
     const int64_t npx = (int64_t)batch_size * image_size * image_size;
-    if (npx == 0) return MR_OK;
-    hipLaunchKernelGGL(texture_sampling_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, faces, textures, face_index_map, weight_map, depth_map,
-                       rgb_map, sampling_index_map, sampling_weight_map, npx, num_faces, image_size,
-                       texture_size, eps);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(texture_sampling_kernel, npx, (hipStream_t)stream, faces, textures, face_index_map, weight_map, depth_map,
+                    rgb_map, sampling_index_map, sampling_weight_map, npx, num_faces, image_size, texture_size, eps);
 }
 
 extern "C" int mr_render_forward(const float* faces, const float* textures, const float* background,
@@ -1787,7 +1777,7 @@ extern "C" int mr_render_forward(const float* faces, const float* textures, cons
         unsigned long long* keys = nullptr;
         hipError_t e = hipMallocAsync((void**)&keys, (size_t)npx * 8 + 256, s);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(raster_brute_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, faces,
+        hipLaunchKernelGGL(raster_brute_kernel, dim3(blocks1d(npx)), dim3(256), 0, s, faces,
                            batch_size, num_faces, image_size, near_, far_, keys);
         rc = (int)hipGetLastError();
         p.keys = keys;
@@ -1805,11 +1795,8 @@ extern "C" int mr_face_inv_map(const float* faces, const int32_t* face_index_map
     if (!faces || !face_index_map || !face_inv_map) return MR_ERR_BADARG;
     if (batch_size < 0 || num_faces < 0 || image_size <= 0) return MR_ERR_BADARG;
     const int64_t npx = (int64_t)batch_size * image_size * image_size;
-    if (npx == 0) return MR_OK;
-    hipLaunchKernelGGL(face_inv_map_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, faces, face_index_map, face_inv_map, npx, num_faces, image_size);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(face_inv_map_kernel, npx, (hipStream_t)stream, faces, face_index_map, face_inv_map, npx, num_faces,
+                    image_size);
 }
 
 extern "C" int mr_render_vc_forward(const float* verts, const int32_t* faces_idx, const float* vcolors,
@@ -1878,7 +1865,7 @@ int mr::launch_flow_render(const FlowRenderArgs& a, hipStream_t s) {
     if (a.batch_size < 0 || a.num_faces < 0 || a.num_verts < 0 || a.image_size <= 0 || a.image_size > 16384) return MR_ERR_BADARG;
     if (((!a.verts || !a.faces_idx || !a.vcolors) && a.num_faces > 0) || !a.face_index_map || !a.workspace) return MR_ERR_BADARG;
     if (a.vertex_id_map && !a.weight_map) return MR_ERR_BADARG;
-    if (a.records ? (a.rgb_img || a.alpha_img || a.mask_img || ((uintptr_t)a.records & 15) || !(a.flags & MR_FLAG_SPARSE_TILES) || a.tile_bound == 0)
+    if (a.records ? (a.rgb_img || a.alpha_img || a.mask_img || misaligned({a.records}, 15) || !(a.flags & MR_FLAG_SPARSE_TILES) || a.tile_bound == 0)
                   : (!a.rgb_img || !a.alpha_img || !a.mask_img))
         return MR_ERR_BADARG;
     if (!a.background || !(a.eps >= 1e-6f)) return MR_ERR_BADARG;

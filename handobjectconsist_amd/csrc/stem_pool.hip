@@ -477,7 +477,7 @@ static inline int stem_layout(int channels_last) { return channels_last == 2 ? 2
 
 // the arg-max codes (layout 1: uchar4 accesses) or the record buffer (layout 2: float4 accesses) must be there and aligned
 static inline bool stem_records_ok(const unsigned char* argmax, int layout) {
-    return argmax && (reinterpret_cast<uintptr_t>(argmax) & (uintptr_t)(layout == 2 ? 15 : 3)) == 0;
+    return argmax && !misaligned({argmax}, layout == 2 ? 15 : 3);
 }
 
 template <bool BACKWARD>

@@ -309,8 +309,7 @@ extern "C" int mr_stem_conv_wrw(const float* grad_y, const float* grad_y2, const
     if (!workspace || workspace_bytes < mr_stem_conv_wrw_workspace_bytes(batch_size, channels, in_height, in_width)) return MR_ERR_BADARG;
     // float4 / uchar4 accesses: the record buffer and the gradients on 16 bytes (the code plane follows the d plane, whose
     // size is a multiple of 16 bytes), the workspace and the output on 4
-    const auto mis = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & m) != 0; };
-    if (mis(records, 15) || mis(grad_y, 15) || mis(grad_y2, 15) || mis(image, 3) || mis(workspace, 3) || mis(grad_conv_weight, 3))
+    if (misaligned({records, grad_y, grad_y2}, 15) || misaligned({image, workspace, grad_conv_weight}, 3))
         return MR_ERR_BADARG;
     p.grad_y = grad_y; p.grad_y2 = grad_y2;
     p.rec_d = reinterpret_cast<const float*>(records);

@@ -128,7 +128,7 @@ using namespace mr;
 // the pair's set-up launch from its argument blocks (raster_fwd.hip's launch_bins: where the binning pass cannot take the
 // vertex stage in); no clearing
 int mr::mr_launch_pair_prologue(const mr::PairPrologue& pro, hipStream_t s) {
-    const int vb = (pro.v.V + 255) / 256, fb = ((pro.f.Fh + pro.f.Fo) * 3 + 255) / 256;
+    const int vb = (int)blocks1d(pro.v.V), fb = (int)blocks1d((pro.f.Fh + pro.f.Fo) * 3);
     if (pro.v.B <= 0 || pro.v.B > 65535 || !pro.v.ndc1 || !pro.v.ndc2 || !pro.v.cols12 || !pro.v.cols21) return MR_ERR_BADARG;
     hipLaunchKernelGGL(pair_prologue_kernel, dim3((unsigned)(vb + fb), (unsigned)pro.v.B), dim3(256), 0, s, pro.v, pro.f, vb,
                        (uint4*)nullptr, 0);
@@ -147,7 +147,7 @@ extern "C" int mr_flow_vertices_forward(const float* verts1, const float* verts2
     if (batch_size > 65535) return MR_ERR_BADARG;
     VertexStageParams p{verts1, verts2, nullptr, nullptr, num_verts, K1, K2, R, t, dist_coeffs, cam_batched ? 1 : 0, orig_size,
                         ndc1, ndc2, cols12, cols21, batch_size, num_verts};
-    hipLaunchKernelGGL(flow_vertices_forward_kernel, dim3((unsigned)((num_verts + 255) / 256), (unsigned)batch_size),
+    hipLaunchKernelGGL(flow_vertices_forward_kernel, dim3(blocks1d(num_verts), (unsigned)batch_size),
                        dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -160,7 +160,7 @@ extern "C" int mr_flow_vertices_backward(const float* verts1, const float* verts
     if (batch_size == 0 || num_verts == 0 || (!grad_verts1 && !grad_verts2)) return MR_OK;
     if (!verts1 || !verts2 || !K1 || !K2) return MR_ERR_BADARG;
     if (batch_size > 65535) return MR_ERR_BADARG;
-    hipLaunchKernelGGL(flow_vertices_backward_kernel, dim3((unsigned)((num_verts + 255) / 256), (unsigned)batch_size),
+    hipLaunchKernelGGL(flow_vertices_backward_kernel, dim3(blocks1d(num_verts), (unsigned)batch_size),
                        dim3(256), 0, (hipStream_t)stream, verts1, verts2, K1, K2, grad_cols12, grad_cols21, grad_verts1,
                        grad_verts2, batch_size, num_verts, (const float*)nullptr, (const float*)nullptr, (float*)nullptr,
                        (float*)nullptr, num_verts);
@@ -182,7 +182,7 @@ extern "C" int mr_flow_vertices_parts_forward(const float* verts1a, const float*
     const int V = num_verts_a + num_verts_b;
     VertexStageParams p{verts1a, verts2a, verts1b, verts2b, num_verts_a, K1, K2, R, t, dist_coeffs, cam_batched ? 1 : 0,
                         orig_size, ndc1, ndc2, cols12, cols21, batch_size, V};
-    hipLaunchKernelGGL(flow_vertices_forward_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)batch_size), dim3(256), 0,
+    hipLaunchKernelGGL(flow_vertices_forward_kernel, dim3(blocks1d(V), (unsigned)batch_size), dim3(256), 0,
                        (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -198,7 +198,7 @@ extern "C" int mr_flow_vertices_parts_backward(const float* verts1a, const float
     if (!verts1b || !verts2b || ((!verts1a || !verts2a) && num_verts_a > 0) || !K1 || !K2) return MR_ERR_BADARG;
     if (batch_size > 65535) return MR_ERR_BADARG;
     const int V = num_verts_a + num_verts_b;
-    hipLaunchKernelGGL(flow_vertices_backward_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)batch_size), dim3(256), 0,
+    hipLaunchKernelGGL(flow_vertices_backward_kernel, dim3(blocks1d(V), (unsigned)batch_size), dim3(256), 0,
                        (hipStream_t)stream, verts1a, verts2a, K1, K2, grad_cols12, grad_cols21, grad_verts1a, grad_verts2a,
                        batch_size, V, verts1b, verts2b, grad_verts1b, grad_verts2b, num_verts_a);
     MR_CHECK_LAUNCH();
@@ -215,7 +215,7 @@ extern "C" int mr_stack_pair_faces(const int64_t* hand_faces, int hand_batched, 
     if (batch_size > 65535) return MR_ERR_BADARG;
     const StackFacesParams q{hand_faces, hand_batched ? (int64_t)num_hand_faces * 3 : (int64_t)0, obj_faces, vertex_offset, faces_out,
                              batch_size, num_hand_faces, num_obj_faces};
-    hipLaunchKernelGGL(stack_pair_faces_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch_size), dim3(256), 0,
+    hipLaunchKernelGGL(stack_pair_faces_kernel, dim3(blocks1d(n), (unsigned)batch_size), dim3(256), 0,
                        (hipStream_t)stream, q);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -242,8 +242,8 @@ extern "C" int mr_flow_pair_prologue_parts(const float* verts1a, const float* ve
                               orig_size, ndc1, ndc2, cols12, cols21, batch_size, V};
     const StackFacesParams q{hand_faces, hand_batched ? (int64_t)num_hand_faces * 3 : (int64_t)0, obj_faces, num_verts_a, faces_out,
                              batch_size, num_hand_faces, num_obj_faces};
-    const int vb = (V + 255) / 256, fb = (n + 255) / 256;
-    if (((uintptr_t)clear16 & 15u) != 0 || clear_bytes < 0 || (clear_bytes & 15) != 0 || clear_bytes > (1 << 24)) return MR_ERR_BADARG;
+    const int vb = (int)blocks1d(V), fb = (int)blocks1d(n);
+    if (misaligned({clear16}, 15) || clear_bytes < 0 || (clear_bytes & 15) != 0 || clear_bytes > (1 << 24)) return MR_ERR_BADARG;
     hipLaunchKernelGGL(pair_prologue_kernel, dim3((unsigned)(vb + fb), (unsigned)batch_size), dim3(256), 0, (hipStream_t)stream,
                        p, q, vb, clear_bytes > 0 ? (uint4*)clear16 : nullptr, (int)(clear_bytes / 16));
     MR_CHECK_LAUNCH();

@@ -1041,8 +1041,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))
 
 using namespace mr;
 
-static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 extern "C" int mr_warp_forward(const float* x, const float* flow, float* out, float* mask, int batch_size,
                                int channels, int height, int width, float thresh, int mode,
                                mr_stream_t stream) {
@@ -1050,11 +1048,9 @@ extern "C" int mr_warp_forward(const float* x, const float* flow, float* out, fl
     if (batch_size < 0 || channels < 0 || height <= 0 || width <= 0 || (mode != 0 && mode != 1))
         return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * height * width;
-    if (n == 0 || channels == 0) return MR_OK;
-    hipLaunchKernelGGL(warp_forward_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, x, flow,
-                       out, mask, batch_size, channels, height, width, thresh, mode);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    if (channels == 0) return MR_OK;
+    return launch1d(warp_forward_kernel, n, (hipStream_t)stream, x, flow, out, mask, batch_size, channels, height, width,
+                    thresh, mode);
 }
 
 extern "C" int mr_warp_backward(const float* x, const float* flow, const float* grad_out, float* grad_x,
@@ -1064,11 +1060,9 @@ extern "C" int mr_warp_backward(const float* x, const float* flow, const float* 
     if (batch_size < 0 || channels < 0 || height <= 0 || width <= 0 || (mode != 0 && mode != 1))
         return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * height * width;
-    if (n == 0 || (!grad_x && !grad_flow)) return MR_OK;
-    hipLaunchKernelGGL(warp_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, x, flow,
-                       grad_out, grad_x, grad_flow, batch_size, channels, height, width, thresh, mode);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    if (!grad_x && !grad_flow) return MR_OK;
+    return launch1d(warp_backward_kernel, n, (hipStream_t)stream, x, flow, grad_out, grad_x, grad_flow, batch_size, channels,
+                    height, width, thresh, mode);
 }
 
 extern "C" int mr_occlusion_mask(const float* mask_flow1, const float* mask_flow2, const float* flow12,
@@ -1079,12 +1073,8 @@ extern "C" int mr_occlusion_mask(const float* mask_flow1, const float* mask_flow
     if (!mask_flow1 || !mask_flow2 || !flow12 || !flow21 || !occl1 || !occl2) return MR_ERR_BADARG;
     if (batch_size < 0 || height <= 0 || width <= 0 || flow_bstride < 2LL * height * width) return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * height * width;
-    if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(occlusion_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, mask_flow1,
-                       mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1, occl2, batch_size,
-                       height, width, distance_thresh, warp_thresh);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(occlusion_kernel, n, (hipStream_t)stream, mask_flow1, mask_flow2, flow12, flow21, flow_bstride,
+                    flow12_scale, flow21_scale, occl1, occl2, batch_size, height, width, distance_thresh, warp_thresh);
 }
 
 extern "C" int mr_occlusion_flow(const float* mask_flow1, const float* mask_flow2, const float* flow12,
@@ -1099,23 +1089,17 @@ extern "C" int mr_occlusion_flow(const float* mask_flow1, const float* mask_flow
     if (batch_size < 0 || height <= 0 || width <= 0 || flow_bstride < 2LL * height * width) return MR_ERR_BADARG;
     if (crop_height <= 0 || crop_width <= 0 || crop_height > height || crop_width > width) return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * height * width;
-    if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(occlusion_flow_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, mask_flow1,
-                       mask_flow2, flow12, flow21, flow_bstride, flow12_scale, flow21_scale, occl1, occl2, flow_out12,
-                       flow_out21, batch_size, height, width, crop_height, crop_width, distance_thresh, warp_thresh,
-                       tile_hit1, tile_hit2, (width + 31) / 32, (height + 7) / 8);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(occlusion_flow_kernel, n, (hipStream_t)stream, mask_flow1, mask_flow2, flow12, flow21, flow_bstride,
+                    flow12_scale, flow21_scale, occl1, occl2, flow_out12, flow_out21, batch_size, height, width, crop_height,
+                    crop_width, distance_thresh, warp_thresh, tile_hit1, tile_hit2, (width + 31) / 32, (height + 7) / 8);
 }
 
 extern "C" int64_t mr_pair_consist_workspace_bytes(int batch_size, int height, int width) {
     if (batch_size < 0 || height <= 0 || width <= 0) return MR_ERR_BADARG;
+    // ONE region at the base: four partial sums per 64 x 4 tile
     const int64_t nblk = (int64_t)((width + PT_W - 1) / PT_W) * ((height + PT_H - 1) / PT_H);
     return (int64_t)batch_size * nblk * 4 * (int64_t)sizeof(float);
 }
-
-// MR_CRITERION_* -> is it one the pair kernels are instantiated for
-static inline bool criterion_ok(int criterion) { return criterion == MR_CRITERION_L1 || criterion == MR_CRITERION_L2; }
 
 // What mr_pair_consist_forward_crit and _backward_crit share: the argument checks (`ptrs_ok`: the caller's own pointers and
 // workspace; every refusal is MR_ERR_BADARG, so their order does not show) and the tile arithmetic of the launch.
@@ -1132,7 +1116,7 @@ static int pair_consist_grid(bool ptrs_ok, int criterion, int jitter_channels, i
     if (width < 2 || (int64_t)height * width > (1LL << 29)) return MR_ERR_BADARG;  // row-pair taps, 32-bit byte offsets
     g.tiles_x = (width + PT_W - 1) / PT_W;
     g.nblk = g.tiles_x * ((height + PT_H - 1) / PT_H);
-    if ((int64_t)g.nblk * batch_size > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (!grid_ok((int64_t)g.nblk * batch_size)) return MR_ERR_BADARG;
     g.hit_tiles_x = (hit_image_size + 31) / 32;
     g.hit_stride = g.hit_tiles_x * ((hit_image_size + 7) / 8) * 4;
     return MR_OK;
@@ -1234,11 +1218,8 @@ extern "C" int mr_flow_mask(const float* alpha_img, const int32_t* face_index_ma
     if (!alpha_img || !mask || batch_size < 0 || image_size <= 0) return MR_ERR_BADARG;
     if (keep_lut && (!face_index_map || n_lut <= 0)) return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * image_size * image_size;
-    if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(flow_mask_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, alpha_img,
-                       face_index_map, keep_lut, n_lut, thresh, mask, n, image_size);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(flow_mask_kernel, n, (hipStream_t)stream, alpha_img, face_index_map, keep_lut, n_lut, thresh, mask, n,
+                    image_size);
 }
 
 extern "C" int mr_flow_finalize_forward(const float* rgb_img, const float* mask_pre, const float* mask_x,
@@ -1248,11 +1229,8 @@ extern "C" int mr_flow_finalize_forward(const float* rgb_img, const float* mask_
     if (batch_size < 0 || image_size <= 0 || height <= 0 || width <= 0 || height > image_size || width > image_size)
         return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * height * width;
-    if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(flow_finalize_forward_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, rgb_img,
-                       mask_pre, mask_x, occl, flow, batch_size, image_size, height, width);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(flow_finalize_forward_kernel, n, (hipStream_t)stream, rgb_img, mask_pre, mask_x, occl, flow, batch_size,
+                    image_size, height, width);
 }
 
 extern "C" int mr_flow_finalize_backward(const float* grad_flow, const float* mask_pre, const float* mask_x,
@@ -1262,11 +1240,8 @@ extern "C" int mr_flow_finalize_backward(const float* grad_flow, const float* ma
     if (batch_size < 0 || image_size <= 0 || height <= 0 || width <= 0 || height > image_size || width > image_size)
         return MR_ERR_BADARG;
     const int64_t n = (int64_t)batch_size * image_size * image_size;
-    if (n == 0) return MR_OK;
-    hipLaunchKernelGGL(flow_finalize_backward_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream,
-                       grad_flow, mask_pre, mask_x, occl, grad_rgb_img, batch_size, image_size, height, width);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return launch1d(flow_finalize_backward_kernel, n, (hipStream_t)stream, grad_flow, mask_pre, mask_x, occl, grad_rgb_img,
+                    batch_size, image_size, height, width);
 }
 
 
@@ -1290,7 +1265,7 @@ extern "C" int mr_occlusion_flow_tiles(const float* mask_flow1, const float* mas
     if (batch_size < 0 || image_size <= 0 || flow_bstride < 2LL * image_size * image_size) return MR_ERR_BADARG;
     if (crop_height <= 0 || crop_width <= 0 || crop_height > image_size || crop_width > image_size) return MR_ERR_BADARG;
     const int tiles_x = (image_size + 31) / 32, tiles_y = (image_size + 7) / 8;
-    if (list_capacity != 2LL * batch_size * tiles_x * tiles_y || list_capacity > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (list_capacity != 2LL * batch_size * tiles_x * tiles_y || !grid_ok(list_capacity)) return MR_ERR_BADARG;
     if (batch_size == 0) return MR_OK;
     OcclTilesParams p{{mask_flow1, mask_flow2}, {flow12, flow21}, {flow12_scale, flow21_scale}, {occl1, occl2},
                       {flow_out12, flow_out21}, {tile_hit1, tile_hit2}, flow_bstride, batch_size, image_size, crop_height,
@@ -1302,10 +1277,18 @@ extern "C" int mr_occlusion_flow_tiles(const float* mask_flow1, const float* mas
     return MR_OK;
 }
 
+// workspace of the listed pair loss, per tile of the 2B stacked images: {sum, count} of the pair loss | (mr_flow_pair_forward_grad_
+// tiles) the largest unit gradient -- word arrays, packed.  Places them in `q` (nullable), returns the bytes.
+static int64_t pair_tiles_work(void* ws, int batch_size, int hit_image_size, FlowPairFwdParams* q = nullptr) {
+    const int64_t tiles = 2LL * batch_size * ((hit_image_size + 31) / 32) * ((hit_image_size + 7) / 8);
+    Carve c;
+    const int64_t partial = c.take(tiles * 2 * (int64_t)sizeof(float), 4), tile_max = c.take(tiles * (int64_t)sizeof(unsigned), 4);
+    if (q) { q->partial = at_offset<float>(ws, partial); q->tile_max = at_offset<unsigned>(ws, tile_max); }
+    return c.total();
+}
 extern "C" int64_t mr_pair_consist_tiles_workspace_bytes(int batch_size, int hit_image_size) {
     if (batch_size < 0 || hit_image_size <= 0) return MR_ERR_BADARG;
-    // per tile of the 2B stacked images: {sum, count} of the pair loss + (mr_flow_pair_forward_grad_tiles) the largest unit gradient
-    return 2LL * batch_size * ((hit_image_size + 31) / 32) * ((hit_image_size + 7) / 8) * 3 * (int64_t)sizeof(float);
+    return pair_tiles_work(nullptr, batch_size, hit_image_size);
 }
 
 extern "C" int64_t mr_flow_pair_scatter_work_bytes(int batch_size, int image_size) {
@@ -1326,7 +1309,7 @@ static int pair_tiles_args_ok(const float* flow12, const float* flow21, const fl
     if (batch_size < 0 || height <= 0 || width <= 0 || hit_image_size < height || hit_image_size < width) return MR_ERR_BADARG;
     if (width < 2 || (int64_t)height * width > (1LL << 29)) return MR_ERR_BADARG;  // row-pair taps, 32-bit byte offsets
     const int64_t T = (int64_t)((hit_image_size + 31) / 32) * ((hit_image_size + 7) / 8);
-    if (list_capacity != 2LL * batch_size * T || list_capacity > 0x7fffffffLL) return MR_ERR_BADARG;
+    if (list_capacity != 2LL * batch_size * T || !grid_ok(list_capacity)) return MR_ERR_BADARG;
     if (!p) return MR_OK;
     p->flow[0] = flow12; p->flow[1] = flow21;
     p->image_ref = image_ref; p->image = image; p->jitter_ref = jitter_ref; p->jitter = jitter; p->Cj = jitter_channels;
@@ -1420,7 +1403,7 @@ extern "C" int mr_pair_consist_backward_tiles(const float* flow12, const float* 
 
 int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
     const bool grad = a.unit_grad != nullptr;
-    if (a.records ? (!grad || ((uintptr_t)a.records & 15))
+    if (a.records ? (!grad || misaligned({a.records}, 15))
                   : (!a.mask_flow1 || !a.mask_flow2 || !a.flow12 || !a.flow21 || !a.occl1 || !a.occl2))
         return MR_ERR_BADARG;
     if (!a.flow_out12 || !a.flow_out21 || !criterion_ok(a.criterion)) return MR_ERR_BADARG;
@@ -1433,20 +1416,18 @@ int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
                                       a.batch_size, a.height, a.width, a.tile_hit1, a.tile_hit2, a.image_size, a.list_header,
                                       a.list_entries, a.list_capacity);
     if (rc != MR_OK) return rc;
-    if (!a.workspace || !a.sums || a.workspace_bytes < mr_pair_consist_tiles_workspace_bytes(a.batch_size, a.image_size))
-        return MR_ERR_BADARG;
+    FlowPairFwdParams q{};
+    if (!a.workspace || !a.sums || a.workspace_bytes < pair_tiles_work(a.workspace, a.batch_size, a.image_size, &q)) return MR_ERR_BADARG;
     if (a.batch_size == 0) return MR_OK;
     const int tiles_x = (a.image_size + 31) / 32, tiles_y = (a.image_size + 7) / 8;
     const TileList* header = (const TileList*)a.list_header;
-    FlowPairFwdParams q{};
     q.o = OcclTilesParams{{a.mask_flow1, a.mask_flow2}, {a.flow12, a.flow21}, {a.flow12_scale, a.flow21_scale}, {a.occl1, a.occl2},
                           {a.flow_out12, a.flow_out21}, {a.tile_hit1, a.tile_hit2}, a.flow_bstride, a.batch_size, a.image_size,
                           a.height, a.width, tiles_x, tiles_y, a.distance_thresh, a.warp_thresh,
                           {header, (const uint4*)a.list_entries, (unsigned)a.list_capacity}};
     q.image_ref = a.image_ref; q.image = a.image; q.jitter_ref = a.jitter_ref; q.jitter = a.jitter; q.Cj = a.jitter_channels;
-    q.partial = (float*)a.workspace; q.thresh = a.pair_thresh;
+    q.thresh = a.pair_thresh;
     q.unit_grad = a.unit_grad;
-    q.tile_max = reinterpret_cast<unsigned*>(q.partial + 2LL * a.batch_size * tiles_x * tiles_y * 2);
     q.rec = (const float4*)a.records;
     // (the form -- records / unit gradient / loss only --, the criterion and the batch's element types are chosen here, once
     // per launch)

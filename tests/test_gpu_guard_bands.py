@@ -129,10 +129,14 @@ def _renderer(ctx, is_, B, aa=False):
 @case("render_generic-raster5-face_gradients", 5, face_grads=True)
 @case("render_generic-raster40-face_gradients", 40, face_grads=True)
 @case("render_generic-raster40-five_entry_points", 40, fused=False, face_grads=True)
-def render_generic(ctx, is_, aa=False, empty=False, fused=True, face_grads=False):
+# (B = 3, F = 5 on rasters of 2 and 6 pixels: the strip weights of mr_render_backward's workspace -- 2 B is / L words, cleared by
+# the marking launch one word per thread -- outnumber that launch's pixel quads, and every region is smaller than its slot)
+@case("render_generic-raster2-5_faces-face_gradients", 2, face_grads=True, few=True)
+@case("render_generic-raster6-5_faces-face_gradients", 6, face_grads=True, few=True)
+def render_generic(ctx, is_, aa=False, empty=False, fused=True, face_grads=False, few=False):
     """rasterize_rgbad on textures, rgb / alpha / depth, forward + backward to the textures (the training setting: a fixed-order
     gather, bit-reproducible); ``face_grads``: to the face coordinates as well (float atomics); ``fused=False``:
-    RasterizeFunction on the five upstream-compatible entry points"""
+    RasterizeFunction on the five upstream-compatible entry points; ``few``: five large random triangles of both windings"""
     from handobjectconsist_amd.neurender import rasterize
     from tests.test_gpu_raster import projected_faces
 
@@ -141,13 +145,20 @@ def render_generic(ctx, is_, aa=False, empty=False, fused=True, face_grads=False
     faces, tex = projected_faces(B, is_, 7)
     if empty:
         faces, tex = faces[:, :0], tex[:, :0]
+    if few:
+        rng = np.random.default_rng(is_)
+        faces = rng.uniform(-1.3, 1.3, (B, 5, 3, 3)).astype(np.float32)
+        faces[..., 2] = rng.uniform(0.3, 3.0, (B, 5, 3))
+        faces[:, 1::2] = faces[:, 1::2, ::-1]
+        tex = rng.uniform(-1, 1, (B, 5, 2, 2, 2, 3)).astype(np.float32)
     f, x = ctx(faces, grad=face_grads), ctx(tex, grad=True)
     out = rasterize.rasterize_rgbad(f, x, is_, aa, 0.1, 100, 1e-3, (0.1, 0.2, 0.3))
     g = _gen(is_, aa, empty)
     grads = [ctx(_rand(g, *out[k].shape)) for k in ("rgb", "alpha", "depth")]
     ctx.backward([out["rgb"], out["alpha"], out["depth"]], grads)
     return dict(out=dict(rgb=out["rgb"], alpha=out["alpha"], depth=out["depth"], grad_faces=f.grad, grad_textures=x.grad),
-                loose=dict(grad_faces=RASTER_TOL, **({} if fused else dict(grad_textures=RASTER_TOL))))
+                loose=dict(grad_faces=RASTER_TOL, **({} if fused else dict(grad_textures=RASTER_TOL))),
+                wants_call=("mr_render_backward",) if few else ())
 
 
 @case("render_vertex_colours-raster40", 40)
@@ -208,6 +219,9 @@ def _pair_loss_cases():
             for dims in ((2, 72, 72, 72, 1), (3, 104, 56, 100, 3)):
                 name = "flow_pair_loss-%s-%s-%dx%d-%dx%d-cj%d" % ((path, batch) + dims)
                 case(name, path, batch, *dims)(flow_pair_loss)
+        # (B = 1 on a raster of 36: 2 x 5 tiles, every region of the listed pair loss's workspace -- partial | tile_max -- and of
+        # the pair step's two buffers ends off the 256-byte grid)
+        case("flow_pair_loss-%s-fp32-1x36-33x35-cj1" % path, path, "fp32", 1, 36, 33, 35, 1)(flow_pair_loss)
 
 
 def flow_pair_loss(ctx, path, batch, B, is_, H, W, Cj):
@@ -426,8 +440,10 @@ def mano_pca(ctx, B):
 
 @case("mano_forward_full-pca", True)
 @case("mano_forward_full-axisang", False)
-def mano_forward_full(ctx, use_pca):
-    B = 2
+# (the padded batch of the backward's split-K partials is 32 at B = 1 and 64 at B = 33; tflag sits behind them)
+@case("mano_forward_full-axisang-B1", False, 1)
+@case("mano_forward_full-axisang-B33", False, 33)
+def mano_forward_full(ctx, use_pca, B=2):
     layer = _mano(ctx, use_pca=use_pca, flat_hand_mean=not use_pca, center_idx=9 if use_pca else None)
     g = _gen(B, use_pca)
     p, b = ctx(_rand(g, B, 18 if use_pca else 48, s=0.4), grad=True), ctx(_rand(g, B, 10), grad=True)
@@ -618,6 +634,20 @@ def color_augment(ctx):
     plans[0, 1:5], plans[0, 5:9] = (C.OP_SATURATION, C.OP_CONTRAST, C.OP_HUE, C.OP_BRIGHTNESS), (1.4, 0.6, -30, 1.2)
     plans[2, 1], plans[2, 5] = C.OP_HUE, 38
     return dict(out=dict(frames=F.color_augment(ctx(frames), ctx.host(plans), flip=[0, 1, 0])))
+
+
+@case("color_augment-1x3x5-contrast")
+def color_augment_contrast(ctx):
+    """one frame of 3 x 5 with a contrast op (the luma sum and the tail kernel) behind a blur: every region of the workspace --
+    plans | luma sums | row-blurred frames -- is smaller than its 256-byte slot"""
+    from handobjectconsist_amd.datasets import frames as F
+    from tests import coloraugm_ref as C
+
+    frames = np.random.default_rng(15).integers(0, 256, (1, 3, 5, 3), dtype=np.uint8)
+    plans = np.zeros((1, 9), np.float32)
+    plans[0, 0] = 1.5
+    plans[0, 1:3], plans[0, 5:7] = (C.OP_BRIGHTNESS, C.OP_CONTRAST), (0.8, 1.3)
+    return dict(out=dict(frames=F.color_augment(ctx(frames), ctx.host(plans), flip=[1])))
 
 
 @case("jpeg_reconstruct-g17x9_s2", "g17x9_s2")
