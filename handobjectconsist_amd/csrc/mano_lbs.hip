@@ -398,10 +398,11 @@ __global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, ManoFu
         part[((int64_t)b * MN_CHUNKS + chunk) * MN_PART + tid] = acc;
     } else if (tid < MN_J * 12 + 3) {
         // d centre = - sum of the vertex gradients (each vertex subtracts the centre); g = gT[.][4 r + 3]
+        // (256 terms one after the other: in double, or the sum -- it is grad trans -- is several fp32 ulps off)
         const int r = tid - MN_J * 12;
-        float acc = 0.0f;
-        for (int u = 0; u < 256; u++) acc += s_gt[u][4 * r + 3];
-        part[((int64_t)b * MN_CHUNKS + chunk) * MN_PART + tid] = -acc;
+        double acc = 0.0;
+        for (int u = 0; u < 256; u++) acc += (double)s_gt[u][4 * r + 3];
+        part[((int64_t)b * MN_CHUNKS + chunk) * MN_PART + tid] = (float)-acc;
     }
 }
 
@@ -442,39 +443,44 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
                                                           const float* __restrict__ grad_jtr,
                                                           float* __restrict__ grad_pose, float* __restrict__ grad_betas,
                                                           int B, int Mpad) {
-    __shared__ float s_gG2[MN_J * 12], s_gc[3], s_gcoef[MN_KP], s_gG[MN_J * 12], s_gR[MN_J * 9], s_gJ[48], s_gp[48];
-    __shared__ float s_G[MN_J * 12], s_R[MN_J * 9], s_J[48], s_gt[MN_J][3];
+    // The adjoints of this kernel are accumulated in DOUBLE: a few thousand flops per sample on one wave, and sums whose
+    // terms cancel (a joint's position enters its own transform and every descendant's with opposite signs), so that fp32
+    // accumulation left grad betas 5 to 11 fp32 ulps off where the inputs allow 1 to 2 (tests/test_gpu_mano_grads.py).
+    // What the forward pass stored (G, rots, joints) and what goes out stay fp32
+    __shared__ double s_gG2[MN_J * 12], s_gc[3], s_gcoef[MN_KP], s_gG[MN_J * 12], s_gRd[MN_J * 9], s_gJ[48], s_gt[MN_J][3];
+    __shared__ float s_gR[MN_J * 9], s_gp[48];
+    __shared__ float s_G[MN_J * 12], s_R[MN_J * 9], s_J[48];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int np = FORM == MN_POSE_AXISANG ? 48 : 3 + mc.ncomps;
     for (int k = lane; k < MN_J * 12; k += 64) {
-        float acc = 0.0f;
-        for (int c = 0; c < MN_CHUNKS; c++) acc += part[((int64_t)b * MN_CHUNKS + c) * MN_PART + k];
+        double acc = 0.0;
+        for (int c = 0; c < MN_CHUNKS; c++) acc += (double)part[((int64_t)b * MN_CHUNKS + c) * MN_PART + k];
         s_gG2[k] = acc;
         s_G[k] = G[b * MN_J * 12 + k];
     }
     if (lane < 3) {
-        float acc = 0.0f;
-        for (int c = 0; c < MN_CHUNKS; c++) acc += part[((int64_t)b * MN_CHUNKS + c) * MN_PART + MN_J * 12 + lane];
+        double acc = 0.0;
+        for (int c = 0; c < MN_CHUNKS; c++) acc += (double)part[((int64_t)b * MN_CHUNKS + c) * MN_PART + MN_J * 12 + lane];
         s_gc[lane] = acc;
     }
     for (int k = lane; k < MN_KP; k += 64) {
-        float acc = 0.0f;
-        for (int s = 0; s < MN_SPLITK; s++) acc += partial[((int64_t)s * Mpad + b) * 160 + k];
+        double acc = 0.0;
+        for (int s = 0; s < MN_SPLITK; s++) acc += (double)partial[((int64_t)s * Mpad + b) * 160 + k];
         s_gcoef[k] = acc;
     }
     for (int k = lane; k < MN_J * 9; k += 64) s_R[k] = rots[b * MN_J * 9 + k];
-    if (lane < 48) { s_J[lane] = joints[b * 48 + lane]; s_gJ[lane] = 0.0f; }
+    if (lane < 48) { s_J[lane] = joints[b * 48 + lane]; s_gJ[lane] = 0.0; }
     __syncthreads();
     // joint rows of jtr: (G[src].t - centre) * 1000 ; centre gradient gathers everything that was centred
     if (lane == 0) {
-        float (*gt)[3] = s_gt;  // (indexed by the reorder table: in LDS, not in scratch)
-        for (int j = 0; j < MN_J; j++) gt[j][0] = gt[j][1] = gt[j][2] = 0.0f;
-        float gc[3] = {s_gc[0], s_gc[1], s_gc[2]};
+        double (*gt)[3] = s_gt;  // (indexed by the reorder table: in LDS, not in scratch)
+        for (int j = 0; j < MN_J; j++) gt[j][0] = gt[j][1] = gt[j][2] = 0.0;
+        double gc[3] = {s_gc[0], s_gc[1], s_gc[2]};
         if (grad_jtr)
             for (int k = 0; k < MN_JT; k++) {
                 const int src = mc.reorder[k];
                 for (int r = 0; r < 3; r++) {
-                    const float g = grad_jtr[(b * MN_JT + k) * 3 + r] * 1000.0f;
+                    const double g = (double)grad_jtr[(b * MN_JT + k) * 3 + r] * 1000.0;
                     if (src < MN_J) { gt[src][r] += g; gc[r] -= g; }
                     // (tips: their share of the centre gradient is in part[] through the vertex rows)
                 }
@@ -482,10 +488,11 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
         if constexpr (FULL) {
             // verts = (skinned + trans) * 1000, joints likewise: d trans = the sum of every incoming gradient x 1000 = -gc,
             // and nothing was centred.  A tip centre's adjoint went into its vertex (mano_skin_bwd_kernel); part[]'s sum
-            // then holds that vertex's addend too and is not used
+            // then holds that vertex's addend too and is not used.  (0 - gc, not -gc: the same value for every gc but zero,
+            // where all-zero incoming gradients then give +0 like every other gradient, not -0)
             const bool in_force = mf.tflag[b] != 0.0f;
             if (grad_trans)
-                for (int r = 0; r < 3; r++) grad_trans[b * 3 + r] = in_force ? -gc[r] : 0.0f;
+                for (int r = 0; r < 3; r++) grad_trans[b * 3 + r] = in_force ? (float)(0.0 - gc[r]) : 0.0f;
             if (mc.center >= 0 && mc.center < MN_J && !in_force)
                 for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
         } else {
@@ -495,10 +502,10 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
         // G2 = [G.R | G.t - G.R J]  ->  dG.R = dG2.R - dG2.t (x) J ; dG.t = dG2.t ; dJ = - G.R^T dG2.t
         for (int j = 0; j < MN_J; j++) {
             for (int r = 0; r < 3; r++) {
-                const float gt2 = s_gG2[j * 12 + 4 * r + 3];
+                const double gt2 = s_gG2[j * 12 + 4 * r + 3];
                 for (int c = 0; c < 3; c++) {
-                    s_gG[j * 12 + 4 * r + c] = s_gG2[j * 12 + 4 * r + c] - gt2 * s_J[3 * j + c];
-                    s_gJ[3 * j + c] -= s_G[j * 12 + 4 * r + c] * gt2;
+                    s_gG[j * 12 + 4 * r + c] = s_gG2[j * 12 + 4 * r + c] - gt2 * (double)s_J[3 * j + c];
+                    s_gJ[3 * j + c] -= (double)s_G[j * 12 + 4 * r + c] * gt2;
                 }
                 s_gG[j * 12 + 4 * r + 3] = gt2 + gt[j][r];
             }
@@ -508,27 +515,27 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
             const int pa = mc.parents[j];
             if (pa < 0) {
                 for (int r = 0; r < 3; r++) {
-                    for (int c = 0; c < 3; c++) s_gR[j * 9 + 3 * r + c] = s_gG[j * 12 + 4 * r + c];
+                    for (int c = 0; c < 3; c++) s_gRd[j * 9 + 3 * r + c] = s_gG[j * 12 + 4 * r + c];
                     s_gJ[3 * j + r] += s_gG[j * 12 + 4 * r + 3];
                 }
                 continue;
             }
-            float rel[12];
+            double rel[12];
             for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) rel[4 * r + c] = s_R[j * 9 + 3 * r + c];
-                rel[4 * r + 3] = s_J[3 * j + r] - s_J[3 * pa + r];
+                for (int c = 0; c < 3; c++) rel[4 * r + c] = (double)s_R[j * 9 + 3 * r + c];
+                rel[4 * r + 3] = (double)s_J[3 * j + r] - (double)s_J[3 * pa + r];
             }
             // d rel = G_p.R^T dG_j ; d G_p.R += dG_j.R rel.R^T + dG_j.t (x) rel.t ; d G_p.t += dG_j.t
             for (int r = 0; r < 3; r++)
                 for (int c = 0; c < 4; c++) {
-                    float acc = 0.0f;
-                    for (int k = 0; k < 3; k++) acc += s_G[pa * 12 + 4 * k + r] * s_gG[j * 12 + 4 * k + c];
-                    if (c < 3) s_gR[j * 9 + 3 * r + c] = acc;
+                    double acc = 0.0;
+                    for (int k = 0; k < 3; k++) acc += (double)s_G[pa * 12 + 4 * k + r] * s_gG[j * 12 + 4 * k + c];
+                    if (c < 3) s_gRd[j * 9 + 3 * r + c] = acc;
                     else { s_gJ[3 * j + r] += acc; s_gJ[3 * pa + r] -= acc; }
                 }
             for (int r = 0; r < 3; r++) {
                 for (int c = 0; c < 3; c++) {
-                    float acc = 0.0f;
+                    double acc = 0.0;
                     for (int k = 0; k < 4; k++) acc += s_gG[j * 12 + 4 * r + k] * rel[4 * c + k];
                     s_gG[pa * 12 + 4 * r + c] += acc;
                 }
@@ -538,7 +545,7 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
     }
     __syncthreads();
     // pose features: coeff[10 + 9 (j - 1) + k] = R_j[k] - I
-    for (int k = lane; k < 135; k += 64) s_gR[9 + k] += s_gcoef[10 + k];
+    for (int k = lane; k < MN_J * 9; k += 64) s_gR[k] = (float)(k >= 9 ? s_gRd[k] + s_gcoef[10 + (k - 9)] : s_gRd[k]);
     __syncthreads();
     if (lane < MN_J) {
         float gr[3];
@@ -556,9 +563,9 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
         grad_pose[b * np + 3 + lane] = acc;
     }
     if (lane < 10) {
-        float acc = s_gcoef[lane];
-        for (int l = 0; l < 48; l++) acc = fmaf(mc.js[l * 10 + lane], s_gJ[l], acc);
-        grad_betas[b * 10 + lane] = acc;
+        double acc = s_gcoef[lane];
+        for (int l = 0; l < 48; l++) acc += (double)mc.js[l * 10 + lane] * s_gJ[l];
+        grad_betas[b * 10 + lane] = (float)acc;
     }
 }
 

@@ -172,17 +172,18 @@ __global__ void __launch_bounds__(256) post_backward_kernel(PostParams p, const 
     }
 }
 
-// adjoint of center3d: gc[3] -> (d s, d tx, d ty) of the raw head outputs (factors applied)
+// adjoint of center3d: gc[3] -> (d s, d tx, d ty) of the raw head outputs (factors applied).  Once per sample: in double,
+// so that the three results are the per-sample sums' own rounding away from exact and no further
 __device__ __forceinline__ void center3d_bwd(const float* K, float s_raw, float tx_raw, float ty_raw, const PostParams& p,
                                              const float* gc, float* out3) {
-    const float f = K[0];
-    const float s = s_raw * p.scale_factor, tx = tx_raw * p.trans_factor, ty = ty_raw * p.trans_factor;
-    const float z0 = f * s + p.off_z;
-    const float ax = tx + p.res_w / 2.0f - K[2], ay = ty + p.res_h / 2.0f - K[5];
-    const float g_z0 = gc[2] + gc[0] * ax / f + gc[1] * ay / f;
-    out3[0] = g_z0 * f * p.scale_factor;
-    out3[1] = gc[0] * z0 / f * p.trans_factor;
-    out3[2] = gc[1] * z0 / f * p.trans_factor;
+    const double f = K[0];
+    const double s = (double)s_raw * p.scale_factor, tx = (double)tx_raw * p.trans_factor, ty = (double)ty_raw * p.trans_factor;
+    const double z0 = f * s + p.off_z;
+    const double ax = tx + p.res_w / 2.0 - K[2], ay = ty + p.res_h / 2.0 - K[5];
+    const double g_z0 = gc[2] + gc[0] * ax / f + gc[1] * ay / f;
+    out3[0] = (float)(g_z0 * f * p.scale_factor);
+    out3[1] = (float)(gc[0] * z0 / f * p.trans_factor);
+    out3[2] = (float)(gc[1] * z0 / f * p.trans_factor);
 }
 
 __global__ void __launch_bounds__(64) post_backward_finish_kernel(PostParams p, const float* __restrict__ sums,
