@@ -4,6 +4,7 @@
 // A zero-initialised block asks for nothing optional: what is not assigned is NULL / 0 / MR_CRITERION_L1.
 #pragma once
 #include "mr_common.hpp"
+#include "launch_plan.hpp"
 #include "vertex_stage_device.hpp"
 
 namespace mr {

@@ -109,8 +109,7 @@ __device__ __forceinline__ void gather_pixel(const GatherParams& p, const Face& 
 // GGL (generic gather) / GLPF (vertex-colour gather) lanes per face: lane `sub` walks bbox rows sub, sub + lanes, ...;
 // the partial sums are combined with shuffles inside the lane group (fixed order: deterministic).  Faces whose bbox
 // exceeds GATHER_BIG pixels are walked by the whole wave instead.
-constexpr int GLPF = 4;
-constexpr int GGL = 8;       // lanes per face of the generic gather (E: 74 -> 64 us, E + F: 105 -> 93 us against 4; 16: 70 / 101)
+// (GLPF / GGL lanes per face of the vertex-colour / the generic gather: launch_plan.hpp)
 constexpr int GATHER_BIG = 128;          // vertex-colour gather: bbox area above which the whole wave probes
 // (256 until round 5: the 114 faces of the bench scene with boxes of 256-500 pixels then took the whole-wave path ONE BEHIND THE
 // OTHER inside the wave that holds them -- consecutive wrist faces -- while as ordinary lane groups they advance side by side: E
@@ -553,9 +552,8 @@ __global__ void __launch_bounds__(256) gather_vc_kernel(GatherVCParams p) {
 // largest gradient -- far below fp32 rounding of the sum -- and the block's sums do not depend on
 // the order of the additions.  Regions whose gradient holds an Inf / NaN take a plain fp32
 // global-atomic path so that non-finite values propagate as they do in the gather kernel.
-constexpr int SV_WAVES = 16;                                    // waves per block
-constexpr int SV_RPW = 2, SV_W = 64, SV_H = SV_WAVES * SV_RPW;  // rows per wave, region
-constexpr int SV_MAX_TABLE_BYTES = 60 * 1024;
+// (SV_WAVES waves per block, SV_RPW rows per wave of a SV_W x SV_H region, SV_MAX_TABLE_BYTES of colour table: launch_plan.hpp)
+static_assert(WAVE == MR_WAVE, "the plans count lanes in waves of MR_WAVE");
 constexpr int SV_FIX_BITS = 50;
 static_assert(3LL * SV_W * SV_H < (1LL << (63 - SV_FIX_BITS)), "fixed-point sums must not overflow");
 
@@ -723,10 +721,8 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
 // identically zero): its table is a third smaller; and eight workgroups of EIGHT waves per image instead of sixteen of
 // four keep the 64 waves per image while halving the per-image fixed work (covered-tile list, table zeroing, flush):
 // 4 x 8 waves fit a compute unit, so all 1024 workgroups of a 128-image launch are resident at once.
-constexpr int ST_G = 8;       // workgroups per image (sp.groups)
-constexpr int ST_WAVES = 8;   // waves per workgroup
-constexpr int ST_TW = 32, ST_TH = 8;  // the forward's tile
-constexpr int ST_MAX_TILES = 4096;    // tiles per image the covered-tile list in LDS can hold (1024 x 1024 pixels)
+// (ST_G workgroups per image or more, ST_WAVES waves each, ST_TW x ST_TH tiles, ST_MAX_TILES of them per image: launch_plan.hpp)
+static_assert(ST_TW == TILE_W && ST_TH == TILE_H, "the scatter walks the forward's tiles");
 // fixed point of the per-workgroup sums: terms below 2^ST_FIX_BITS in magnitude (2^-37 of the workgroup's largest gradient
 // per term: 13 bits below the last bit of an fp32 value of that size), sums below 2^ST_SUM_BITS (see scatter_tiles_body)
 constexpr int ST_FIX_BITS = 37, ST_SUM_BITS = 50;
@@ -1587,7 +1583,6 @@ __device__ __forceinline__ float wave_max_last(float v) {
 // the owners of ONE image and reads nothing else of a face).
 // faces per thread: 1 -- seven workgroups per image of the bench meshes instead of two; most of this kernel's time is the zero
 // rows it writes (60 MB per launch at the metric config), which 128 workgroups do not stream at the chip's rate: 17.8 -> 13.8 us
-constexpr int CO_TPB = 1024, CO_PER = 1;
 __global__ void __launch_bounds__(CO_TPB) compact_owners_kernel(PixelMapParams p, const uint8_t* __restrict__ owns,
                                                                 unsigned* __restrict__ counter, uint32_t* __restrict__ list,
                                                                 unsigned* __restrict__ img_count, float4* __restrict__ img_recs,
@@ -1750,20 +1745,7 @@ __device__ __forceinline__ void ps_count_terms(int n) {
     for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off);
     if ((threadIdx.x & 63) == 0 && tot) atomicAdd(&mr_pixel_map_terms_counter, (unsigned long long)tot);
 }
-constexpr int PS_T = 256;
-constexpr int PS_QCAP = 1024;  // queued entries; a round of PS_T faces adds at most 3 * PS_T
-
-// lines per strip: the most whose records leave room for three workgroups per compute unit; 0 = raster too wide
-static int strip_lines(int is) {
-    for (int L = 4; L >= 1; L >>= 1)
-        if (L * (is + 1) * 36LL <= 37 * 1024) return L;
-    return ((is + 1) * 36LL <= 50 * 1024) ? 1 : 0;  // (one workgroup of 64 KB)
-}
-constexpr int PS_TASKS = 1024;  // chunk tasks of a wave's batch: 64 items, at most 16 chunks each
-static int64_t strip_lds_bytes(int is, int L) {
-    return 2LL * L * (is + 1) * 16 + (((int64_t)L * (is + 1) * 4 + 15) & ~15LL) + PS_QCAP * 4LL +
-           (PS_T / MR_WAVE) * (PS_TASKS * 2LL + MR_WAVE * 8LL);
-}
+// (PS_T threads, PS_QCAP queued entries, PS_TASKS chunk tasks, the lines per strip and the strip kernel's LDS bytes: launch_plan.hpp)
 
 // The strips that have work, XCD by XCD (image b runs on XCD b % 8: all strips of an image behind one L2), HEAVIEST FIRST.
 // One workgroup per XCD reads the weights compact_owners_kernel left (owners with crossings per strip), and lists the
@@ -1772,7 +1754,6 @@ static int64_t strip_lds_bytes(int is, int L) {
 // line range (each used to hold one of the chip's 768 slots for a microsecond or two), and the strips through the middle
 // of the meshes (up to 100 us each) start first instead of wherever the image order put them (workgroup timeline,
 // profiles/r03_kernel_d.txt: last start 265 us into a 315 us launch, 650-700 working strips resident of 768).
-constexpr int SL_T = 1024;
 __global__ void __launch_bounds__(SL_T) strip_list_kernel(const unsigned* __restrict__ strip_w, unsigned* __restrict__ lists,
                                                           unsigned* __restrict__ counts, int B, int S, int cap) {
     __shared__ unsigned s_max, s_n[3], s_at[3];
@@ -2223,14 +2204,11 @@ static OwnerList owner_list(void* workspace, int B, int F) {
     return o;
 }
 // flags -> lists (+ zero rows); the workspace's flags and counts must have been cleared (ol.clear_bytes) and marked
-static int launch_compact(const PixelMapParams& q, const OwnerList& ol, bool per_image, hipStream_t s,
+static int launch_compact(const CompactPlan& plan, const PixelMapParams& q, const OwnerList& ol, bool per_image, hipStream_t s,
                           unsigned* strip_w = nullptr, int strip_l = 1, int strips_axis = 0) {
-    const int chunks = (q.F + CO_TPB * CO_PER - 1) / (CO_TPB * CO_PER);
-    const int64_t blocks = (int64_t)q.B * chunks;
-    if (!grid_ok(blocks)) return MR_ERR_BADARG;
-    if (blocks == 0) return MR_OK;
-    hipLaunchKernelGGL(compact_owners_kernel, dim3((unsigned)blocks), dim3(CO_TPB), 0, s, q, (const uint8_t*)ol.owns, ol.counter,
-                       ol.list, per_image ? ol.img_count : (unsigned*)nullptr, per_image ? ol.img_recs : (float4*)nullptr, chunks,
+    if (plan.status != MR_OK || !plan.launch) return plan.status;
+    hipLaunchKernelGGL(compact_owners_kernel, dim3(plan.wgs), dim3(CO_TPB), 0, s, q, (const uint8_t*)ol.owns, ol.counter,
+                       ol.list, per_image ? ol.img_count : (unsigned*)nullptr, per_image ? ol.img_recs : (float4*)nullptr, plan.chunks,
                        strip_w, strip_l, strips_axis);
     MR_CHECK_LAUNCH();
     return MR_OK;
@@ -2241,108 +2219,72 @@ struct StripLists {
     unsigned* weights;
     unsigned* lists;
     unsigned* counts;
-    int strips_axis, cap;
-    int64_t n_weights, bytes;
+    int64_t bytes;
 };
-static int strip_lines(int is);
-static StripLists strip_lists(void* workspace, int B, int F, int is) {
+static StripLists strip_lists(void* workspace, int B, int F, const StripShape& shape) {
     StripLists sl{};
-    const int L = strip_lines(is);
-    if (L == 0) return sl;  // (a raster whose lines do not fit LDS: no strips, no bytes)
-    sl.strips_axis = (is + L - 1) / L;
-    const int64_t S = 2LL * sl.strips_axis;
-    sl.cap = (int)(((B + 7) / 8) * S);
-    sl.n_weights = (int64_t)B * S;
+    if (shape.lines == 0) return sl;  // (a raster whose lines do not fit LDS: no strips, no bytes)
     void* base = at_offset<char>(workspace, owner_list(workspace, B, F).bytes);
     Carve c;
-    sl.weights = at_offset<unsigned>(base, c.take(sl.n_weights * 4));
-    sl.lists = at_offset<unsigned>(base, c.take(8LL * sl.cap * 4));
+    sl.weights = at_offset<unsigned>(base, c.take(shape.n_weights * 4));
+    sl.lists = at_offset<unsigned>(base, c.take(8LL * shape.cap * 4));
     sl.counts = at_offset<unsigned>(base, c.take(256));
     sl.bytes = c.total();
     return sl;
 }
 static int64_t pixel_map_workspace_bytes(int B, int F, int is) {
-    return owner_list(nullptr, B, F).bytes + strip_lists(nullptr, B, F, is).bytes;
+    return owner_list(nullptr, B, F).bytes + strip_lists(nullptr, B, F, strip_shape(B, is)).bytes;
 }
 
-// kernel D by strips needs the workspace, a raster whose lines fit LDS and 24-bit owner numbers
-static bool strips_apply(int B, int F, int is, const void* workspace, int64_t workspace_bytes, int flags) {
-    return workspace && workspace_bytes >= pixel_map_workspace_bytes(B, F, is) && !(flags & MR_FLAG_REFERENCE_ALGO) &&
-           strip_lines(is) != 0 && (int64_t)B * F < 0x7fffffffLL && F < (1 << 24);
-}
-
-// kernel D: by strips when a workspace of pixel_map_workspace_bytes is available (leaves the owner list for the gather
-// behind), else the plane-reading per-face walk (same results up to the order of the fp32 additions)
-// `fused` (nullable): the E / F gather of the same call, to go out INSIDE the strip kernel's launch (strip_gather_kernel);
-// *fused_done says whether it did (not when the walk takes the plane-reading kernel)
-struct FusedGather {
-    GatherParams g;
-    bool tex, depth;
-    int64_t threads;
-};
-// the marking pass over the face index map, four pixels per thread where the raster allows; `weights` (nullable): the strip
-// weights it clears on the way, one word per thread
-static int launch_mark_owners(const int32_t* fim, uint8_t* owns, int B, int is, int F, unsigned* weights, int64_t n_weights,
+// the marking pass over the face index map (plan_mark); `weights` (nullable): the strip weights it clears on the way
+static int launch_mark_owners(const MarkPlan& plan, const int32_t* fim, uint8_t* owns, int F, unsigned* weights, int64_t n_weights,
                               hipStream_t s) {
-    const int64_t ppi = (int64_t)is * is, npx = ppi * B;
-    if (ppi % 4 == 0) return launch1d(mark_owners_kernel, std::max(npx / 4, n_weights), s, fim, owns, npx / 4, ppi, F, weights, n_weights);
-    return launch1d(mark_owners_scalar_kernel, std::max(npx, n_weights), s, fim, owns, npx, ppi, F, weights, n_weights);
+    if (plan.quads) return launch1d(mark_owners_kernel, plan.threads, s, fim, owns, plan.items, plan.ppi, F, weights, n_weights);
+    return launch1d(mark_owners_scalar_kernel, plan.threads, s, fim, owns, plan.items, plan.ppi, F, weights, n_weights);
 }
 
+// the strip kernel with the E / F gather inside, for a strip of L lines
+template <bool IMG, int L>
+static auto strip_gather_for(GatherForm form) {
+    switch (form) {
+    case GatherForm::TEX_DEPTH: return strip_gather_kernel<IMG, L, true, true>;
+    case GatherForm::TEX: return strip_gather_kernel<IMG, L, true, false>;
+    default: return strip_gather_kernel<IMG, L, false, true>;
+    }
+}
+
+// kernel D (plan_pixel_map): by strips, or the plane-reading per-face walk
+// `g` (nullable): the E / F gather of the same call, which goes out INSIDE the strip kernel's launch when plan.fused
 template <bool IMG>
-static int launch_pixel_map(const PixelMapParams& p, void* workspace, int64_t workspace_bytes, int flags,
-                            hipStream_t s, const FusedGather* fused = nullptr, bool* fused_done = nullptr) {
-    const int64_t nfaces = (int64_t)p.B * p.F;
-    if (!strips_apply(p.B, p.F, p.is, workspace, workspace_bytes, flags))
-        return launch1d(pixel_map_kernel<IMG>, nfaces * MR_WAVE, s, p);
+static int launch_pixel_map(const PixelMapPlan& plan, const PixelMapParams& p, void* workspace, hipStream_t s, const GatherParams* g = nullptr) {
+    if (!plan.strips) return launch1d(pixel_map_kernel<IMG>, plan.walk_threads, s, p);
     const OwnerList ol0 = owner_list(workspace, p.B, p.F);
-    const int strip_l = strip_lines(p.is);
     hipError_t e0 = hipMemsetAsync(ol0.owns, 0, ol0.clear_bytes, s);  // flags and the counts behind them
     if (e0 != hipSuccess) return (int)e0;
-    const StripLists sl = strip_lists(workspace, p.B, p.F, p.is);
-    // (the marking pass clears the weights, one word per thread: 2 B is / L words -- more than B is^2 / 4 pixel quads for
-    // rasters of one or two pixels, found by tests/fuzz_parity.py: the launch then covers the weights, the kernels guard)
-    int rc = launch_mark_owners(p.fim, ol0.owns, p.B, p.is, p.F, sl.weights, sl.n_weights, s);
-    if (rc != MR_OK || nfaces == 0) return rc;
+    const StripLists sl = strip_lists(workspace, p.B, p.F, plan.shape);
+    int rc = launch_mark_owners(plan.mark, p.fim, ol0.owns, p.F, sl.weights, plan.shape.n_weights, s);
+    if (rc != MR_OK || !plan.after_mark) return rc;
     PixelMapParams q = p;
     q.zero_owner_rows = 1;
-    rc = launch_compact(q, ol0, true, s, sl.weights, strip_l, sl.strips_axis);
+    const int strip_l = plan.shape.lines, strips_axis = plan.shape.strips_axis, cap = plan.shape.cap;
+    rc = launch_compact(plan.compact, q, ol0, true, s, sl.weights, strip_l, strips_axis);
     if (rc != MR_OK) return rc;
-    const int strips_axis = sl.strips_axis;
     hipLaunchKernelGGL(strip_list_kernel, dim3(8), dim3(SL_T), 0, s, (const unsigned*)sl.weights, sl.lists, sl.counts, p.B,
-                       2 * strips_axis, sl.cap);
+                       plan.shape.strips, cap);
     MR_CHECK_LAUNCH();
-    const int64_t grid = 8LL * sl.cap;
-    if (!grid_ok(grid)) return MR_ERR_BADARG;
-    const size_t lds = (size_t)strip_lds_bytes(p.is, strip_l);
-    if (fused && (fused->tex || fused->depth)) {
-        const int64_t gblocks = (fused->threads + PS_T - 1) / PS_T;
-        const int64_t ggroups = (gblocks + 7) / 8, total = (ggroups + sl.cap) * 8;
-        if (grid_ok(total) && ggroups <= 0x0fffffffLL) {
-            const GatherParams g = fused->g;
-#define MR_SG_LAUNCH(L_, T_, D_)                                                                                          \
-            hipLaunchKernelGGL((strip_gather_kernel<IMG, L_, T_, D_>), dim3((unsigned)total), dim3(PS_T), lds, s, p,      \
-                               (const unsigned*)ol0.img_count, (const float4*)ol0.img_recs, strips_axis,                  \
-                               (const unsigned*)sl.lists, (const unsigned*)sl.counts, sl.cap, g, (unsigned)ggroups)
-#define MR_SG_PICK(L_)                                                                                                    \
-            do {                                                                                                          \
-                if (fused->tex && fused->depth) MR_SG_LAUNCH(L_, true, true);                                             \
-                else if (fused->tex) MR_SG_LAUNCH(L_, true, false);                                                       \
-                else MR_SG_LAUNCH(L_, false, true);                                                                       \
-            } while (0)
-            if (strip_l == 4) MR_SG_PICK(4);
-            else if (strip_l == 2) MR_SG_PICK(2);
-            else MR_SG_PICK(1);
-#undef MR_SG_PICK
-#undef MR_SG_LAUNCH
-            MR_CHECK_LAUNCH();
-            if (fused_done) *fused_done = true;
-            return MR_OK;
-        }
+    if (plan.status_grid != MR_OK) return plan.status_grid;
+    if (plan.fused) {
+        auto fused_kernel = strip_l == 4 ? strip_gather_for<IMG, 4>(plan.gather)
+                                         : (strip_l == 2 ? strip_gather_for<IMG, 2>(plan.gather) : strip_gather_for<IMG, 1>(plan.gather));
+        hipLaunchKernelGGL(fused_kernel, dim3(plan.fused_wgs), dim3(PS_T), plan.lds, s, p, (const unsigned*)ol0.img_count,
+                           (const float4*)ol0.img_recs, strips_axis, (const unsigned*)sl.lists, (const unsigned*)sl.counts, cap, *g,
+                           plan.gather_groups);
+        MR_CHECK_LAUNCH();
+        return MR_OK;
     }
     auto kernel = strip_l == 4 ? pixel_map_strip_kernel<IMG, 4> : (strip_l == 2 ? pixel_map_strip_kernel<IMG, 2> : pixel_map_strip_kernel<IMG, 1>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(PS_T), lds, s, p, (const unsigned*)ol0.img_count,
-                       (const float4*)ol0.img_recs, strips_axis, (const unsigned*)sl.lists, (const unsigned*)sl.counts, sl.cap);
+    hipLaunchKernelGGL(kernel, dim3(plan.wgs), dim3(PS_T), plan.lds, s, p, (const unsigned*)ol0.img_count,
+                       (const float4*)ol0.img_recs, strips_axis, (const unsigned*)sl.lists, (const unsigned*)sl.counts, cap);
     MR_CHECK_LAUNCH();
     return MR_OK;
 }
@@ -2371,8 +2313,10 @@ extern "C" int mr_backward_pixel_map(const float* faces, const int32_t* face_ind
     if (return_alpha && (!alpha_map || !grad_alpha_map)) return MR_ERR_BADARG;
     if (batch_size < 0 || num_faces < 0 || image_size <= 0) return MR_ERR_BADARG;
     if (!return_rgb && !return_alpha) return MR_OK;
-    PixelMapParams p{faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, grad_faces,
-                     batch_size, num_faces, image_size, eps, return_rgb, return_alpha, 0, 0};
+    PixelMapParams p{};  // (value-initialised, then filled: the padding bytes are kernel-argument bytes too)
+    p.faces = faces; p.fim = face_index_map; p.rgb = rgb_map; p.alpha = alpha_map; p.grad_rgb = grad_rgb_map; p.grad_alpha = grad_alpha_map;
+    p.grad_faces = grad_faces; p.B = batch_size; p.F = num_faces; p.is = image_size; p.eps = eps;
+    p.return_rgb = return_rgb; p.return_alpha = return_alpha;
     if (batch_size == 0 || num_faces == 0) return MR_OK;
     // scratch for the walk by strips, stream-ordered like the forward entry point's record list;
     // if it cannot be had the plane-reading kernel does the same job
@@ -2383,7 +2327,8 @@ extern "C" int mr_backward_pixel_map(const float* faces, const int32_t* face_ind
         (void)hipGetLastError();
         work = nullptr;
     }
-    const int rc = launch_pixel_map<false>(p, work, work ? bytes : 0, 0, s);
+    const PixelMapPlan plan = plan_pixel_map(batch_size, num_faces, image_size, strips_apply(batch_size, num_faces, image_size, work ? bytes : 0, bytes, 0));
+    const int rc = launch_pixel_map<false>(plan, p, work, s);
     if (work) (void)hipFreeAsync(work, s);
     return rc;
 }
@@ -2415,6 +2360,17 @@ extern "C" int mr_backward_depth_map(const float* faces, const float* depth_map,
                     face_inv_map, weight_map, grad_depth_map, grad_faces, npx, num_faces, image_size);
 }
 
+// the E / F gather on its own, in a plan's form
+static void (*gather_kernel_of(GatherForm form))(GatherParams) {
+    switch (form) {
+    case GatherForm::TEX_DEPTH: return gather_kernel<true, true, true>;
+    case GatherForm::TEX: return gather_kernel<true, true, false>;
+    case GatherForm::DEPTH: return gather_kernel<true, false, true>;
+    case GatherForm::NONE: break;
+    }
+    return gather_kernel<true, false, false>;
+}
+
 extern "C" int mr_render_backward(const float* faces, const float* textures,
                                   const int32_t* face_index_map, const float* rgb_img,
                                   const float* alpha_img, const float* grad_rgb_img,
@@ -2430,77 +2386,66 @@ extern "C" int mr_render_backward(const float* faces, const float* textures,
     if (!faces || !face_index_map) return MR_ERR_BADARG;
     if (grad_textures && (!return_rgb || !grad_rgb_img || texture_size < 2)) return MR_ERR_BADARG;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nfaces = (int64_t)batch_size * num_faces;
-    const int64_t npx = (int64_t)batch_size * image_size * image_size;
-    int rc = MR_OK;
-
-    // D: pixel-map term (writes all 9 slots of every face row)
-    const bool want_d = grad_faces && ((return_rgb && grad_rgb_img && rgb_img) ||
-                                       (return_alpha && grad_alpha_img && alpha_img));
-    const bool want_f = grad_faces && return_depth && grad_depth_img;
-    const bool gather_tex = grad_textures && texture_size == 2 && eps >= 1e-6f && !(flags & 1);
-    const bool run_gather = (gather_tex || grad_faces) && (gather_tex || want_f || !want_d);
-    // with a workspace the faces that own a pixel are listed once (kernel D needs the list anyway) and the gather
-    // walks only those: the others -- four fifths of a hand + object mesh -- get their zero rows when the list is built
-    const bool strips_d = strips_apply(batch_size, num_faces, image_size, workspace, workspace_bytes, flags);
-    const bool use_list = want_d ? strips_d
-                                 : (workspace && workspace_bytes >= owner_list(nullptr, batch_size, num_faces).bytes &&
-                                    !(flags & MR_FLAG_REFERENCE_ALGO) && nfaces <= 0xffffffffLL);
+    // plan
+    BackwardRequest req{};
+    req.B = batch_size; req.F = num_faces; req.is = image_size; req.ts = texture_size; req.flags = flags; req.eps = eps;
+    req.grad_faces = grad_faces != nullptr; req.grad_textures = grad_textures != nullptr;
+    req.rgb = return_rgb && grad_rgb_img && rgb_img; req.alpha = return_alpha && grad_alpha_img && alpha_img;
+    req.depth = return_depth && grad_depth_img;
+    req.workspace_bytes = workspace ? workspace_bytes : 0;
+    req.list_bytes = owner_list(nullptr, batch_size, num_faces).bytes;
+    req.full_bytes = pixel_map_workspace_bytes(batch_size, num_faces, image_size);
+    const BackwardPlan plan = plan_render_backward(req);
     // the E / F gather of the faces that own a pixel (or of all of them without a list)
     GatherParams g{};
     g.faces = faces; g.fim = face_index_map;
-    g.grad_rgb = gather_tex ? grad_rgb_img : nullptr;
-    g.grad_depth = want_f ? grad_depth_img : nullptr;
+    g.grad_rgb = plan.gather_tex ? grad_rgb_img : nullptr;
+    g.grad_depth = plan.want_f ? grad_depth_img : nullptr;
     g.grad_faces = grad_faces;
-    g.grad_textures = gather_tex ? grad_textures : nullptr;
+    g.grad_textures = plan.gather_tex ? grad_textures : nullptr;
     g.B = batch_size; g.F = num_faces; g.is = image_size; g.eps = eps;
-    g.accumulate_faces = want_d ? 1 : 0;
-    if (use_list) {
-        const OwnerList ol = owner_list(workspace, batch_size, num_faces);
-        g.owners = ol.list; g.n_owners = ol.counter;
-    }
-    const int64_t gather_threads = nfaces * GGL;
-    auto launch_gather = [&](hipStream_t gs) -> int {
-        if (gather_tex && want_f) return launch1d(gather_kernel<true, true, true>, gather_threads, gs, g);
-        if (gather_tex) return launch1d(gather_kernel<true, true, false>, gather_threads, gs, g);
-        if (want_f) return launch1d(gather_kernel<true, false, true>, gather_threads, gs, g);
-        return launch1d(gather_kernel<true, false, false>, gather_threads, gs, g);
-    };
-    bool gathered = false;
-    if (want_d) {
-        const int rr = return_rgb && grad_rgb_img && rgb_img, ra = return_alpha && grad_alpha_img && alpha_img;
-        PixelMapParams p{faces, face_index_map, rgb_img, alpha_img, grad_rgb_img, grad_alpha_img,
-                         grad_faces, batch_size, num_faces, image_size, eps, rr, ra, 1, (flags & MR_FLAG_COUNT_PIXEL_MAP_TERMS) ? 1 : 0};
-        p.zero_textures = (use_list && run_gather && gather_tex) ? grad_textures : nullptr;
-        // Round 5: kernel D's walk and the E / F gather go out as ONE launch when both run over the owner lists
-        // (strip_gather_kernel)
-        FusedGather fg{g, gather_tex, want_f, gather_threads};
-        const bool fuse = use_list && strips_d && run_gather && (gather_tex || want_f);
-        rc = launch_pixel_map<true>(p, workspace, workspace_bytes, flags, s, fuse ? &fg : nullptr, &gathered);
+    g.accumulate_faces = plan.accumulate_faces ? 1 : 0;
+    const OwnerList ol = owner_list(workspace, batch_size, num_faces);
+    if (plan.use_list) { g.owners = ol.list; g.n_owners = ol.counter; }
+    // launch
+    int rc = MR_OK;
+    if (plan.want_d) {
+        PixelMapParams p{};  // (value-initialised, then filled: the padding bytes are kernel-argument bytes too)
+        p.faces = faces; p.fim = face_index_map; p.rgb = rgb_img; p.alpha = alpha_img; p.grad_rgb = grad_rgb_img; p.grad_alpha = grad_alpha_img;
+        p.grad_faces = grad_faces; p.B = batch_size; p.F = num_faces; p.is = image_size; p.eps = eps;
+        p.return_rgb = req.rgb; p.return_alpha = req.alpha; p.write_backfacing = 1; p.count_terms = plan.count_terms ? 1 : 0;
+        p.zero_textures = plan.zero_textures_in_d ? grad_textures : nullptr;
+        rc = launch_pixel_map<true>(plan.pixel_map, p, workspace, s, &g);
         if (rc != MR_OK) return rc;
-    } else if (use_list && run_gather) {
-        const OwnerList ol = owner_list(workspace, batch_size, num_faces);
+    } else if (plan.list_only) {
         hipError_t e = hipMemsetAsync(ol.owns, 0, ol.clear_bytes, s);  // flags and the counts behind them
         if (e != hipSuccess) return (int)e;
-        rc = launch_mark_owners(face_index_map, ol.owns, batch_size, image_size, num_faces, nullptr, 0, s);
+        rc = launch_mark_owners(plan.mark, face_index_map, ol.owns, num_faces, nullptr, 0, s);
         if (rc != MR_OK) return rc;
         PixelMapParams q{};
         q.faces = faces; q.grad_faces = grad_faces; q.B = batch_size; q.F = num_faces; q.is = image_size;
         q.write_backfacing = 1;
-        q.zero_textures = gather_tex ? grad_textures : nullptr;
-        rc = launch_compact(q, ol, false, s);
+        q.zero_textures = plan.zero_textures_in_list ? grad_textures : nullptr;
+        rc = launch_compact(plan.compact, q, ol, false, s);
         if (rc != MR_OK) return rc;
     }
-    if (grad_textures && !gather_tex) {
-        const size_t bytes = (size_t)nfaces * texture_size * texture_size * texture_size * 3 * sizeof(float);
-        hipError_t e = hipMemsetAsync(grad_textures, 0, bytes, s);
+    if (plan.tex_atomics) {
+        hipError_t e = hipMemsetAsync(grad_textures, 0, plan.tex_bytes, s);
         if (e != hipSuccess) return (int)e;
-        rc = launch1d(textures_atomic_recompute_kernel<true>, npx, s, faces, face_index_map, grad_rgb_img,
-                      grad_textures, npx, num_faces, image_size, texture_size, eps);
+        rc = launch1d(textures_atomic_recompute_kernel<true>, plan.tex_threads, s, faces, face_index_map, grad_rgb_img, grad_textures,
+                      plan.tex_threads, num_faces, image_size, texture_size, eps);
         if (rc != MR_OK) return rc;
     }
-    if (run_gather && !gathered) rc = launch_gather(s);
+    if (plan.gather_threads > 0) rc = launch1d(gather_kernel_of(plan.gather_form), plan.gather_threads, s, g);
     return rc;
+}
+
+// fills the gather's fields INSIDE a value-initialised block: its padding bytes are kernel-argument bytes too, and a
+// list-initialised temporary leaves them to the stack
+static void fill_gather_vc(GatherVCParams& g, const float* verts, const int32_t* fidx, const int32_t* fim, const float* grad_rgb,
+                           float* grad_vcolors, int B, int V, int F0, int fill_back, int is, float eps, int texel) {
+    g.verts = verts; g.fidx = fidx; g.fim = fim; g.grad_rgb = grad_rgb; g.grad_vcolors = grad_vcolors;
+    g.B = B; g.V = V; g.F0 = F0; g.fill_back = fill_back; g.is = is; g.eps = eps; g.texel = texel;
 }
 
 extern "C" int mr_render_vc_backward(const float* verts, const int32_t* faces_idx, const int32_t* face_index_map,
@@ -2515,22 +2460,22 @@ extern "C" int mr_render_vc_backward(const float* verts, const int32_t* faces_id
     if (e != hipSuccess) return (int)e;
     if (num_faces == 0) return MR_OK;
     if (!verts || !faces_idx || !face_index_map || !grad_rgb_img || !(eps >= 1e-6f)) return MR_ERR_BADARG;
-    GatherVCParams g{verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces,
-                     fill_back, image_size, eps, texel_layout};
-    // pixel-parallel scatter when the per-image colour table fits LDS (MR_FLAG_FORCE_GATHER: the gather)
-    const int64_t table_bytes = (((int64_t)num_verts * 3 + 1) / 2) * 16;
-    if (table_bytes <= SV_MAX_TABLE_BYTES && !(flags & MR_FLAG_FORCE_GATHER)) {
-        ScatterVCParams sp{g, weight_map, depth_img, (image_size + SV_W - 1) / SV_W, (image_size + SV_H - 1) / SV_H};
-        const int64_t blocks = (int64_t)batch_size * sp.rx_n * sp.ry_n;
-        if (!grid_ok(blocks)) return MR_ERR_BADARG;
+    ScatterVCParams sp{};
+    fill_gather_vc(sp.g, verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces, fill_back, image_size, eps,
+                   texel_layout);
+    sp.weight = weight_map; sp.depth = depth_img;
+    const GatherVCParams& g = sp.g;
+    const ScatterVCPlan plan = plan_scatter_vc(batch_size, num_verts, num_faces, image_size, flags);
+    if (plan.status != MR_OK) return plan.status;
+    if (plan.scatter) {
+        sp.rx_n = plan.rx_n; sp.ry_n = plan.ry_n;
         const bool stored = weight_map && depth_img;
-        hipLaunchKernelGGL(stored ? scatter_vc_kernel<true> : scatter_vc_kernel<false>, dim3((unsigned)blocks),
-                           dim3(SV_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
+        hipLaunchKernelGGL(stored ? scatter_vc_kernel<true> : scatter_vc_kernel<false>, dim3(plan.wgs), dim3(SV_WAVES * MR_WAVE), plan.lds, s,
+                           sp);
         MR_CHECK_LAUNCH();
         return MR_OK;
     }
-    if (image_size > 8192) return MR_ERR_BADARG;  // gather fragment encoding: 13 bits per bbox offset
-    return launch1d(gather_vc_kernel<0>, (int64_t)batch_size * num_faces * GLPF, s, g);
+    return launch1d(gather_vc_kernel<0>, plan.gather_threads, s, g);
 }
 
 // ---- the tile-scatter launches: mr_render_flow_backward, mr_flow_pair_backward_tiles, mr_flow_pair_backward_unit_tiles ----
@@ -2552,21 +2497,10 @@ static int launch_scatter_tiles(ScatterTilesParams& sp, int flags, bool pairs, b
     }
     if (g.F0 == 0) return MR_OK;
     if (!g.fim || !sp.weight || !(g.eps >= 1e-6f) || !maps_ok) return MR_ERR_BADARG;
-    // the tile walk reads 4-pixel groups with 16-byte loads and keeps the colour table in LDS: three sums per vertex for a
-    // colour-space gradient, two for a flow-space one
-    const int64_t table_bytes = (((int64_t)g.V * (g.grad_rgb ? 3 : 2) + 1) / 2) * 16;
-    sp.tiles_x = (g.is + ST_TW - 1) / ST_TW; sp.tiles_y = (g.is + ST_TH - 1) / ST_TH;
-    if (g.is % 4 != 0 || table_bytes > SV_MAX_TABLE_BYTES || (int64_t)sp.tiles_x * sp.tiles_y > ST_MAX_TILES) return MR_ERR_NOTIMPL;
-    // workgroups per image.  mr_render_flow_backward: ST_G.  The pair launches walk a workgroup's covered tiles a wave (the
-    // pair loss's backward, pass 1: two tiles, one behind the other) at a time, and larger rasters have more of them per image
-    // (a sixth of 256 / 900 / 1600 tiles), so they get more workgroups, ~8 tiles each: 8 / 32 / 32.  A 480 x 480 pair at
-    // B = 8: 73 -> 46 us (mr_flow_pair_backward_tiles), 30 -> 19 us (_unit_tiles) with 32 instead of 8; 640 x 640 at B = 32:
-    // 86 -> 74 us cold (_unit_tiles)
-    sp.groups = ST_G;
-    while (pairs && sp.groups < 32 && sp.tiles_x * sp.tiles_y > 48 * sp.groups) sp.groups *= 2;
-    const int64_t blocks = (int64_t)g.B * sp.groups;
-    if (!grid_ok(blocks)) return MR_ERR_BADARG;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(ST_WAVES * MR_WAVE), (size_t)table_bytes, s, sp);
+    const ScatterPlan plan = plan_scatter_tiles(g.B, g.V, g.is, g.grad_rgb != nullptr, pairs);
+    if (plan.status != MR_OK) return plan.status;
+    sp.tiles_x = plan.tiles_x; sp.tiles_y = plan.tiles_y; sp.groups = plan.groups;
+    hipLaunchKernelGGL(kernel, dim3(plan.wgs), dim3(ST_WAVES * MR_WAVE), plan.lds, s, sp);
     MR_CHECK_LAUNCH();
     return MR_OK;
 }
@@ -2581,8 +2515,8 @@ extern "C" int mr_render_flow_backward(const float* verts, const int32_t* faces_
                                        mr_stream_t stream) {
     const bool flowgrad = grad_rgb_img == nullptr;
     ScatterTilesParams sp{};
-    sp.g = GatherVCParams{verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces,
-                          fill_back, image_size, eps, texel_layout};
+    fill_gather_vc(sp.g, verts, faces_idx, face_index_map, grad_rgb_img, grad_vcolors, batch_size, num_verts, num_faces, fill_back, image_size, eps,
+                   texel_layout);
     sp.weight = weight_map; sp.depth = depth_img; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.grad_flow = grad_flow; sp.m_pre = mask_pre; sp.m_x_lo = mask_x_lo; sp.m_x_hi = mask_x_hi; sp.occl = occl;
     sp.split = split; sp.H = height; sp.W = width;
@@ -2606,8 +2540,8 @@ extern "C" int mr_flow_pair_backward_tiles_crit(const int32_t* face_index_map, c
                                                 int texel_layout, mr_stream_t stream, int criterion) {
     if (!criterion_ok(criterion)) return MR_ERR_BADARG;
     ScatterTilesParams sp{};
-    sp.g = GatherVCParams{nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces,
-                          fill_back, image_size, eps, texel_layout};
+    fill_gather_vc(sp.g, nullptr, nullptr, face_index_map, nullptr, grad_vcolors, batch_size, num_verts, num_faces, fill_back, image_size, eps,
+                   texel_layout);
     sp.weight = weight_map; sp.tile_hit = tile_hit; sp.vid_map = vertex_id_map;
     sp.m_pre = mask_pre; sp.m_x_lo = mask_x_lo; sp.m_x_hi = mask_x_hi; sp.occl = occl;
     sp.split = batch_size / 2; sp.H = height; sp.W = width;
@@ -2640,8 +2574,8 @@ extern "C" int mr_flow_pair_backward_tiles(const int32_t* face_index_map, const 
 
 int mr::launch_unit_scatter_tiles(const UnitScatterArgs& a, hipStream_t s) {
     ScatterTilesParams sp{};
-    sp.g = GatherVCParams{nullptr, nullptr, a.face_index_map, nullptr, a.grad_vcolors, a.batch_size, a.num_verts, a.num_faces,
-                          a.fill_back, a.image_size, a.eps, a.texel_layout};
+    fill_gather_vc(sp.g, nullptr, nullptr, a.face_index_map, nullptr, a.grad_vcolors, a.batch_size, a.num_verts, a.num_faces, a.fill_back,
+                   a.image_size, a.eps, a.texel_layout);
     sp.weight = a.weight_map; sp.tile_hit = a.tile_hit; sp.vid_map = a.vertex_id_map;
     sp.split = a.batch_size / 2; sp.H = a.height; sp.W = a.width;
     sp.unit_grad = a.unit_grad; sp.unit_max = a.unit_grad_max; sp.sums = a.sums; sp.gl_fwd = a.grad_loss_fwd; sp.gl_bwd = a.grad_loss_bwd;

@@ -55,8 +55,7 @@
 
 namespace mr {
 
-constexpr int TILE_W = 32, TILE_H = 8;  // tile size in pixels (one pixel per thread)
-constexpr int TPB = 256;              // threads per workgroup (4 waves)
+// (TILE_W x TILE_H pixels per tile, TPB threads per workgroup: launch_plan.hpp)
 constexpr int NB = 32;                // faces per batch (stage S1: one lane per face).  48 and 64 were measured (one
                                       // batch per wave for the ~145 faces of a typical geometry tile): the larger face
                                       // cache costs occupancy (5 / 4 instead of 7 waves per SIMD) and the kernel gets slower
@@ -101,36 +100,15 @@ __device__ __forceinline__ int wave_max(int v) {
     return v;
 }
 
-constexpr int BIN_TPB = 1024;         // bin_boxes_kernel: one workgroup per image
-constexpr int MAX_BINS = 8192;        // LDS counters (32 KB)
+// (BIN_TPB threads per workgroup of the binning pass, MAX_BINS LDS counters: launch_plan.hpp)
 constexpr int SMALL_MAX_BINS = 8;     // a face overlapping more bins goes to the image's large list
 constexpr int REC_CAP = SMALL_MAX_BINS + 1;  // record capacity per image, in units of F: 8 F binned + F large
-constexpr int MAX_PARTS_DEV = 16;            // most workgroups per image of the binning pass (= MAX_PARTS of launch_bins)
+constexpr int MAX_PARTS_DEV = 16;            // most workgroups per image of the binning pass (= MAX_PARTS of plan_bins)
+static_assert(MAX_PARTS_DEV == MAX_PARTS, "the parts' exchange unrolls over the most parts a plan hands out");
+static_assert(TILE_W * TILE_H == TPB, "one pixel per thread");
 constexpr int ARRIVE_STRIDE = 32;            // words between the arrival counters of two images
 
-// PROLOGUE (pair steps): the parts of an image split its faces AT the hand / object boundary -- Kh parts share the Fh hand faces,
-// K - Kh the Fo object faces, in proportion -- so that a part needs only the vertices of ITS side in LDS (hand faces index the
-// hand's vertices, object faces the object's: warpbranch.py:49-55, the contract of the stacked mesh): one trip of the vertex
-// stage per part instead of two at the metric workload.  Returns the part's real faces [r0, r0 + nr) and its side (0 hand, 1 object,
-// -1: no split -- one part, or a mesh with one side only).
-__host__ __device__ inline int pair_part_range(int part, int K, int Fh, int Fo, int& r0, int& nr) {
-    const int F0 = Fh + Fo;
-    if (K < 2 || Fh <= 0 || Fo <= 0) {
-        r0 = (int)((int64_t)F0 * part / K); nr = (int)((int64_t)F0 * (part + 1) / K) - r0;
-        return -1;
-    }
-    int Kh = (int)(((int64_t)K * Fh + F0 / 2) / F0);
-    Kh = Kh < 1 ? 1 : (Kh > K - 1 ? K - 1 : Kh);
-    if (part < Kh) {
-        r0 = (int)((int64_t)Fh * part / Kh); nr = (int)((int64_t)Fh * (part + 1) / Kh) - r0;
-        return 0;
-    }
-    const int q = part - Kh, Ko = K - Kh;
-    r0 = (int)((int64_t)Fo * q / Ko); nr = (int)((int64_t)Fo * (q + 1) / Ko) - r0;
-    r0 += Fh;
-    return 1;
-}
-
+// (pair_part_range, the split of a pair step's parts at the hand / object boundary: launch_plan.hpp)
 struct BinParams {
     const float* faces;      // !VC: [B,F,3,3]
     const float* verts;      // VC: [B,V,3]
@@ -1417,56 +1395,64 @@ __global__ void __launch_bounds__(256) face_inv_map_kernel(const float* __restri
 // workspace layout: [B] ImageHdr | [B * nbins] BinHdr | [B * F] FaceBox | [B * REC_CAP * F] FaceRec | [B * F] RecVerts
 // | TileList | [B * tiles] tile ids    (every byte the tile kernel reads is written by the two setup kernels: no memset)
 struct WorkLayout {
-    int nbx, nby, ysh;
-    int parts;  // workgroups per image of the binning pass (bin_boxes_kernel, PARTS)
+    BinGrid grid;
+    int parts;  // workgroups per image of the binning pass the workspace has counters for (bin_layout_parts)
     size_t off_bins, off_boxes, off_recs, off_rverts, off_tlist, off_arrive, off_tile_ids, off_bg, off_part_cnt, total;
 };
+static_assert(sizeof(FaceBox) == FACE_BOX_BYTES, "plan_bins sizes the LDS copy of a part's boxes");
 
-// Workgroups per image of the binning pass: the largest power of two (<= 16) that keeps B x parts within the device's
-// compute units -- every workgroup of the launch resident at once, which the parts' barrier relies on -- and leaves a part
-// at least 256 faces.  Phase stamps (profiles/r05_binning_parts.txt): the exchange costs a part
-// ~2.5 us (publish 0.4, barrier 0.8, the other parts' counters 1.4) once it stays inside the XCD's L2; 16 renders of 480 x 480
-// (config 3, the reference's default batch size) 19.5 -> 13.9 us per workgroup, 64 renders 19.6 -> 16.6, 128 renders 21.7 -> ~19.
+// the device's compute units, asked once per device
+static int current_device() {
+    int dev = 0;
+    return (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) ? dev : -1;
+}
 static int device_cus() {
     static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    const int dev = current_device();
+    if (dev < 0) return 0;
     if (cus[dev] == 0) {
         int n = 0;
         cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : -1;
     }
     return cus[dev] > 0 ? cus[dev] : 0;
 }
-constexpr int MAX_PARTS = MAX_PARTS_DEV, MAX_PART_CUS = 256;
-static int bin_parts(int B, int F, int cus, int per_cu = 2) {
-    int k = 1;
-    while (k < MAX_PARTS && (int64_t)B * k * 2 <= (int64_t)per_cu * cus && F / (k * 2) >= 256) k *= 2;
-    return k;
-}
 
 static WorkLayout work_layout(int B, int F, int is) {
     WorkLayout w;
-    const int tiles_x = (is + TILE_W - 1) / TILE_W, tiles_y = (is + TILE_H - 1) / TILE_H;
-    w.nbx = tiles_x;
-    w.ysh = 0;
-    while ((int64_t)tiles_x * ((tiles_y + (1 << w.ysh) - 1) >> w.ysh) > MAX_BINS) w.ysh++;
-    w.nby = (tiles_y + (1 << w.ysh) - 1) >> w.ysh;
+    w.grid = bin_grid(is);
+    const int64_t tiles = (int64_t)w.grid.tiles_x * w.grid.tiles_y;
     Carve c;
     c.take((size_t)B * sizeof(ImageHdr));  // the image headers, at the base
-    w.off_bins = c.take((size_t)B * w.nbx * w.nby * sizeof(BinHdr));
+    w.off_bins = c.take((size_t)B * w.grid.nbins() * sizeof(BinHdr));
     w.off_boxes = c.take((size_t)B * F * sizeof(FaceBox));
     w.off_recs = c.take((size_t)B * REC_CAP * F * sizeof(FaceRec));
     w.off_rverts = c.take((size_t)B * F * sizeof(RecVerts));  // (VC needs F / 2 of it with fill-back)
     // (the images' arrival counters sit right behind the list header: ONE region for the caller of MR_FLAG_TILE_LIST_CLEARED to clear)
     w.off_tlist = c.take(sizeof(TileList));
     w.off_arrive = c.take((size_t)B * ARRIVE_STRIDE * sizeof(unsigned));
-    w.off_tile_ids = c.take((size_t)2 * B * tiles_x * tiles_y * sizeof(uint4));  // heavy part | light part
-    w.off_bg = c.take((size_t)B * tiles_x * tiles_y * sizeof(uint32_t));  // dense listed launches: ids of the tiles off the list
-    // (sized for a 256-CU device, the most launch_bins assumes: the layout must not depend on the device at hand)
-    w.parts = bin_parts(B, F, MAX_PART_CUS);
-    w.off_part_cnt = c.take(w.parts > 1 ? (size_t)B * w.parts * ((w.nbx * w.nby + 4 + 31) & ~31) * sizeof(int) : 0);
+    w.off_tile_ids = c.take((size_t)2 * B * tiles * sizeof(uint4));  // heavy part | light part
+    w.off_bg = c.take((size_t)B * tiles * sizeof(uint32_t));  // dense listed launches: ids of the tiles off the list
+    w.parts = bin_layout_parts(B, F);
+    w.off_part_cnt = c.take(w.parts > 1 ? (size_t)B * w.parts * part_counter_words(w.grid) * sizeof(int) : 0);
     w.total = c.total();
     return w;
+}
+
+// dynamic LDS beyond the default limit is an opt-in of a kernel on a device, raised for the eight binning kernels at once the
+// first time a plan asks for it there.  One guard per instantiation of the launcher (`vc` or not) keeps the recorded sequence of
+// attribute calls stable: the second instantiation's eight calls repeat the first's.  Without a known device (dev < 0) nothing
+// is remembered and the eight calls go out with every launch that needs them
+static int raise_bin_lds_limit(bool vc, std::initializer_list<const void*> kernels) {
+    static bool raised_by[2][64] = {{false}};
+    bool* raised = raised_by[vc ? 1 : 0];
+    const int dev = current_device();
+    if (dev >= 0 && raised[dev]) return MR_OK;
+    for (const void* f : kernels) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (dev >= 0) raised[dev] = true;
+    return MR_OK;
 }
 
 // per-face records + boxes (pass A), bin lists (pass B); fills the record-source fields of `fp`
@@ -1480,19 +1466,27 @@ template <bool VC>
 static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int F, int is, hipStream_t s, int flags,
                        uint8_t* tile_hit = nullptr, bool dense_list = false, bool list_cleared = false,
                        const PairPrologue* pro = nullptr) {
+    // plan
+    BinRequest req{};
+    req.vc = VC; req.B = B; req.F = F; req.F0 = bp.F0; req.V = bp.V; req.fill_back = bp.fill_back != 0; req.is = is; req.flags = flags;
+    req.cus = (flags & MR_FLAG_ONE_WORKGROUP_PER_IMAGE) ? 0 : device_cus();
+    req.want_list = tile_hit || dense_list; req.list_cleared = list_cleared;
+    req.pair = pro != nullptr; req.Fh = pro ? pro->f.Fh : 0; req.Fo = pro ? pro->f.Fo : 0;
+    const BinPlan plan = plan_bins(req);
+    if (plan.status != MR_OK) return plan.status;
+    // the parameter blocks
     const WorkLayout w = work_layout(B, F, is);
-    if (w.nbx > MAX_BINS) return MR_ERR_BADARG;  // (image_size <= 16384 keeps a row of bins within the counters)
     char* base = (char*)workspace;
     if (dense_list) {
         bp.bg_ids = (uint32_t*)(base + w.off_bg);
         fp.bg_ids = bp.bg_ids;
         tile_hit = (uint8_t*)bp.bg_ids;  // (not written in this mode: any non-null value asks for the list)
     }
-    if (tile_hit && w.ysh == 0 && grid_ok((int64_t)B * w.nbx * w.nby)) {
+    if (plan.list) {
         bp.tlist = (TileList*)(base + w.off_tlist);
         bp.tile_ids = (uint4*)(base + w.off_tile_ids);
         bp.tile_hit = tile_hit;
-        bp.tile_cap = (int64_t)B * w.nbx * w.nby;
+        bp.tile_cap = plan.tile_cap;
         fp.tlist = bp.tlist; fp.tile_ids = bp.tile_ids; fp.tile_cap = (unsigned)bp.tile_cap;
     }
     bp.hdrs = (ImageHdr*)base;
@@ -1500,130 +1494,71 @@ static int launch_bins(BinParams bp, FwdParams& fp, void* workspace, int B, int 
     bp.boxes = (FaceBox*)(base + w.off_boxes);
     bp.recs = (FaceRec*)(base + w.off_recs);
     bp.rverts = (RecVerts*)(base + w.off_rverts);
-    bp.F = F; bp.is = is; bp.nbx = w.nbx; bp.nby = w.nby; bp.ysh = w.ysh;
-    const int nbins = w.nbx * w.nby;
-    // parts per image (bin_boxes_kernel, PARTS): B x parts workgroups, all resident at once; MR_FLAG_ONE_WORKGROUP_PER_IMAGE: one
-    // (at most one workgroup per compute unit: two per compute unit were measured at 2B = 128: 37.7 us against 28.9 with two
-    // parts and 28.5 with one; config 3's 16 renders: 16 parts 23.1 us, one part 26.0)
-    int parts = (flags & MR_FLAG_ONE_WORKGROUP_PER_IMAGE) ? 1 : bin_parts(B, F, std::min(device_cus(), MAX_PART_CUS), 1);
-    if (parts > w.parts) parts = w.parts;
-    // (list_cleared: the caller cleared the tile list's header on this stream -- what the per-face pass's first thread does)
-    const bool fused_records = VC && list_cleared && bp.tlist && bp.F0 > 0;
-    // The parts pay where they split the PER-FACE pass (fused_records: 64 renders of 256 x 256 22.1 us with 4 parts against 24.3
-    // with one, 16 renders of 480 x 480 21.9 / 24.5, 64 of 640 x 640 31.1 / 35.5; 128 renders: 28.3 / 28.5).  With the boxes
-    // already in memory a part only saves counting, and the exchange costs more than that unless the bins are many: 128 renders
-    // of 256 x 256 19.6 us with two parts, 17.8 with one; 64 renders 16.9 / 15.6; 16 of 480 x 480 18.3 / 17.5; 64 of 640 x 640
-    // (1600 bins) 26.2 / 27.9 (round 6, rocprofv3 over `bench.py --kernels-only` / scripts/hot_only.py).
-    if (!fused_records && nbins <= 1024 && !(flags & MR_FLAG_FORCE_PARTS)) parts = 1;
-    bp.B = B; bp.parts = parts;
+    bp.F = F; bp.is = is; bp.nbx = plan.grid.nbx; bp.nby = plan.grid.nby; bp.ysh = plan.grid.ysh;
+    bp.B = B; bp.parts = plan.parts;
     bp.part_cnt = (int*)(base + w.off_part_cnt);
     bp.arrive = (unsigned*)(base + w.off_arrive);
-    size_t lds = (size_t)((nbins + 3) & ~3) * sizeof(int);
-    // (boxes of the largest part: its share of the real faces in both orientations, or of the virtual faces)
-    int box_cap = (F + parts - 1) / parts + 2;
-    if (pro) {  // (the parts of a pair step split at the hand / object boundary: pair_part_range)
-        int most = 0;
-        for (int k = 0; k < parts; k++) {
-            int r0, nr;
-            pair_part_range(k, parts, pro->f.Fh, pro->f.Fo, r0, nr);
-            most = std::max(most, nr);
-        }
-        box_cap = std::max(box_cap, (bp.fill_back ? 2 * most : most) + 2);
-    }
-    bp.box_cap = box_cap;
-    bp.split_fh = pro ? pro->f.Fh : 0; bp.split_fo = pro ? pro->f.Fo : 0;
-    const size_t box_lds = (size_t)box_cap * sizeof(FaceBox);
-    bp.lds_boxes = (lds + box_lds <= 152 * 1024) ? 1 : 0;
-    if (bp.lds_boxes) lds += box_lds;
+    bp.box_cap = plan.box_cap;
+    bp.split_fh = req.Fh; bp.split_fo = req.Fo;
+    bp.lds_boxes = plan.lds_boxes;
     fp.hdrs = bp.hdrs; fp.bins = bp.bins; fp.recs = bp.recs; fp.rverts = bp.rverts;
-    fp.nbx = w.nbx; fp.nby = w.nby; fp.ysh = w.ysh;
-    if (B == 0) return MR_OK;
-    if (B > 65535) return MR_ERR_BADARG;
-    const bool fused_records_ok = fused_records && bp.lds_boxes;
-    bool pro_fused = false;
-    if (pro) {
-        const size_t v_lds = (size_t)bp.V * 3 * sizeof(float);
-        if (VC && fused_records_ok && (B & 1) == 0 && lds + v_lds <= 152 * 1024) {
-            pro_fused = true;
-            lds += v_lds;
-        } else {
-            const int rc = mr_launch_pair_prologue(*pro, s);
-            if (rc != MR_OK) return rc;
-        }
+    fp.nbx = plan.grid.nbx; fp.nby = plan.grid.nby; fp.ysh = plan.grid.ysh;
+    if (!plan.launch) return MR_OK;
+    // launch
+    if (plan.prologue == BinPlan::PRO_SEPARATE) {
+        const int rc = mr_launch_pair_prologue(*pro, s);
+        if (rc != MR_OK) return rc;
     }
-    if (fused_records_ok) {
-        // nothing: the per-face pass runs inside the binning kernel
-    } else if (bp.F0 > 0) {
-        hipLaunchKernelGGL((face_records_kernel<VC>), dim3(blocks1d(bp.F0), (unsigned)B), dim3(256), 0, s,
-                           bp);
+    switch (plan.faces) {
+    case BinPlan::FACES_LAUNCH:
+        hipLaunchKernelGGL((face_records_kernel<VC>), dim3(plan.face_blocks, plan.images), dim3(256), 0, s, bp);
         MR_CHECK_LAUNCH();
-    } else if (bp.tlist) {
-        // no face, no per-face pass: the list counters that pass clears (thread 0 of image 0) are cleared here, before
-        // the binning pass adds to them -- an empty mesh gives an empty list, not whatever the workspace held
+        break;
+    case BinPlan::FACES_CLEAR_LIST: {
         hipError_t e = hipMemsetAsync(bp.tlist, 0, sizeof(TileList), s);
         if (e != hipSuccess) return (int)e;
+        break;
     }
-    static size_t allowed = 48 * 1024;  // dynamic LDS beyond the default limit is an opt-in, raised on demand
-    if (lds > allowed) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_boxes_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bin_boxes_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        const void* more[] = {reinterpret_cast<const void*>(&bin_boxes_prologue_kernel), reinterpret_cast<const void*>(&bin_count_prologue_kernel),
-                              reinterpret_cast<const void*>(&bin_count_kernel<false>), reinterpret_cast<const void*>(&bin_count_kernel<true>),
-                              reinterpret_cast<const void*>(&bin_fill_kernel<false>), reinterpret_cast<const void*>(&bin_fill_kernel<true>)};
-        for (const void* f : more)
-            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-        if (e != hipSuccess) return (int)e;
-        allowed = 152 * 1024;
+    case BinPlan::FACES_IN_KERNEL:
+    case BinPlan::FACES_NONE:
+        break;
     }
-    // (parts > 1: workgroup i = part (i / 8) % parts of image (i / 8 / parts) * 8 + i % 8 -- an image's parts on one XCD)
-    const unsigned grid = parts > 1 ? (unsigned)((B + 7) / 8) * 8u * (unsigned)parts : (unsigned)B;
-    // (eight parts or more: the parts' exchange across a kernel boundary -- count launch, fill launch.  Measured on one box, pair
-    // steps, device time per hot-path pass: 16 renders of 480 x 480 in 16 parts 27.7 us as one launch, 13.0 + 8.7 as two (0.097 ->
-    // 0.092 ms); 32 renders in 8 parts and 64 in 4: no difference (0.0811 / 0.0818, 0.1109 / 0.1112); 128 renders of 256 x 256 in
-    // 2 parts 33.4 against 22.4 + 13.1 -- with few parts the last arriver's serial share is small and the second launch's floor
-    // is not.  MR_FLAG_PARTS_IN_ONE_LAUNCH: the last-arriver form whatever the parts)
-    const bool two_launches = parts >= 8 && !(flags & MR_FLAG_PARTS_IN_ONE_LAUNCH);
-    if (two_launches) {
-        if (pro_fused) hipLaunchKernelGGL(bin_count_prologue_kernel, dim3(grid), dim3(BIN_TPB), lds, s, bp, *pro);
-        else if (fused_records_ok) hipLaunchKernelGGL(bin_count_kernel<true>, dim3(grid), dim3(BIN_TPB), lds, s, bp);
-        else hipLaunchKernelGGL(bin_count_kernel<false>, dim3(grid), dim3(BIN_TPB), lds, s, bp);
-        MR_CHECK_LAUNCH();
-        const size_t lds2 = (size_t)((nbins + 3) & ~3) * sizeof(int);  // (counters only: the fill launch keeps no boxes in LDS)
-        if (fused_records_ok) hipLaunchKernelGGL(bin_fill_kernel<true>, dim3(grid), dim3(BIN_TPB), lds2, s, bp);
-        else hipLaunchKernelGGL(bin_fill_kernel<false>, dim3(grid), dim3(BIN_TPB), lds2, s, bp);
-    } else if (pro_fused) hipLaunchKernelGGL(bin_boxes_prologue_kernel, dim3(grid), dim3(BIN_TPB), lds, s, bp, *pro);
-    else if (fused_records_ok) hipLaunchKernelGGL(bin_boxes_kernel<true>, dim3(grid), dim3(BIN_TPB), lds, s, bp);
-    else hipLaunchKernelGGL(bin_boxes_kernel<false>, dim3(grid), dim3(BIN_TPB), lds, s, bp);
+    // the binning pass's kernels: one launch or count + fill, each without and with the per-face pass inside (BinPlan::PLAIN,
+    // RECORDS), and the pair step's two with the vertex stage in front of that (PROLOGUE)
+    static_assert(BinPlan::PLAIN == 0 && BinPlan::RECORDS == 1, "the kernel tables are indexed by form");
+    void (*const boxes[])(BinParams) = {bin_boxes_kernel<false>, bin_boxes_kernel<true>};
+    void (*const count[])(BinParams) = {bin_count_kernel<false>, bin_count_kernel<true>};
+    void (*const fill[])(BinParams) = {bin_fill_kernel<false>, bin_fill_kernel<true>};
+    if (plan.lds_opt_in) {
+        const int rc = raise_bin_lds_limit(VC, {reinterpret_cast<const void*>(boxes[0]), reinterpret_cast<const void*>(boxes[1]),
+                                                reinterpret_cast<const void*>(&bin_boxes_prologue_kernel),
+                                                reinterpret_cast<const void*>(&bin_count_prologue_kernel), reinterpret_cast<const void*>(count[0]),
+                                                reinterpret_cast<const void*>(count[1]), reinterpret_cast<const void*>(fill[0]),
+                                                reinterpret_cast<const void*>(fill[1])});
+        if (rc != MR_OK) return rc;
+    }
+    const dim3 grid(plan.wgs), block(BIN_TPB);
+    if (plan.form == BinPlan::PROLOGUE)
+        hipLaunchKernelGGL(plan.two_launches ? bin_count_prologue_kernel : bin_boxes_prologue_kernel, grid, block, plan.lds, s, bp, *pro);
+    else
+        hipLaunchKernelGGL((plan.two_launches ? count : boxes)[plan.form], grid, block, plan.lds, s, bp);
     MR_CHECK_LAUNCH();
+    if (plan.two_launches) {
+        hipLaunchKernelGGL(fill[plan.form == BinPlan::PLAIN ? 0 : 1], grid, block, plan.lds_fill, s, bp);
+        MR_CHECK_LAUNCH();
+    }
     return MR_OK;
 }
 
-// `tile_bound` (listed launches): the caller's guess of the tile-list length = workgroups to dispatch; a longer list
-// is walked with a grid stride, surplus workgroups leave after one scalar load
+// the tile kernel over the whole screen, or over the tile list `p.tlist` with the caller's guess of its length (plan_tiles)
 template <bool FUSED, bool VC>
 static int launch_tiles(FwdParams& p, hipStream_t s, int64_t tile_bound = 0) {
+    const TilePlan plan = plan_tiles(p.B, p.is, p.tlist != nullptr, FUSED, tile_bound);
     if (p.rgb_channels == 0) p.rgb_channels = 3;
-    p.tiles_x = (p.is + TILE_W - 1) / TILE_W;
-    p.tiles_y = (p.is + TILE_H - 1) / TILE_H;
-    int64_t nblocks = (int64_t)p.B * p.tiles_x * p.tiles_y;
-    if (nblocks == 0) return MR_OK;
-    if (!grid_ok(nblocks)) return MR_ERR_BADARG;
-    if (p.tlist) {
-        // Listed launch: `bound` workgroups take one list entry each; whatever the list holds beyond the caller's guess
-        // is walked afterwards by the same workgroups (raster_overflow_tiles).
-        if (tile_bound <= 0) tile_bound = (nblocks + 3) / 4;
-        const int64_t bound = std::min<int64_t>(nblocks, std::max<int64_t>((tile_bound + 7) & ~(int64_t)7, 8));
-        if constexpr (FUSED) {
-            hipLaunchKernelGGL((raster_tile_kernel<FUSED, VC>), dim3((unsigned)bound), dim3(TPB), 0, s, p);
-            MR_CHECK_LAUNCH();
-            return MR_OK;
-        }
-        return MR_ERR_NOTIMPL;  // (no lists for the five-entry-point compatible path)
-    }
-    hipLaunchKernelGGL((raster_tile_kernel<FUSED, VC>), dim3((unsigned)nblocks), dim3(TPB), 0, s, p);
+    p.tiles_x = plan.tiles_x;
+    p.tiles_y = plan.tiles_y;
+    if (!plan.launch) return plan.status;
+    hipLaunchKernelGGL((raster_tile_kernel<FUSED, VC>), dim3(plan.wgs), dim3(TPB), 0, s, p);
     MR_CHECK_LAUNCH();
     return MR_OK;
 }
@@ -1641,15 +1576,6 @@ __global__ void __launch_bounds__(256) selftest_division_kernel(const float* __r
 }  // namespace mr
 
 using namespace mr;
-
-// Can a dense launch (every requested plane written for every pixel) go over the tile list?  Full tiles with 16-byte rows,
-// no per-pixel inverse map (the background stream does not write one), a raster whose bins are tiles.
-static bool dense_list_ok(int B, int F, int is, const float* face_inv_map, int flags) {
-    if ((flags & (MR_FLAG_REFERENCE_ALGO | MR_FLAG_TILE_PER_WORKGROUP)) || face_inv_map) return false;
-    if ((is % TILE_W) != 0 || (is % TILE_H) != 0) return false;
-    const WorkLayout w = work_layout(B, F, is);
-    return w.ysh == 0 && grid_ok((int64_t)B * w.nbx * w.nby);
-}
 
 // ... over the tile list: a quarter of the screen as the grid (a longer list is walked in rounds, surplus workgroups leave
 // after their share of the background), every workgroup streams its share of the tiles off the list first
@@ -1682,11 +1608,11 @@ extern "C" int mr_render_tile_list(const void* workspace, int batch_size, int nu
     if (batch_size < 0 || num_faces < 0 || image_size <= 0 || image_size > 16384) return MR_ERR_BADARG;
     const WorkLayout w = work_layout(batch_size, num_faces, image_size);
     // (a list is built when a bin is a tile and the global tile ids fit 31 bits: launch_bins)
-    if (w.ysh != 0 || !grid_ok((int64_t)batch_size * w.nbx * w.nby)) return MR_ERR_NOTIMPL;
+    if (!tile_list_ok(batch_size, w.grid)) return MR_ERR_NOTIMPL;
     const char* base = (const char*)workspace;
     *list_header = base + w.off_tlist;
     *list_entries = base + w.off_tile_ids;
-    *list_capacity = (int64_t)batch_size * w.nbx * w.nby;
+    *list_capacity = (int64_t)batch_size * w.grid.nbins();
     return MR_OK;
 }
 
@@ -1757,7 +1683,7 @@ extern "C" int mr_render_forward(const float* faces, const float* textures, cons
     FwdParams p{};
     BinParams bp{};
     bp.faces = faces; bp.F0 = num_faces;
-    const bool dense_list = dense_list_ok(batch_size, num_faces, image_size, face_inv_map, flags);
+    const bool dense_list = dense_list_ok(batch_size, image_size, face_inv_map != nullptr, flags);
     int rc = (flags & MR_FLAG_REFERENCE_ALGO) ? MR_OK
                                               : launch_bins<false>(bp, p, workspace, batch_size, num_faces, image_size, s, flags, nullptr, dense_list);
     if (rc != MR_OK) return rc;
@@ -1821,7 +1747,7 @@ extern "C" int mr_render_vc_forward(const float* verts, const int32_t* faces_idx
     BinParams bp{};
     bp.verts = verts; bp.fidx = faces_idx; bp.V = num_verts; bp.F0 = num_faces; bp.fill_back = fill_back;
     if (batch_size > 65535) return MR_ERR_BADARG;
-    const bool dense_list = dense_list_ok(batch_size, F, image_size, nullptr, flags);
+    const bool dense_list = dense_list_ok(batch_size, image_size, false, flags);
     const int rc = launch_bins<true>(bp, p, workspace, batch_size, F, image_size, s, flags, nullptr, dense_list);
     if (rc != MR_OK) return rc;
     p.background = background; p.bg_stride = bg_stride;

@@ -1137,10 +1137,13 @@ extern "C" int mr_pair_consist_forward_crit(const float* flow12, const float* fl
                                      criterion, jitter_channels, batch_size, height, width, tile_hit12 || tile_hit21, hit_image_size, g);
     if (rc != MR_OK || batch_size == 0) return rc;
     const int nblk = g.nblk;
-    PairParams p{flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, (float*)workspace,
-                 full_mask1, full_mask2, warp_mask1, warp_mask2, warp1, warp2, diff1, diff2,
-                 batch_size, height, width, nblk, g.tiles_x, thresh, tile_hit12, tile_hit21, hit_image_size,
-                 g.hit_tiles_x, g.hit_stride};
+    PairParams p{};  // (value-initialised, then filled: the padding bytes are kernel-argument bytes too)
+    p.flow12 = flow12; p.flow21 = flow21; p.image_ref = image_ref; p.image = image; p.jitter_ref = jitter_ref; p.jitter = jitter;
+    p.Cj = jitter_channels; p.partial = (float*)workspace;
+    p.full_mask1 = full_mask1; p.full_mask2 = full_mask2; p.warp_mask1 = warp_mask1; p.warp_mask2 = warp_mask2;
+    p.warp1 = warp1; p.warp2 = warp2; p.diff1 = diff1; p.diff2 = diff2;
+    p.B = batch_size; p.H = height; p.W = width; p.nblk = nblk; p.tiles_x = g.tiles_x; p.thresh = thresh;
+    p.hit12 = tile_hit12; p.hit21 = tile_hit21; p.hit_is = hit_image_size; p.hit_tiles_x = g.hit_tiles_x; p.hit_stride = g.hit_stride;
     hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_consist_forward_l2_kernel : pair_consist_forward_kernel,
                        dim3((unsigned)(nblk * batch_size)), dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
@@ -1178,10 +1181,13 @@ extern "C" int mr_pair_consist_backward_crit(const float* flow12, const float* f
                                      criterion, jitter_channels, batch_size, height, width, tile_hit12 || tile_hit21, hit_image_size, g);
     if (rc != MR_OK || batch_size == 0) return rc;
     const int nblk = g.nblk;
-    PairBwdParams p{flow12, flow21, image_ref, image, jitter_ref, jitter, jitter_channels, sums,
-                    grad_loss_fwd, grad_loss_bwd, grad_flow12, grad_flow21, batch_size, height, width, nblk,
-                    g.tiles_x, thresh, tile_hit12, tile_hit21, hit_image_size, g.hit_tiles_x, g.hit_stride,
-                    reinterpret_cast<unsigned*>(grad_max)};
+    PairBwdParams p{};  // (value-initialised, then filled: see mr_pair_consist_forward_crit)
+    p.flow12 = flow12; p.flow21 = flow21; p.image_ref = image_ref; p.image = image; p.jitter_ref = jitter_ref; p.jitter = jitter;
+    p.Cj = jitter_channels; p.sums = sums; p.grad_loss_fwd = grad_loss_fwd; p.grad_loss_bwd = grad_loss_bwd;
+    p.grad_flow12 = grad_flow12; p.grad_flow21 = grad_flow21;
+    p.B = batch_size; p.H = height; p.W = width; p.ntiles = nblk; p.tiles_x = g.tiles_x; p.thresh = thresh;
+    p.hit12 = tile_hit12; p.hit21 = tile_hit21; p.hit_is = hit_image_size; p.hit_tiles_x = g.hit_tiles_x; p.hit_stride = g.hit_stride;
+    p.grad_max = reinterpret_cast<unsigned*>(grad_max);
     hipLaunchKernelGGL(criterion == MR_CRITERION_L2 ? pair_consist_backward_l2_kernel : pair_consist_backward_kernel,
                        dim3((unsigned)((nblk * batch_size + PT_SUB - 1) / PT_SUB)), dim3(256), 0, (hipStream_t)stream, p);
     MR_CHECK_LAUNCH();
@@ -1246,11 +1252,7 @@ extern "C" int mr_flow_finalize_backward(const float* grad_flow, const float* ma
 
 
 // ---- listed launches of the warp half (see the kernels) --------------------------------------------------------------
-static unsigned listed_grid(int64_t tile_bound, int64_t cap) {
-    if (tile_bound <= 0) tile_bound = (cap + 3) / 4;
-    const int64_t bound = std::min<int64_t>((cap + 7) & ~(int64_t)7, std::max<int64_t>((tile_bound + 7) & ~(int64_t)7, 8));
-    return (unsigned)bound;
-}
+// (listed_grid, the workgroups of a launch over the render's tile list: launch_plan.hpp)
 
 extern "C" int mr_occlusion_flow_tiles(const float* mask_flow1, const float* mask_flow2, const float* flow12,
                                        const float* flow21, int64_t flow_bstride, const float* flow12_scale,
@@ -1401,6 +1403,35 @@ extern "C" int mr_pair_consist_backward_tiles(const float* flow12, const float* 
 }
 
 
+// the kernel of a plan: the batch's element types, the form (records / unit gradient / loss only) and the criterion
+static void (*pair_forward_kernel(const PairFwdPlan& plan))(FlowPairFwdParams) {
+    const bool l2 = plan.l2;
+    switch (plan.types) {
+    case PairFwdPlan::F32_F32:
+        switch (plan.form) {
+        case PairFwdPlan::RECORDS: return l2 ? flow_pair_forward_tiles_l2_kernel<true, true> : flow_pair_forward_tiles_kernel<true, true>;
+        case PairFwdPlan::UNIT_GRAD: return l2 ? flow_pair_forward_tiles_l2_kernel<true> : flow_pair_forward_tiles_kernel<true>;
+        case PairFwdPlan::LOSS_ONLY: return l2 ? flow_pair_forward_tiles_l2_kernel<false> : flow_pair_forward_tiles_kernel<false>;
+        }
+        break;
+    case PairFwdPlan::BF16_U8:
+        switch (plan.form) {
+        case PairFwdPlan::RECORDS: return l2 ? flow_pair_forward_tiles_l2_bf16u8_kernel<true, true> : flow_pair_forward_tiles_bf16u8_kernel<true, true>;
+        case PairFwdPlan::UNIT_GRAD: return l2 ? flow_pair_forward_tiles_l2_bf16u8_kernel<true> : flow_pair_forward_tiles_bf16u8_kernel<true>;
+        case PairFwdPlan::LOSS_ONLY: return l2 ? flow_pair_forward_tiles_l2_bf16u8_kernel<false> : flow_pair_forward_tiles_bf16u8_kernel<false>;
+        }
+        break;
+    case PairFwdPlan::BF16_F32:
+        switch (plan.form) {
+        case PairFwdPlan::RECORDS: return l2 ? flow_pair_forward_tiles_l2_bf16f32_kernel<true, true> : flow_pair_forward_tiles_bf16f32_kernel<true, true>;
+        case PairFwdPlan::UNIT_GRAD: return l2 ? flow_pair_forward_tiles_l2_bf16f32_kernel<true> : flow_pair_forward_tiles_bf16f32_kernel<true>;
+        case PairFwdPlan::LOSS_ONLY: return l2 ? flow_pair_forward_tiles_l2_bf16f32_kernel<false> : flow_pair_forward_tiles_bf16f32_kernel<false>;
+        }
+        break;
+    }
+    return nullptr;
+}
+
 int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
     const bool grad = a.unit_grad != nullptr;
     if (a.records ? (!grad || misaligned({a.records}, 15))
@@ -1419,33 +1450,22 @@ int mr::launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s) {
     FlowPairFwdParams q{};
     if (!a.workspace || !a.sums || a.workspace_bytes < pair_tiles_work(a.workspace, a.batch_size, a.image_size, &q)) return MR_ERR_BADARG;
     if (a.batch_size == 0) return MR_OK;
-    const int tiles_x = (a.image_size + 31) / 32, tiles_y = (a.image_size + 7) / 8;
+    const PairFwdPlan plan = plan_pair_forward(a.batch_size, a.image_size, a.records != nullptr, grad, a.criterion, a.image_dtype, a.mask_dtype,
+                                               a.tile_bound, a.list_capacity);
     const TileList* header = (const TileList*)a.list_header;
     q.o = OcclTilesParams{{a.mask_flow1, a.mask_flow2}, {a.flow12, a.flow21}, {a.flow12_scale, a.flow21_scale}, {a.occl1, a.occl2},
                           {a.flow_out12, a.flow_out21}, {a.tile_hit1, a.tile_hit2}, a.flow_bstride, a.batch_size, a.image_size,
-                          a.height, a.width, tiles_x, tiles_y, a.distance_thresh, a.warp_thresh,
+                          a.height, a.width, plan.tiles_x, plan.tiles_y, a.distance_thresh, a.warp_thresh,
                           {header, (const uint4*)a.list_entries, (unsigned)a.list_capacity}};
     q.image_ref = a.image_ref; q.image = a.image; q.jitter_ref = a.jitter_ref; q.jitter = a.jitter; q.Cj = a.jitter_channels;
     q.thresh = a.pair_thresh;
     q.unit_grad = a.unit_grad;
     q.rec = (const float4*)a.records;
-    // (the form -- records / unit gradient / loss only --, the criterion and the batch's element types are chosen here, once
-    // per launch)
-    const bool l2 = a.criterion == MR_CRITERION_L2;
-#define MR_PICK_FORM(L1K, L2K)                                 \
-    (a.records ? (l2 ? L2K<true, true> : L1K<true, true>)      \
-     : grad    ? (l2 ? L2K<true> : L1K<true>)                  \
-               : (l2 ? L2K<false> : L1K<false>))
-    void (*kernel)(FlowPairFwdParams) =
-        a.image_dtype == MR_DTYPE_F32 ? MR_PICK_FORM(flow_pair_forward_tiles_kernel, flow_pair_forward_tiles_l2_kernel)
-        : a.mask_dtype == MR_DTYPE_U8 ? MR_PICK_FORM(flow_pair_forward_tiles_bf16u8_kernel, flow_pair_forward_tiles_l2_bf16u8_kernel)
-                                      : MR_PICK_FORM(flow_pair_forward_tiles_bf16f32_kernel, flow_pair_forward_tiles_l2_bf16f32_kernel);
-#undef MR_PICK_FORM
-    hipLaunchKernelGGL(kernel, dim3(listed_grid(a.tile_bound, a.list_capacity)), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(pair_forward_kernel(plan), dim3(plan.wgs), dim3(256), 0, s, q);
     MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pair_consist_finalize_tiles_kernel, dim3(a.batch_size), dim3(256), 0, s, (const float*)a.workspace,
+    hipLaunchKernelGGL(pair_consist_finalize_tiles_kernel, dim3(plan.finalize_wgs), dim3(256), 0, s, (const float*)a.workspace,
                        reinterpret_cast<const uint32_t*>(a.tile_hit1), reinterpret_cast<const uint32_t*>(a.tile_hit2), a.batch_size,
-                       tiles_x * tiles_y, a.sums, a.loss_fwd, a.loss_bwd, grad ? (const unsigned*)q.tile_max : (const unsigned*)nullptr,
+                       plan.tiles_x * plan.tiles_y, a.sums, a.loss_fwd, a.loss_bwd, grad ? (const unsigned*)q.tile_max : (const unsigned*)nullptr,
                        grad ? reinterpret_cast<unsigned*>(a.unit_grad_max) : (unsigned*)nullptr, a.loss_sum,
                        scatter_work_at(grad ? a.scatter_work : nullptr, 2 * a.batch_size),
                        // (the arrival counter of the batch mean: a spare word of the list header the caller cleared with it)
