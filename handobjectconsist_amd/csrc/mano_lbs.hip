@@ -16,9 +16,11 @@
 //   mano_blend_bwd_kernel d coeff = d v_posed[B,2334] x blend^T on the matrix cores, split-K partials
 //   mano_pre_bwd_kernel   one wave per sample: sums the partials, chain / Rodrigues / PCA adjoints
 // This is the only GEMM-shaped work on the whole path (M = 2334, K = 145, N = batch).
-// The pre / skin kernels and their adjoints are templates: <PCA pose, network call> is mr_mano_forward /
-// mr_mano_backward as ever; the FULL instantiations (mr_mano_forward_full / mr_mano_backward_full) add the 48-value
-// axis-angle pose, a finger-tip centre, manopth's translation rule and the ground-truth epilogue.
+// One family of kernels serves both entry-point pairs.  What a call adds to plain skinning -- a translation under manopth's
+// rule, the ground-truth epilogue -- arrives in ManoFull at run time; the network's call (mr_mano_forward / mr_mano_backward:
+// PCA pose, a joint centre or none) passes an empty one, the general call (mr_mano_forward_full / mr_mano_backward_full,
+// DESIGN 18) fills it and may take the 48-value axis-angle pose and a finger-tip centre.  The pose form is the only
+// template parameter.
 #include "mr_common.hpp"
 
 namespace mr {
@@ -40,20 +42,23 @@ struct ManoConst {
     const int* parents;    // [16], parents[0] = -1
     const int* tips;       // [5] vertex ids
     const int* reorder;    // [21] output joint k = cat(joints, tips)[reorder[k]]
-    int ncomps, center;    // center: index into cat(joints, tips) BEFORE the reorder, or -1; >= 16 (a tip): FULL kernels only
+    int ncomps, center;    // center: index into cat(joints, tips) BEFORE the reorder, or -1; >= 16: a finger tip
 };
 
-// what the FULL kernels take on top (mr_mano_forward_full / mr_mano_backward_full)
+// what a call adds to plain skinning; all zero (ManoFull{}) = nothing extra, the network's call
 struct ManoFull {
     const float* trans;        // [B,3] th_trans, or NULL
     int ntrans;                // 3 B (0 without a translation): the bound of the all-zero scan
-    float* tflag;              // [B] workspace: 1.0f where the translation is in force (every sample holds the same value)
+    float* tflag;              // [B] workspace: 1.0f where the translation is in force (every sample holds the same value);
+                               //   NULL = no translation in force: mano_pre_kernel writes no flag and nobody reads one
     float out_scale;           // the rigid epilogue, applied iff post_rot != NULL: x = v * out_scale; x = x + post_trans[b];
     const float* post_trans;   //   x = post_rot[b] x; x = x - post_trans2[b]   (either translation may be NULL)
     const float* post_rot;     // [B,9]
     const float* post_trans2;  // [B,3]
 };
 constexpr int MN_POSE_PCA = 0, MN_POSE_AXISANG = 1;  // MR_MANO_POSE_*
+
+__device__ __forceinline__ bool trans_in_force(const ManoFull& mf, int b) { return mf.tflag && mf.tflag[b] != 0.0f; }
 
 // ---------------------------------------------------------------------------------------------------
 // small helpers (per-lane serial 3x3 / 3x4 algebra; everything here is a few hundred flops per sample)
@@ -75,14 +80,13 @@ __device__ __forceinline__ void rigid_mul(const float* A, const float* B, float*
 // forward
 // ---------------------------------------------------------------------------------------------------
 // one wave per sample.  Outputs: coeff[B,MN_KP], G[B,16,12] (chain), G2[B,16,12] (rest-pose corrected),
-// rots[B,16,9], joints[B,16,3]; the 16 joint rows of jtr_out (centred, x1000, reordered).
-template <int FORM, bool FULL>
+// rots[B,16,9], joints[B,16,3]; tflag[B] where the call has one.
+template <int FORM>
 __global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, ManoFull mf, const float* __restrict__ pose,
                                                       const float* __restrict__ betas, float* __restrict__ coeff,
                                                       float* __restrict__ G, float* __restrict__ G2,
                                                       float* __restrict__ rots, float* __restrict__ joints,
-                                                      float* __restrict__ full_pose_out, float* __restrict__ jtr_out,
-                                                      int B) {
+                                                      float* __restrict__ full_pose_out, int B) {
     __shared__ float s_pose[48], s_R[MN_J * 9], s_J[48], s_G[MN_J * 12];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int np = FORM == MN_POSE_AXISANG ? 48 : 3 + mc.ncomps;
@@ -96,7 +100,7 @@ __global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, ManoFull mf,
             s_pose[3 + lane] = mc.mean[lane] + acc;
         }
     }
-    if constexpr (FULL) {
+    if (mf.tflag) {
         // manopth's rule: a translation whose norm over the WHOLE tensor is zero counts as absent.  Every sample's wave
         // scans all 3 B values and ORs their magnitude bits: no flag shared between samples, no atomic, no second launch
         unsigned bits = 0u;
@@ -156,16 +160,7 @@ __global__ void __launch_bounds__(64) mano_pre_kernel(ManoConst mc, ManoFull mf,
                          fmaf(s_G[j * 12 + 4 * r + 1], s_J[3 * j + 1], s_G[j * 12 + 4 * r] * s_J[3 * j]));
         G2[b * MN_J * 12 + k] = v;
     }
-    // joint rows of the output (tips come from mano_skin_kernel; FULL: so do these rows, the centre may be a tip)
-    if constexpr (!FULL) {
-        if (lane < MN_JT * 3) {
-            const int k = lane / 3, r = lane % 3, src = mc.reorder[k];
-            if (src < MN_J) {
-                const float ctr = mc.center >= 0 ? s_G[mc.center * 12 + 4 * r + 3] : 0.0f;
-                jtr_out[(b * MN_JT + k) * 3 + r] = (s_G[src * 12 + 4 * r + 3] - ctr) * 1000.0f;
-            }
-        }
-    }
+    // (every row of jtr_out comes from mano_skin_kernel: the centre may be a finger tip, a skinned vertex)
 }
 
 // D[M = batch rows, N = 2334] = coeff[B, MN_KP] x blend[MN_KP, 2334] + template; one 32 x 32 tile per wave
@@ -212,8 +207,8 @@ __device__ __forceinline__ void skin_vertex(const float* __restrict__ weights, c
     for (int r = 0; r < 3; r++) o[r] = fmaf(T[4 * r + 2], p[2], fmaf(T[4 * r + 1], p[1], T[4 * r] * p[0])) + T[4 * r + 3];
 }
 
-// FULL: translation or centre, the millimetre scale, then the rigid epilogue -- separate multiplies and adds in the order
-// of the host code it stands for (scale, translate, rotate, subtract)
+// translation or centre, the millimetre scale, then the rigid epilogue where there is one -- separate multiplies and adds in
+// the order of the host code it stands for (scale, translate, rotate, subtract)
 __device__ __forceinline__ void full_finish(const ManoFull& mf, int b, bool in_force, bool centred, const float* off,
                                             float* o) {
 #pragma unroll
@@ -234,8 +229,7 @@ __device__ __forceinline__ void full_finish(const ManoFull& mf, int b, bool in_f
     }
 }
 
-// one thread per (sample, vertex)
-template <bool FULL>
+// one thread per (sample, vertex); block 0 of a sample also writes its 16 joint rows
 __global__ void __launch_bounds__(256) mano_skin_kernel(ManoConst mc, ManoFull mf, const float* __restrict__ v_posed,
                                                         const float* __restrict__ G, const float* __restrict__ G2,
                                                         float* __restrict__ verts_out, float* __restrict__ jtr_out,
@@ -245,48 +239,37 @@ __global__ void __launch_bounds__(256) mano_skin_kernel(ManoConst mc, ManoFull m
     const int b = blockIdx.y, v = blockIdx.x * blockDim.x + threadIdx.x;
     for (int k = threadIdx.x; k < MN_J * 12; k += blockDim.x) s_G2[k] = G2[b * MN_J * 12 + k];
     __syncthreads();
-    bool in_force = false;
-    if constexpr (FULL) {
-        in_force = mf.tflag[b] != 0.0f;
-        if (threadIdx.x == 0) {  // what every output of the sample is shifted by: the translation, or the centre
-            float c[3] = {0.0f, 0.0f, 0.0f};
-            if (in_force) {
+    const bool in_force = trans_in_force(mf, b);
+    if (threadIdx.x == 0) {  // what every output of the sample is shifted by: the translation, or the centre
+        float c[3] = {0.0f, 0.0f, 0.0f};
+        if (in_force) {
 #pragma unroll
-                for (int r = 0; r < 3; r++) c[r] = mf.trans[b * 3 + r];
-            } else if (mc.center >= MN_J) {  // a finger tip is a skinned vertex: recomputed here, the same arithmetic
-                skin_vertex(mc.weights, s_G2, v_posed, b, mc.tips[mc.center - MN_J], c);
-            } else if (mc.center >= 0) {
+            for (int r = 0; r < 3; r++) c[r] = mf.trans[b * 3 + r];
+        } else if (mc.center >= MN_J) {  // a finger tip is a skinned vertex: recomputed here, the same arithmetic
+            skin_vertex(mc.weights, s_G2, v_posed, b, mc.tips[mc.center - MN_J], c);
+        } else if (mc.center >= 0) {
 #pragma unroll
-                for (int r = 0; r < 3; r++) c[r] = G[(b * MN_J + mc.center) * 12 + 4 * r + 3];
-            }
-#pragma unroll
-            for (int r = 0; r < 3; r++) s_off[r] = c[r];
+            for (int r = 0; r < 3; r++) c[r] = G[(b * MN_J + mc.center) * 12 + 4 * r + 3];
         }
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x < MN_JT) {  // the joint rows (mano_pre_kernel writes them for the network call)
-            const int k = threadIdx.x, src = mc.reorder[k];
-            if (src < MN_J) {
-                float o[3];
 #pragma unroll
-                for (int r = 0; r < 3; r++) o[r] = G[(b * MN_J + src) * 12 + 4 * r + 3];
-                full_finish(mf, b, in_force, mc.center >= 0, s_off, o);
+        for (int r = 0; r < 3; r++) s_off[r] = c[r];
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x < MN_JT) {  // the joint rows
+        const int k = threadIdx.x, src = mc.reorder[k];
+        if (src < MN_J) {
+            float o[3];
 #pragma unroll
-                for (int r = 0; r < 3; r++) jtr_out[(b * MN_JT + k) * 3 + r] = o[r];
-            }
+            for (int r = 0; r < 3; r++) o[r] = G[(b * MN_J + src) * 12 + 4 * r + 3];
+            full_finish(mf, b, in_force, mc.center >= 0, s_off, o);
+#pragma unroll
+            for (int r = 0; r < 3; r++) jtr_out[(b * MN_JT + k) * 3 + r] = o[r];
         }
     }
     if (v >= MN_V) return;
     float o[3];
     skin_vertex(mc.weights, s_G2, v_posed, b, v, o);
-    if constexpr (FULL) {
-        full_finish(mf, b, in_force, mc.center >= 0, s_off, o);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const float ctr = mc.center >= 0 ? G[(b * MN_J + mc.center) * 12 + 4 * r + 3] : 0.0f;
-            o[r] = (o[r] - ctr) * 1000.0f;
-        }
-    }
+    full_finish(mf, b, in_force, mc.center >= 0, s_off, o);
 #pragma unroll
     for (int r = 0; r < 3; r++) verts_out[((int64_t)b * MN_V + v) * 3 + r] = o[r];
 #pragma unroll
@@ -307,7 +290,6 @@ __global__ void __launch_bounds__(256) mano_skin_kernel(ManoConst mc, ManoFull m
 constexpr int MN_CHUNKS = (MN_V + 255) / 256;
 constexpr int MN_PART = MN_J * 12 + 3;
 
-template <bool FULL>
 __global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, ManoFull mf, const float* __restrict__ v_posed,
                                                             const float* __restrict__ G2,
                                                             const float* __restrict__ grad_verts,
@@ -320,35 +302,33 @@ __global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, ManoFu
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x, v = chunk * 256 + tid;
     for (int k = tid; k < MN_J * 12; k += 256) s_G2[k] = G2[b * MN_J * 12 + k];
     __syncthreads();
-    // FULL, a finger-tip centre in force: the centre IS vertex cv, so its adjoint -- minus the sum of every incoming
+    // A finger-tip centre in force: the centre IS vertex cv, so its adjoint -- minus the sum of every incoming
     // gradient of the sample, 778 vertex rows + 21 joint rows -- joins that vertex's gradient.  Summed by the one chunk
     // that holds cv, in a fixed order (strided partial sums, then a tree over LDS): deterministic
     int cv = -1;
     float gctr[3] = {0.0f, 0.0f, 0.0f};
-    if constexpr (FULL) {
-        if (mc.center >= MN_J && mf.tflag[b] == 0.0f) cv = mc.tips[mc.center - MN_J];
-        if (cv >= 0 && cv / 256 == chunk) {  // (uniform over the block)
-            float a[3] = {0.0f, 0.0f, 0.0f};
-            for (int i = tid; i < MN_V + MN_JT; i += 256) {
-                const float* src = i < MN_V ? (grad_verts ? grad_verts + ((int64_t)b * MN_V + i) * 3 : nullptr)
-                                            : (grad_jtr ? grad_jtr + (b * MN_JT + (i - MN_V)) * 3 : nullptr);
-                if (src)
+    if (mc.center >= MN_J && !trans_in_force(mf, b)) cv = mc.tips[mc.center - MN_J];
+    if (cv >= 0 && cv / 256 == chunk) {  // (uniform over the block)
+        float a[3] = {0.0f, 0.0f, 0.0f};
+        for (int i = tid; i < MN_V + MN_JT; i += 256) {
+            const float* src = i < MN_V ? (grad_verts ? grad_verts + ((int64_t)b * MN_V + i) * 3 : nullptr)
+                                        : (grad_jtr ? grad_jtr + (b * MN_JT + (i - MN_V)) * 3 : nullptr);
+            if (src)
 #pragma unroll
-                    for (int r = 0; r < 3; r++) a[r] += src[r] * 1000.0f;
-            }
+                for (int r = 0; r < 3; r++) a[r] += src[r] * 1000.0f;
+        }
 #pragma unroll
-            for (int r = 0; r < 3; r++) s_gt[tid][r] = a[r];
-            __syncthreads();
-            for (int h = 128; h > 0; h >>= 1) {
-                if (tid < h)
+        for (int r = 0; r < 3; r++) s_gt[tid][r] = a[r];
+        __syncthreads();
+        for (int h = 128; h > 0; h >>= 1) {
+            if (tid < h)
 #pragma unroll
-                    for (int r = 0; r < 3; r++) s_gt[tid][r] += s_gt[tid + h][r];
-                __syncthreads();
-            }
-#pragma unroll
-            for (int r = 0; r < 3; r++) gctr[r] = -s_gt[0][r];
+                for (int r = 0; r < 3; r++) s_gt[tid][r] += s_gt[tid + h][r];
             __syncthreads();
         }
+#pragma unroll
+        for (int r = 0; r < 3; r++) gctr[r] = -s_gt[0][r];
+        __syncthreads();
     }
     float g[3] = {0.0f, 0.0f, 0.0f};
     if (v < MN_V) {
@@ -370,10 +350,9 @@ __global__ void __launch_bounds__(256) mano_skin_bwd_kernel(ManoConst mc, ManoFu
                         if (mc.reorder[k] == MN_J + tpi)
 #pragma unroll
                             for (int r = 0; r < 3; r++) g[r] += grad_jtr[(b * MN_JT + k) * 3 + r] * 1000.0f;
-        if constexpr (FULL)
-            if (v == cv)
+        if (v == cv)
 #pragma unroll
-                for (int r = 0; r < 3; r++) g[r] += gctr[r];
+            for (int r = 0; r < 3; r++) g[r] += gctr[r];
         const float* vp = v_posed + ((int64_t)b * MN_V + v) * 3;
         const float p[4] = {vp[0], vp[1], vp[2], 1.0f};
 #pragma unroll
@@ -433,7 +412,7 @@ __global__ void __launch_bounds__(64) mano_blend_bwd_kernel(const float* __restr
 }
 
 // one wave per sample
-template <int FORM, bool FULL>
+template <int FORM>
 __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull mf, float* __restrict__ grad_trans,
                                                           const float* __restrict__ full_pose,
                                                           const float* __restrict__ rots,
@@ -485,20 +464,16 @@ __global__ void __launch_bounds__(64) mano_pre_bwd_kernel(ManoConst mc, ManoFull
                     // (tips: their share of the centre gradient is in part[] through the vertex rows)
                 }
             }
-        if constexpr (FULL) {
-            // verts = (skinned + trans) * 1000, joints likewise: d trans = the sum of every incoming gradient x 1000 = -gc,
-            // and nothing was centred.  A tip centre's adjoint went into its vertex (mano_skin_bwd_kernel); part[]'s sum
-            // then holds that vertex's addend too and is not used.  (0 - gc, not -gc: the same value for every gc but zero,
-            // where all-zero incoming gradients then give +0 like every other gradient, not -0)
-            const bool in_force = mf.tflag[b] != 0.0f;
-            if (grad_trans)
-                for (int r = 0; r < 3; r++) grad_trans[b * 3 + r] = in_force ? (float)(0.0 - gc[r]) : 0.0f;
-            if (mc.center >= 0 && mc.center < MN_J && !in_force)
-                for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
-        } else {
-            if (mc.center >= 0)
-                for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
-        }
+        // A translation in force: verts = (skinned + trans) * 1000, joints likewise, so d trans = the sum of every incoming
+        // gradient x 1000 = -gc, and nothing was centred.  Otherwise a joint centre's adjoint, gc, goes to its joint; a tip
+        // centre's went into its vertex (mano_skin_bwd_kernel), part[]'s sum then holds that vertex's addend too and is not
+        // used.  (0 - gc, not -gc: the same value for every gc but zero, where all-zero incoming gradients then give +0
+        // like every other gradient, not -0)
+        const bool in_force = trans_in_force(mf, b);
+        if (grad_trans)
+            for (int r = 0; r < 3; r++) grad_trans[b * 3 + r] = in_force ? (float)(0.0 - gc[r]) : 0.0f;
+        if (mc.center >= 0 && mc.center < MN_J && !in_force)
+            for (int r = 0; r < 3; r++) gt[mc.center][r] += gc[r];
         // G2 = [G.R | G.t - G.R J]  ->  dG.R = dG2.R - dG2.t (x) J ; dG.t = dG2.t ; dJ = - G.R^T dG2.t
         for (int j = 0; j < MN_J; j++) {
             for (int r = 0; r < 3; r++) {
@@ -580,10 +555,11 @@ static ManoConst mano_const(const float* comps, const float* mean, const float* 
                      ncomps, center};
 }
 
-// coeff | G | G2 | rots | joints | full_pose | v_posed | grad_vp | part | partial ( | tflag): float arrays, packed
+// coeff | G | G2 | rots | joints | full_pose | v_posed | grad_vp | part | partial | tflag: float arrays, packed.  Both
+// entry-point pairs carve the same regions; tflag lies behind the others, and only mr_mano_full_workspace_floats counts it:
+// the network's call has no translation and passes the kernels no flag
 struct ManoWork {
-    float *coeff, *G, *G2, *rots, *joints, *full_pose, *v_posed, *grad_vp, *part, *partial;
-    float* tflag;  // [B], behind the regions of mr_mano_workspace_floats: mr_mano_full_workspace_floats only
+    float *coeff, *G, *G2, *rots, *joints, *full_pose, *v_posed, *grad_vp, *part, *partial, *tflag;
     int Mpad;
     int64_t floats, full_floats;  // without / with tflag
 };
@@ -601,6 +577,46 @@ static ManoWork mano_work(float* w, int64_t B) {
     return m;
 }
 
+// The three forward launches of either entry point, arguments already checked.  The switch on the pose form is here and in
+// mano_launch_backward, nowhere else
+static int mano_launch_forward(const ManoConst& mc, const ManoFull& mf, int pose_form, float* workspace, const float* pose,
+                               const float* betas, float* verts_out, float* jtr_out, int B, hipStream_t s) {
+    const ManoWork m = mano_work(workspace, B);
+    const auto pre = pose_form == MN_POSE_AXISANG ? mano_pre_kernel<MN_POSE_AXISANG> : mano_pre_kernel<MN_POSE_PCA>;
+    hipLaunchKernelGGL(pre, dim3((unsigned)B), dim3(64), 0, s, mc, mf, pose, betas, m.coeff, m.G, m.G2, m.rots, m.joints,
+                       m.full_pose, B);
+    MR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((B + 31) / 32)), dim3(64), 0, s,
+                       (const float*)m.coeff, mc.blend, mc.templ, m.v_posed, B);
+    MR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mano_skin_kernel, dim3(blocks1d(MN_V), (unsigned)B), dim3(256), 0, s, mc, mf, (const float*)m.v_posed,
+                       (const float*)m.G, (const float*)m.G2, verts_out, jtr_out, B);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
+
+// ... and the three backward launches; mf.tflag is what the forward call left in the workspace, or NULL
+static int mano_launch_backward(const ManoConst& mc, const ManoFull& mf, int pose_form, float* workspace,
+                                const float* grad_verts, const float* grad_jtr, float* grad_pose, float* grad_betas,
+                                float* grad_trans, int B, hipStream_t s) {
+    const ManoWork m = mano_work(workspace, B);
+    hipLaunchKernelGGL(mano_skin_bwd_kernel, dim3(MN_CHUNKS, (unsigned)B), dim3(256), 0, s, mc, mf, (const float*)m.v_posed,
+                       (const float*)m.G2, grad_verts, grad_jtr, m.grad_vp, m.part, B);
+    MR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mano_blend_bwd_kernel, dim3(5, (unsigned)(m.Mpad / 32), MN_SPLITK), dim3(64), 0, s,
+                       (const float*)m.grad_vp, mc.blend, m.partial, B, m.Mpad);
+    MR_CHECK_LAUNCH();
+    const auto pre_bwd = pose_form == MN_POSE_AXISANG ? mano_pre_bwd_kernel<MN_POSE_AXISANG> : mano_pre_bwd_kernel<MN_POSE_PCA>;
+    hipLaunchKernelGGL(pre_bwd, dim3((unsigned)B), dim3(64), 0, s, mc, mf, grad_trans, (const float*)m.full_pose,
+                       (const float*)m.rots, (const float*)m.joints, (const float*)m.G, (const float*)m.part,
+                       (const float*)m.partial, grad_jtr, grad_pose, grad_betas, B, m.Mpad);
+    MR_CHECK_LAUNCH();
+    return MR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the network's call: PCA pose, a joint centre or none, nothing extra (an empty ManoFull, a workspace without tflag)
+// ---------------------------------------------------------------------------------------------------
 extern "C" int64_t mr_mano_workspace_floats(int batch_size) {
     if (batch_size < 0) return MR_ERR_BADARG;
     return mano_work(nullptr, batch_size).floats;
@@ -617,21 +633,10 @@ extern "C" int mr_mano_forward(const float* pose_coeffs, const float* betas, con
         !tips || !reorder || !workspace || !verts_out || !jtr_out)
         return MR_ERR_BADARG;
     if (batch_size > 65535) return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
-    const ManoWork m = mano_work(workspace, batch_size);
-    hipLaunchKernelGGL((mano_pre_kernel<MN_POSE_PCA, false>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, ManoFull{},
-                       pose_coeffs, betas, m.coeff, m.G, m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((batch_size + 31) / 32)), dim3(64), 0, s,
-                       (const float*)m.coeff, blend, v_template, m.v_posed, batch_size);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_skin_kernel<false>, dim3(blocks1d(MN_V), (unsigned)batch_size), dim3(256), 0, s, mc,
-                       ManoFull{}, (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out,
-                       batch_size);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return mano_launch_forward(mc, ManoFull{}, MN_POSE_PCA, workspace, pose_coeffs, betas, verts_out, jtr_out, batch_size,
+                               (hipStream_t)stream);
 }
 
 extern "C" int mr_mano_backward(const float* comps, const float* hands_mean, const float* js, const float* jt,
@@ -645,22 +650,10 @@ extern "C" int mr_mano_backward(const float* comps, const float* hands_mean, con
         !workspace || !grad_pose_coeffs || !grad_betas)
         return MR_ERR_BADARG;
     if (batch_size > 65535) return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
-    const ManoWork m = mano_work(workspace, batch_size);
-    hipLaunchKernelGGL(mano_skin_bwd_kernel<false>, dim3(MN_CHUNKS, (unsigned)batch_size), dim3(256), 0, s, mc, ManoFull{},
-                       (const float*)m.v_posed, (const float*)m.G2, grad_verts, grad_jtr, m.grad_vp, m.part, batch_size);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_blend_bwd_kernel, dim3(5, (unsigned)(m.Mpad / 32), MN_SPLITK), dim3(64), 0, s,
-                       (const float*)m.grad_vp, blend, m.partial, batch_size, m.Mpad);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL((mano_pre_bwd_kernel<MN_POSE_PCA, false>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, ManoFull{},
-                       (float*)nullptr, (const float*)m.full_pose, (const float*)m.rots, (const float*)m.joints,
-                       (const float*)m.G, (const float*)m.part, (const float*)m.partial, grad_jtr, grad_pose_coeffs,
-                       grad_betas, batch_size, m.Mpad);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    return mano_launch_backward(mc, ManoFull{}, MN_POSE_PCA, workspace, grad_verts, grad_jtr, grad_pose_coeffs, grad_betas,
+                                nullptr, batch_size, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -700,25 +693,12 @@ extern "C" int mr_mano_forward_full(const float* pose, const float* betas, const
     if (rc != MR_OK) return rc;
     if (!pose || !betas || !verts_out || !jtr_out || (!post_rot && (post_trans || post_trans2))) return MR_ERR_BADARG;
     if (misaligned({pose, betas, trans, post_trans, post_rot, post_trans2, verts_out, jtr_out}, 3)) return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
-    const ManoWork m = mano_work(workspace, batch_size);
-    const ManoFull mf{trans, trans ? 3 * batch_size : 0, m.tflag, out_scale, post_trans, post_rot, post_trans2};
-    if (pose_form == MN_POSE_AXISANG)
-        hipLaunchKernelGGL((mano_pre_kernel<MN_POSE_AXISANG, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf, pose,
-                           betas, m.coeff, m.G, m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
-    else
-        hipLaunchKernelGGL((mano_pre_kernel<MN_POSE_PCA, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf, pose,
-                           betas, m.coeff, m.G, m.G2, m.rots, m.joints, m.full_pose, jtr_out, batch_size);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_blend_kernel, dim3((MN_NV3 + 31) / 32, (unsigned)((batch_size + 31) / 32)), dim3(64), 0, s,
-                       (const float*)m.coeff, blend, v_template, m.v_posed, batch_size);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_skin_kernel<true>, dim3(blocks1d(MN_V), (unsigned)batch_size), dim3(256), 0, s, mc, mf,
-                       (const float*)m.v_posed, (const float*)m.G, (const float*)m.G2, verts_out, jtr_out, batch_size);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    const ManoFull mf{trans, trans ? 3 * batch_size : 0, mano_work(workspace, batch_size).tflag, out_scale, post_trans,
+                      post_rot, post_trans2};
+    return mano_launch_forward(mc, mf, pose_form, workspace, pose, betas, verts_out, jtr_out, batch_size,
+                               (hipStream_t)stream);
 }
 
 extern "C" int mr_mano_backward_full(const float* comps, const float* hands_mean, const float* js, const float* jt,
@@ -734,27 +714,9 @@ extern "C" int mr_mano_backward_full(const float* comps, const float* hands_mean
     if (rc != MR_OK) return rc;
     if (!grad_pose || !grad_betas) return MR_ERR_BADARG;
     if (misaligned({grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans}, 3)) return MR_ERR_BADARG;
-    hipStream_t s = (hipStream_t)stream;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
-    const ManoWork m = mano_work(workspace, batch_size);
-    const ManoFull mf{nullptr, 0, m.tflag, 1.0f, nullptr, nullptr, nullptr};  // (the forward call left tflag in the workspace)
-    hipLaunchKernelGGL(mano_skin_bwd_kernel<true>, dim3(MN_CHUNKS, (unsigned)batch_size), dim3(256), 0, s, mc, mf,
-                       (const float*)m.v_posed, (const float*)m.G2, grad_verts, grad_jtr, m.grad_vp, m.part, batch_size);
-    MR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mano_blend_bwd_kernel, dim3(5, (unsigned)(m.Mpad / 32), MN_SPLITK), dim3(64), 0, s,
-                       (const float*)m.grad_vp, blend, m.partial, batch_size, m.Mpad);
-    MR_CHECK_LAUNCH();
-    if (pose_form == MN_POSE_AXISANG)
-        hipLaunchKernelGGL((mano_pre_bwd_kernel<MN_POSE_AXISANG, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf,
-                           grad_trans, (const float*)m.full_pose, (const float*)m.rots, (const float*)m.joints,
-                           (const float*)m.G, (const float*)m.part, (const float*)m.partial, grad_jtr, grad_pose,
-                           grad_betas, batch_size, m.Mpad);
-    else
-        hipLaunchKernelGGL((mano_pre_bwd_kernel<MN_POSE_PCA, true>), dim3((unsigned)batch_size), dim3(64), 0, s, mc, mf,
-                           grad_trans, (const float*)m.full_pose, (const float*)m.rots, (const float*)m.joints,
-                           (const float*)m.G, (const float*)m.part, (const float*)m.partial, grad_jtr, grad_pose,
-                           grad_betas, batch_size, m.Mpad);
-    MR_CHECK_LAUNCH();
-    return MR_OK;
+    const ManoFull mf{nullptr, 0, mano_work(workspace, batch_size).tflag, 1.0f, nullptr, nullptr, nullptr};
+    return mano_launch_backward(mc, mf, pose_form, workspace, grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans,
+                                batch_size, (hipStream_t)stream);
 }

@@ -184,35 +184,6 @@ MANO_REORDER = [0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 
 USE_HIP_MANO = True
 
 
-class _ManoLBSFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pose_coeffs, betas, layer):
-        ctx.set_materialize_grads(False)
-        pose, beta = _lib.contig(pose_coeffs.detach()), _lib.contig(betas.detach())
-        B = pose.shape[0]
-        c = layer.hip_constants()
-        dev = pose.device
-        work = torch.empty((max(int(_lib.load().mr_mano_workspace_floats(B)), 1),), dtype=torch.float32, device=dev)
-        verts = torch.empty((B, 778, 3), dtype=torch.float32, device=dev)
-        jtr = torch.empty((B, 21, 3), dtype=torch.float32, device=dev)
-        _lib.call("mr_mano_forward", _lib.ptr(pose), _lib.ptr(beta), *[_lib.ptr(t) for t in c["tensors"]], c["ncomps"],
-                  c["center"], _lib.ptr(work), _lib.ptr(verts), _lib.ptr(jtr), B, _lib.stream_ptr(dev))
-        ctx.layer, ctx.work, ctx.B = layer, work, B
-        return verts, jtr
-
-    @staticmethod
-    def backward(ctx, g_verts, g_jtr):
-        c = ctx.layer.hip_constants()
-        B, dev = ctx.B, ctx.work.device
-        g_pose = torch.empty((B, 3 + c["ncomps"]), dtype=torch.float32, device=dev)
-        g_beta = torch.empty((B, 10), dtype=torch.float32, device=dev)
-        gv = _lib.contig(g_verts) if g_verts is not None else None
-        gj = _lib.contig(g_jtr) if g_jtr is not None else None
-        _lib.call("mr_mano_backward", *[_lib.ptr(t) for t in c["tensors"]], c["ncomps"], c["center"], _lib.ptr(ctx.work),
-                  _lib.ptr(gv), _lib.ptr(gj), _lib.ptr(g_pose), _lib.ptr(g_beta), B, _lib.stream_ptr(dev))
-        return g_pose, g_beta, None
-
-
 def _post_arrays(post, B):
     """The ground-truth epilogue of ``forward_full`` as (scale, trans[B,3] | None, rot[B,3,3], trans2[B,3] | None); each of
     ``post``'s entries a host array or a tensor, ``rot`` the identity where absent."""
@@ -235,31 +206,39 @@ def _post_arrays(post, B):
     return float(post.get("scale", 1.0)), arr("trans", (B, 3)), rot, arr("trans2", (B, 3))
 
 
-class _ManoFullFunction(torch.autograd.Function):
-    """mr_mano_forward_full / mr_mano_backward_full: either pose form, any centre, th_trans; with ``post`` (the rigid
-    ground-truth epilogue) the outputs carry no gradient."""
+class _ManoFunction(torch.autograd.Function):
+    """The MANO kernels through either entry-point pair.  ``general=False``: mr_mano_forward / mr_mano_backward, the network's
+    call (PCA pose, a joint centre or none; ``trans`` and ``post`` are None).  ``general=True``: mr_mano_forward_full /
+    mr_mano_backward_full -- either pose form, any centre, th_trans; with ``post`` (the rigid ground-truth epilogue) the
+    outputs carry no gradient."""
 
     @staticmethod
-    def forward(ctx, pose, betas, trans, layer, post):
+    def forward(ctx, pose, betas, trans, layer, post, general):
         ctx.set_materialize_grads(False)
+        P = _lib.ptr
         pose, beta = _lib.contig(pose.detach()), _lib.contig(betas.detach())
         tr = _lib.contig(trans.detach()) if trans is not None else None
         B, dev = pose.shape[0], pose.device
         c = layer.hip_constants()
-        work = torch.empty((max(int(_lib.load().mr_mano_full_workspace_floats(B)), 1),), dtype=torch.float32, device=dev)
+        floats = getattr(_lib.load(), "mr_mano_full_workspace_floats" if general else "mr_mano_workspace_floats")(B)
+        work = torch.empty((max(int(floats), 1),), dtype=torch.float32, device=dev)
         verts = torch.empty((B, 778, 3), dtype=torch.float32, device=dev)
         jtr = torch.empty((B, 21, 3), dtype=torch.float32, device=dev)
-        scale, p_trans, p_rot, p_trans2 = post if post is not None else (1.0, None, None, None)
-        _lib.call("mr_mano_forward_full", _lib.ptr(pose), _lib.ptr(beta), _lib.ptr(tr), *[_lib.ptr(t) for t in c["tensors"]],
-                  c["pose_form"], c["ncomps"], c["center"], scale, _lib.ptr(p_trans), _lib.ptr(p_rot), _lib.ptr(p_trans2),
-                  _lib.ptr(work), _lib.ptr(verts), _lib.ptr(jtr), B, _lib.stream_ptr(dev))
+        consts, outs = [P(t) for t in c["tensors"]], (P(work), P(verts), P(jtr), B, _lib.stream_ptr(dev))
+        if general:
+            scale, p_trans, p_rot, p_trans2 = post if post is not None else (1.0, None, None, None)
+            _lib.call("mr_mano_forward_full", P(pose), P(beta), P(tr), *consts, c["pose_form"], c["ncomps"], c["center"], scale,
+                      P(p_trans), P(p_rot), P(p_trans2), *outs)
+        else:
+            _lib.call("mr_mano_forward", P(pose), P(beta), *consts, c["ncomps"], c["center"], *outs)
         if post is not None:
             ctx.mark_non_differentiable(verts, jtr)
-        ctx.layer, ctx.work, ctx.B, ctx.has_trans = layer, work, B, tr is not None
+        ctx.layer, ctx.work, ctx.B, ctx.has_trans, ctx.general = layer, work, B, tr is not None, general
         return verts, jtr
 
     @staticmethod
     def backward(ctx, g_verts, g_jtr):
+        P = _lib.ptr
         c = ctx.layer.hip_constants()
         B, dev = ctx.B, ctx.work.device
         g_pose = torch.empty((B, 48 if c["pose_form"] == _lib.MANO_POSE_AXISANG else 3 + c["ncomps"]), dtype=torch.float32,
@@ -268,10 +247,13 @@ class _ManoFullFunction(torch.autograd.Function):
         g_trans = torch.empty((B, 3), dtype=torch.float32, device=dev) if ctx.has_trans else None
         gv = _lib.contig(g_verts) if g_verts is not None else None
         gj = _lib.contig(g_jtr) if g_jtr is not None else None
-        _lib.call("mr_mano_backward_full", *[_lib.ptr(t) for t in c["tensors"]], c["pose_form"], c["ncomps"], c["center"],
-                  _lib.ptr(ctx.work), _lib.ptr(gv), _lib.ptr(gj), _lib.ptr(g_pose), _lib.ptr(g_beta), _lib.ptr(g_trans), B,
-                  _lib.stream_ptr(dev))
-        return g_pose, g_beta, g_trans, None, None
+        consts, grads = [P(t) for t in c["tensors"]], (P(ctx.work), P(gv), P(gj), P(g_pose), P(g_beta))
+        if ctx.general:
+            _lib.call("mr_mano_backward_full", *consts, c["pose_form"], c["ncomps"], c["center"], *grads, P(g_trans), B,
+                      _lib.stream_ptr(dev))
+        else:
+            _lib.call("mr_mano_backward", *consts, c["ncomps"], c["center"], *grads, B, _lib.stream_ptr(dev))
+        return g_pose, g_beta, g_trans, None, None, None
 
 
 class SynthManoLayer(nn.Module):
@@ -348,7 +330,7 @@ class SynthManoLayer(nn.Module):
         if self._hip_path(th_pose_coeffs, th_betas, th_trans):
             if th_betas is None:
                 th_betas = th_pose_coeffs.new_zeros((th_pose_coeffs.shape[0], 10))
-            return _ManoLBSFunction.apply(th_pose_coeffs, th_betas, self)
+            return _ManoFunction.apply(th_pose_coeffs, th_betas, None, self, None, False)
         if th_pose_coeffs.is_cuda and USE_HIP_MANO and not self.torch_variants:
             raise RuntimeError(
                 "SynthManoLayer: no HIP kernel for this call (needs fp32 PCA coefficients [B, 3 + ncomps], no translation, a "
@@ -391,7 +373,7 @@ class SynthManoLayer(nn.Module):
             if post is not None:
                 dev_arr = lambda a: None if a is None else a.to(pose.device, torch.float32).contiguous()
                 post = (post[0], dev_arr(post[1]), dev_arr(post[2]), dev_arr(post[3]))
-            return _ManoFullFunction.apply(pose, betas, trans, self, post)
+            return _ManoFunction.apply(pose, betas, trans, self, post, True)
         # manopth's rule lives in forward_torch's caller: a translation of zero norm counts as absent
         if trans is not None and float(torch.norm(trans.detach())) == 0.0:
             trans = None

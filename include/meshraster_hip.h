@@ -409,7 +409,10 @@ MR_API int mr_mano_backward(const float* comps, const float* hands_mean, const f
  * calls made OUTSIDE the network -- the datasets' ground-truth meshes (fhbhands.py:355-359,
  * ho3dv2.py:341-348: 48 axis-angle values, flat mean, no centre), a translation th_trans
  * (manobranch.py:130-136) and a finger-tip centre.  Same constants, same workspace scheme
- * (mr_mano_full_workspace_floats(B) floats), same kernels where the arithmetic is the same.
+ * (mr_mano_full_workspace_floats(B) floats: B more, the translation's flags) and the same kernels:
+ * one family serves both calls, mr_mano_forward / _backward are this call with nothing extra, and
+ * where both apply (PCA pose, a chain-joint centre or none, no translation, no epilogue) the two give
+ * the same bits, values and gradients.
  *   pose_form  MR_MANO_POSE_PCA: pose[B, 3 + ncomps] as above.  MR_MANO_POSE_AXISANG: pose[B,48],
  *              hand part = hands_mean + pose[:, 3:48]; comps is not read and may be NULL.
  *   center     -1 (none), 0..15 (a chain joint) or 16..20 (a finger tip: a skinned vertex), as an

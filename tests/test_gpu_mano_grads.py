@@ -69,8 +69,9 @@ def test_every_gradient_component_matches_the_fp64_differences(cuda, variant, ru
 @pytest.mark.parametrize("variant", ["forward-pca-centre9", "forward-pca-uncentred"])
 @pytest.mark.parametrize("run", list(C.MANO_RUNS))
 def test_the_two_entry_points_give_the_same_bits_where_both_apply(cuda, variant, run):
-    """PCA coefficients, an articulated centre or none, no translation: ``forward`` and ``forward_full`` are instantiations of
-    the same templates -- values and gradients bit for bit, under every weight pattern."""
+    """PCA coefficients, an articulated centre or none, no translation: ``forward`` and ``forward_full`` reach the same kernels
+    through two entry-point pairs (mr_mano_forward / _backward with an empty ``ManoFull`` and a workspace without ``tflag``,
+    mr_mano_forward_full / _backward_full) -- values and gradients bit for bit, under every weight pattern."""
     gpu_layer, _ = layers(variant, cuda)
     for pattern in C.MANO_WEIGHTS:
         pose, betas, trans, wv, wj = C.mano_case_inputs(variant, run, pattern)
