@@ -717,7 +717,9 @@ def flow_pair_loss(verts_cam, faces, camintrs, neurenderer, orig_img_size, image
         hand_face, obj_faces = faces
         tensors_ok = (all(x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 for x in (h1, o1, h2, o2))
                       and h2.shape == h1.shape and o2.shape == o1.shape and o1.shape[0] == h1.shape[0] and obj_faces.is_cuda
-                      and hand_face.is_cuda and obj_faces.dim() == 3 and obj_faces.shape[0] == h1.shape[0])
+                      and hand_face.is_cuda and obj_faces.dim() == 3 and obj_faces.shape[0] == h1.shape[0]
+                      # (an empty batch or a pair without an object: outside the kernels' contract, the composed path takes it)
+                      and h1.shape[0] > 0 and o1.shape[1] > 0)
         B, V, dev = h1.shape[0], h1.shape[1] + (o1.shape[1] if tensors_ok else 0), h1.device
         num_faces0 = (hand_face.shape[-2] + obj_faces.shape[1]) if tensors_ok else 0
     else:

@@ -79,8 +79,9 @@ class _Plan:
             st.mean_of = int(mean_of)
         sc, sv, th = _I64(), _I64(), _I64()
         rc = lib.mr_pair_step_sizes(_c.byref(self.st), _c.byref(sc), _c.byref(sv), _c.byref(th))
+        # (MR_ERR_NOTIMPL and MR_ERR_BADARG -- a shape outside the kernels' contract -- both send the pair to the composed path)
         self.ok = rc == 0
-        if rc not in (0, -2):
+        if rc not in (0, -1, -2):
             raise RuntimeError(f"mr_pair_step_sizes failed: {rc}")
         self.scratch_bytes, self.saved_bytes, self.tile_hit_offset = int(sc.value), int(sv.value), int(th.value)
         self.scratch = None
@@ -201,7 +202,8 @@ class _PairStepFunction(torch.autograd.Function):
 def pair_step(parts1, parts2, hand_face, obj_faces, K1, K2, neurenderer, is_, H, W, image_ref, image, jitter_ref, jitter, lut,
               mean_of_fwd_only=False, poison=False, flags=0, criterion=_lib.CRITERION_L1):
     """One frame pair through the two struct calls.  Returns ``(mean, loss_sum, loss_fwd, loss_bwd, flows[2B,H,W,2], tile_hit)``
-    or None where the fused path does not apply (sizes: mr_pair_step_sizes says MR_ERR_NOTIMPL).  Callers
+    or None where the fused path does not apply (sizes: mr_pair_step_sizes says MR_ERR_NOTIMPL or MR_ERR_BADARG; an empty batch;
+    a pair without object vertices).  Callers
     (``opticalflow.flow_pair_loss``) have checked devices / dtypes / shapes of the tensors they pass.  ``criterion``: the pair
     loss's MR_CRITERION_* (``_lib.CRITERION_L1`` / ``CRITERION_L2``).  The images are fp32 (masks then become fp32) or the
     compact batch as it is -- bf16 images with uint8 or fp32 masks (``_lib.batch_dtypes``) --; any other combination: None."""
@@ -213,6 +215,8 @@ def pair_step(parts1, parts2, hand_face, obj_faces, K1, K2, neurenderer, is_, H,
     h2, o2 = parts2
     dev = h1.device
     B, Va, Vb = h1.shape[0], h1.shape[1], o1.shape[1]
+    if B == 0 or Vb == 0:  # (an empty batch has no mean to report; a pair without an object is outside the kernels' contract)
+        return None
     hand_batched = hand_face.dim() == 3 and hand_face.shape[0] == B and B > 1
     hf = _faces64(hand_face, first_only=not (hand_face.dim() == 2 or hand_batched))
     of = _faces64(obj_faces)

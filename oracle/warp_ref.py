@@ -157,9 +157,11 @@ def batch_masked_mean_loss(dists, mask):
 
 
 def pair_consist(recons_flow, image_ref, image, jitter_mask_ref, jitter_mask, use_backward=False,
-                 thresh=0.99999):
-    """imgflowarp.pair_consist (imgflowarp.py:58-115) with PyramidCriterion('l1'), level_nb=1
-    (pyramidloss.py:56-62).  recons_flow = [flow12, flow21], each [B,H,W,2]."""
+                 thresh=0.99999, criterion="l1"):
+    """imgflowarp.pair_consist (imgflowarp.py:58-115) with PyramidCriterion('l1') -- or 'l2': the squared
+    difference, torch.nn.MSELoss(reduction="none") --, level_nb=1 (pyramidloss.py:56-62).
+    recons_flow = [flow12, flow21], each [B,H,W,2]."""
+    assert criterion in ("l1", "l2")
     f0 = recons_flow[0].transpose(0, 3, 1, 2)
     f1 = recons_flow[1].transpose(0, 3, 1, 2)
     warp1, warp_mask1 = warp(image_ref, f1, thresh)
@@ -172,8 +174,9 @@ def pair_consist(recons_flow, image_ref, image, jitter_mask_ref, jitter_mask, us
     valid_mask1 = (warp_mask1[:, 0] != 0) & flow_mask1[..., 0] & (jitter_mask[:, 0] == 1)
     flow_mask2 = ~(recons_flow[0] == 0)
     valid_mask2 = (warp_mask2[:, 0] != 0) & flow_mask2[..., 0] & (jitter_mask_ref[:, 0] == 1)
-    diff_fwd = np.abs(warp1 - image.astype(F32))
-    diff_bwd = np.abs(warp2 - image_ref.astype(F32))
+    diff_fwd = warp1 - image.astype(F32)
+    diff_bwd = warp2 - image_ref.astype(F32)
+    diff_fwd, diff_bwd = (np.abs(diff_fwd), np.abs(diff_bwd)) if criterion == "l1" else (diff_fwd * diff_fwd, diff_bwd * diff_bwd)
     m1 = np.repeat(valid_mask1[:, None], 3, 1)
     m2 = np.repeat(valid_mask2[:, None], 3, 1)
     losses_fwd = batch_masked_mean_loss(diff_fwd, m1)
@@ -187,10 +190,10 @@ def pair_consist(recons_flow, image_ref, image, jitter_mask_ref, jitter_mask, us
 
 
 def pair_consist_grad(recons_flow, image_ref, image, jitter_mask_ref, jitter_mask, grad_loss,
-                      use_backward=False, thresh=0.99999):
+                      use_backward=False, thresh=0.99999, criterion="l1"):
     """d (sum_b grad_loss[b] * warp_loss[b]) / d recons_flow -> [g_flow12, g_flow21], [B,H,W,2]."""
     _, masks, warps, _, _ = pair_consist(recons_flow, image_ref, image, jitter_mask_ref, jitter_mask,
-                                         use_backward, thresh)
+                                         use_backward, thresh, criterion)
     f0 = recons_flow[0].transpose(0, 3, 1, 2)
     f1 = recons_flow[1].transpose(0, 3, 1, 2)
     B = image.shape[0]
@@ -201,7 +204,8 @@ def pair_consist_grad(recons_flow, image_ref, image, jitter_mask_ref, jitter_mas
     ):
         cnt = np.maximum(3.0 * m.reshape(B, -1).sum(1), 1.0)
         cnt[m.reshape(B, -1).sum(1) == 0] = 1
-        g = np.sign(warped - tgt.astype(F32)) * m[:, None].astype(F32)
+        res = warped - tgt.astype(F32)
+        g = (np.sign(res) if criterion == "l1" else F32(2) * res) * m[:, None].astype(F32)
         g = g * (grad_loss.astype(F32) / cnt.astype(F32))[:, None, None, None]
         gflow, _ = warp_backward(src, flow, g.astype(F32), thresh)
         out.append(gflow.transpose(0, 2, 3, 1).astype(F32))
@@ -240,10 +244,12 @@ def get_occlusion_mask(mask_flow1, mask_flow2, flow12, flow21, thresh=0.99999):
 
 
 def get_opticalflow(raster, verts_cam, faces_idx, camintrs, renderer_kw, orig_img_size=None,
-                    mask_occlusions=True, ignore_face_idxs=None, return_renders=False):
+                    mask_occlusions=True, ignore_face_idxs=None, return_renders=False, return_masks=False):
     """opticalflow.get_opticalflow (opticalflow.py:51-156) on top of the render oracle.
     `raster` is the oracle.raster_ref module; renderer_kw are the Renderer settings of
-    warpreg.py:40-51 (image_size, R, t, dist_coeffs, orig_size, near, far, eps...)."""
+    warpreg.py:40-51 (image_size, R, t, dist_coeffs, orig_size, near, far, eps...).
+    return_masks (with return_renders): a third element, the factor [B,1,is,is] each direction's render
+    is multiplied with before the crop (the product of every mask on its way, image orientation)."""
     loc1 = raster.batch_proj2d(verts_cam[0], camintrs[0])
     loc2 = raster.batch_proj2d(verts_cam[1], camintrs[1])
     outs = []
@@ -259,6 +265,7 @@ def get_opticalflow(raster, verts_cam, faces_idx, camintrs, renderer_kw, orig_im
             mask = mask * ign.astype(F32)[:, None]
         outs.append((ro, mask, ro["rgb"] * mask))
     (ro1, mask_flow1, pred12), (ro2, mask_flow2, pred21) = outs
+    factors = [mask_flow1, mask_flow2]
     if mask_occlusions:
         mask_flow2 = ro2["alpha"][:, None].astype(F32)  # raw alpha
         occl1, occl2 = get_occlusion_mask(mask_flow1, mask_flow2, pred12, pred21)
@@ -266,6 +273,7 @@ def get_opticalflow(raster, verts_cam, faces_idx, camintrs, renderer_kw, orig_im
         mask_flow2 = mask_flow2 * occl2[:, None]
         pred12 = pred12 * mask_flow1
         pred21 = pred21 * mask_flow2
+        factors = [factors[0] * mask_flow1, factors[1] * mask_flow2]
     pred12 = pred12.transpose(0, 2, 3, 1)[..., :2]
     pred21 = pred21.transpose(0, 2, 3, 1)[..., :2]
     if orig_img_size is not None:
@@ -273,5 +281,82 @@ def get_opticalflow(raster, verts_cam, faces_idx, camintrs, renderer_kw, orig_im
         pred21 = pred21[:, : orig_img_size[1], : orig_img_size[0]]
     flows = [np.ascontiguousarray(pred12, F32), np.ascontiguousarray(pred21, F32)]
     if return_renders:
-        return flows, [ro1, ro2]
+        return (flows, [ro1, ro2], factors) if return_masks else (flows, [ro1, ro2])
     return flows
+
+
+# texel (i, j, k) of a 2 x 2 x 2 texture has flat index 4 i + 2 j + k: batch_vertex_textures puts the colour of a face's
+# vertex 0 / 1 / 2 at (1,0,0) / (0,1,0) / (0,0,1), and fill_back's transposed texture keeps that true of the reversed face
+_VERTEX_TEXELS = ((0, 4), (1, 2), (2, 1))
+
+
+def _vertex_colour_grad(raster, ro, faces2, grad_rgb_map, num_verts, fp32):
+    """Adjoint of texture sampling + fill_back + batch_vertex_textures for vertex-colour textures: the sampling weights of
+    each covered pixel that fall on one of its face's three vertex texels, times the pixel's gradient, added to that vertex.
+    grad_rgb_map [B,is,is,3] in RASTER orientation -> [B,V,3].  float64 sums (np.add.at), or with ``fp32`` the chain's
+    existing fp32 pieces: raster.backward_textures (kernel E, serial fp32 sums) and an fp32 scatter of its texels."""
+    sv = ro["_saved"]
+    fim, swgt, sidx = sv["face_index_map"], sv["sampling_weight_map"], sv["sampling_index_map"]
+    B = fim.shape[0]
+    if fp32:
+        gt = raster.backward_textures(fim, swgt, sidx, grad_rgb_map.astype(F32), faces2.shape[1], 2).reshape(B, faces2.shape[1], 8, 3)
+        gcol = np.zeros((B, num_verts, 3), F32)
+        for b in range(B):
+            for slot, texel in _VERTEX_TEXELS:
+                np.add.at(gcol[b], faces2[b, :, slot], gt[b, :, texel])
+        return gcol
+    b, y, x = np.nonzero(fim >= 0)
+    f = fim[b, y, x]
+    g = grad_rgb_map[b, y, x].astype(np.float64)
+    gcol = np.zeros((B, num_verts, 3), np.float64)
+    for pn in range(8):
+        isc, w = sidx[b, y, x, pn], swgt[b, y, x, pn].astype(np.float64)
+        for slot, texel in _VERTEX_TEXELS:
+            sel = isc == texel
+            np.add.at(gcol, (b[sel], faces2[b[sel], f[sel], slot]), w[sel, None] * g[sel])
+    return gcol
+
+
+def _proj2d_grad(verts, camintr, grad_loc, dtype):
+    """Adjoint of raster.batch_proj2d: loc = (K v)[:2] / (K v)[2]; grad_loc [B,V,2] -> [B,V,3]."""
+    v, K, g = verts.astype(dtype), camintr.astype(dtype), grad_loc.astype(dtype)
+    h = np.matmul(v, K.transpose(0, 2, 1))
+    gh = np.stack([g[..., 0] / h[..., 2], g[..., 1] / h[..., 2],
+                   -(g[..., 0] * h[..., 0] + g[..., 1] * h[..., 1]) / (h[..., 2] * h[..., 2])], -1)
+    return np.matmul(gh, K)
+
+
+def get_opticalflow_vertex_grad(raster, verts_cam, faces_idx, camintrs, renderer_kw, grad_flows, orig_img_size=None,
+                                ignore_face_idxs=None, forward=None, fp32=False):
+    """d (sum flow12 * grad_flows[0] + sum flow21 * grad_flows[1]) / d (verts1, verts2) of ``get_opticalflow`` in the
+    reference's training graph (opticalflow.py:51-156 with detach_textures=False, detach_renders=True): the renders are
+    detached, so geometry gets no gradient through the rasteriser, and every mask is a constant -- the vertices enter through
+    the two displacement textures alone.  Built from the oracle's FORWARD decision maps (face index, sampling weights, masks,
+    occlusion), then, in float64: the adjoint of the crop and the mask products, the scatter of each covered pixel's sampling
+    weights to its face's vertices (what kernel E and the adjoints of fill_back and batch_vertex_textures amount to for
+    vertex-colour textures) and the adjoint of batch_proj2d.  Returns (grad_verts1, grad_verts2), float64 [B,V,3].
+
+    ``forward``: the ``(renders, factors)`` of a ``get_opticalflow(..., return_renders=True, return_masks=True)`` call on the
+    same arguments with ``keep_saved=True`` among the renderer settings (spares the two renders).  ``fp32``: the same chain
+    with its existing fp32 pieces (raster.backward_textures, fp32 sums and products) -- what an fp32 implementation in the
+    reference's order of operations gives; float32 result."""
+    dtype = F32 if fp32 else np.float64
+    if forward is None:
+        _, renders, factors = get_opticalflow(raster, verts_cam, faces_idx, camintrs, dict(renderer_kw, keep_saved=True), orig_img_size,
+                                              True, ignore_face_idxs, return_renders=True, return_masks=True)
+    else:
+        renders, factors = forward
+    B, V = verts_cam[0].shape[:2]
+    is_ = renders[0]["_saved"]["face_index_map"].shape[1]
+    faces_idx = np.asarray(faces_idx)
+    faces2 = raster.fill_back(faces_idx)[0] if renderer_kw.get("fill_back_", True) else faces_idx
+    gcols = []
+    for ro, factor, g in zip(renders, factors, grad_flows):
+        H, W = g.shape[1:3]
+        full = np.zeros((B, is_, is_, 3), dtype)
+        full[:, :H, :W, :2] = g  # (adjoint of the crop and of dropping the third channel)
+        full = full * factor[:, 0, :, :, None].astype(dtype)  # (... of the mask products)
+        gcols.append(_vertex_colour_grad(raster, ro, faces2, full[:, ::-1], V, fp32))  # (... of the vertical flip)
+    # colours of render 1: (loc2 - loc1, 1); of render 2: (loc1 - loc2, 1)
+    g_loc2 = gcols[0][..., :2] - gcols[1][..., :2]
+    return (_proj2d_grad(verts_cam[0], camintrs[0], -g_loc2, dtype), _proj2d_grad(verts_cam[1], camintrs[1], g_loc2, dtype))

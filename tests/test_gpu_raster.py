@@ -179,7 +179,7 @@ def test_fused_backward_matches_oracle(cuda, kind, B, is_, seed, reference_algo)
                                             ("scene", 1, 600, 15), ("big", 1, 1100, 16), ("big", 1, 1500, 17)])
 def test_fused_backward_strip_widths(cuda, kind, B, is_, seed):
     """Kernel D by strips (raster_bwd.hip) beyond the sizes of CASES: an odd raster (partial last strip, flags marked pixel
-    by pixel), more images than XCDs, rasters that take two lines (257..527) and one line (528..1421) per strip, and one
+    by pixel), more images than XCDs, rasters that take two lines (263..525) and one line (526..1421) per strip (four up to 262: strip_lines), and one
     too wide for LDS (1500: the plane-reading walk) -- all against the C oracle's ordered walk."""
     from handobjectconsist_amd.neurender import rasterize
 
