@@ -43,7 +43,9 @@ def _gather(x, iy, ix):
     b = np.arange(B)[:, None, None]
     vals = x[b, :, iyc, ixc]  # [B,H,W,C]
     vals = np.moveaxis(vals, -1, 1)
-    return vals * inb[:, None].astype(F32), inb
+    # a tap outside the image is SKIPPED (grid_sample's within_bounds test), not multiplied by zero: what the clamped address
+    # holds -- a NaN, say -- never reaches the result
+    return np.where(inb[:, None], vals, F32(0)).astype(F32), inb
 
 
 def grid_sample(x, vgrid, mode="bilinear", with_grad=False):
@@ -68,27 +70,36 @@ def grid_sample(x, vgrid, mode="bilinear", with_grad=False):
     ix_ne, iy_ne = ix_nw + 1, iy_nw
     ix_sw, iy_sw = ix_nw, iy_nw + 1
     ix_se, iy_se = ix_nw + 1, iy_nw + 1
-    nw = (ix_se - ix) * (iy_se - iy)
-    ne = (ix - ix_sw) * (iy_sw - iy)
-    sw = (ix_ne - ix) * (iy - iy_ne)
-    se = (ix - ix_nw) * (iy - iy_nw)
+    with np.errstate(invalid="ignore"):  # (inf - inf at a non-finite position: NaN weights, and no tap in bounds)
+        nw = (ix_se - ix) * (iy_se - iy)
+        ne = (ix - ix_sw) * (iy_sw - iy)
+        sw = (ix_ne - ix) * (iy - iy_ne)
+        se = (ix - ix_nw) * (iy - iy_nw)
 
     def toint(a):
         a = np.where(np.isfinite(a), a, -10)
         return np.clip(a, -10, 1 << 30).astype(np.int64)
 
-    v_nw, _ = _gather(x, toint(iy_nw), toint(ix_nw))
-    v_ne, _ = _gather(x, toint(iy_ne), toint(ix_ne))
-    v_sw, _ = _gather(x, toint(iy_sw), toint(ix_sw))
-    v_se, _ = _gather(x, toint(iy_se), toint(ix_se))
-    out = v_nw * nw[:, None] + v_ne * ne[:, None] + v_sw * sw[:, None] + v_se * se[:, None]
+    v_nw, b_nw = _gather(x, toint(iy_nw), toint(ix_nw))
+    v_ne, b_ne = _gather(x, toint(iy_ne), toint(ix_ne))
+    v_sw, b_sw = _gather(x, toint(iy_sw), toint(ix_sw))
+    v_se, b_se = _gather(x, toint(iy_se), toint(ix_se))
+
+    def tap(inb, v, w):
+        # a skipped tap adds nothing, whatever its weight is (a non-finite position has non-finite weights and no tap in bounds:
+        # the sample is 0, as where the float-to-int conversion of such a position saturates)
+        with np.errstate(invalid="ignore"):
+            return np.where(inb[:, None], v * w[:, None], F32(0)).astype(F32)
+
+    out = tap(b_nw, v_nw, nw) + tap(b_ne, v_ne, ne) + tap(b_sw, v_sw, sw) + tap(b_se, v_se, se)
     out = out.astype(F32)
     if not with_grad:
         return out
-    gix = (-v_nw * (iy_se - iy)[:, None] + v_ne * (iy_sw - iy)[:, None]
-           - v_sw * (iy - iy_ne)[:, None] + v_se * (iy - iy_nw)[:, None])
-    giy = (-v_nw * (ix_se - ix)[:, None] - v_ne * (ix - ix_sw)[:, None]
-           + v_sw * (ix_ne - ix)[:, None] + v_se * (ix - ix_nw)[:, None])
+    with np.errstate(invalid="ignore"):
+        gix = (-tap(b_nw, v_nw, iy_se - iy) + tap(b_ne, v_ne, iy_sw - iy)
+               - tap(b_sw, v_sw, iy - iy_ne) + tap(b_se, v_se, iy - iy_nw))
+        giy = (-tap(b_nw, v_nw, ix_se - ix) - tap(b_ne, v_ne, ix - ix_sw)
+               + tap(b_sw, v_sw, ix_ne - ix) + tap(b_se, v_se, ix - ix_nw))
     return out, gix.astype(F32), giy.astype(F32)
 
 
@@ -132,8 +143,9 @@ def warp_backward(x, flow, grad_out, thresh=0.99999):
     x0 = np.floor(ix)
     y0 = np.floor(iy)
     gx = np.zeros((B, C, H, W), np.float64)
-    taps = [(0, 0, (x0 + 1 - ix) * (y0 + 1 - iy)), (1, 0, (ix - x0) * (y0 + 1 - iy)),
-            (0, 1, (x0 + 1 - ix) * (iy - y0)), (1, 1, (ix - x0) * (iy - y0))]
+    with np.errstate(invalid="ignore"):  # (a non-finite position: NaN weights of taps that are not in bounds)
+        taps = [(0, 0, (x0 + 1 - ix) * (y0 + 1 - iy)), (1, 0, (ix - x0) * (y0 + 1 - iy)),
+                (0, 1, (x0 + 1 - ix) * (iy - y0)), (1, 1, (ix - x0) * (iy - y0))]
     bidx = np.arange(B)[:, None, None].repeat(H, 1).repeat(W, 2)
     for dx, dy, w in taps:
         xi = (x0 + dx)

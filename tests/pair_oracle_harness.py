@@ -1,0 +1,371 @@
+"""What the pair-step test files share (a helper module: nothing pytest collects): the CPU oracle of a case, computed once per
+(case, seed) and never written to; ``Run``, one case on the device with guarded inputs, poisoned render outputs and an empty
+plan cache; ``check_values`` and ``check_grads``, the rules; ``fused_case`` / ``composed_case``, the test bodies.
+
+``CASES``: tests/pair_mesh_cases.py's and tests/pair_border_cases.py's, by name.  A case may bring its own scene
+(``scene_fn(case, seed)``; default ``pair_mesh_cases.scene_of``), its own images and jitter masks (``images_fn(case, seed)``;
+default ``synth.random_images``) and the tag its printed lines start with.
+
+The oracle shares nothing with the product: W.get_opticalflow + W.pair_consist for flows and losses, and W.pair_consist_grad +
+W.get_opticalflow_vertex_grad (float64, pinned to the reference run in tests/test_oracle_warp.py) for the gradient of the
+weighted losses with respect to the four vertex tensors, element by element.
+
+Rules.  Flows: the non-zero pattern under the covered tiles equals the oracle's EXACTLY (the precondition of a per-element
+gradient comparison; seeds are chosen for it, a mismatch fails), NaN under uncovered tiles, values within 1e-4 x max(|ref|, 1).
+Losses (forward, forward + backward, the node's own sum and mean): 2e-5 x max(1, |ref|) (fuzz sweep 8's figures); l2: 1e-5
+relative + 1e-7 (test_gpu_l2_criterion.py's against its reference).  Vertex gradients: |got - ref| <= 1e-4 |ref| + 1e-5 x the
+largest |ref| of the same sample and leaf (test_gpu_raster.py's rule, normalised per sample instead of per tensor).
+"""
+import time
+
+import numpy as np
+import torch
+
+from handobjectconsist_amd.utils import synth
+from oracle import raster_ref as R
+from oracle import warp_ref as W
+from tests import guarded_alloc as G
+from tests import pair_border_cases as PB
+from tests import pair_mesh_cases as P
+
+CASES = {**P.CASES, **PB.CASES}
+assert len(CASES) == len(P.CASES) + len(PB.CASES)
+
+LEAVES = ("hand 1", "object 1", "hand 2", "object 2")
+SECOND_SEED = 100  # added to a case's seed for the second call through its plan
+WM = 3.0           # weight of the batch mean
+
+
+def weights(B):
+    """per-sample weights of loss_fwd, loss_bwd and their sum (distinct per sample), as numpy fp32"""
+    lin = lambda a, b: np.linspace(a, b, B).astype(np.float32)
+    return lin(0.5, 1.5), lin(2.0, 0.25), lin(-0.5, 0.75)
+
+
+def tag(case):
+    return case.get("tag", "PAIR-MESHES")
+
+
+# ---------------------------------------------------------------------------------------------------
+# the oracle, once per (case, seed) and (criterion, batch type): shared by the tests, never written to
+# ---------------------------------------------------------------------------------------------------
+_FORWARD, _ORACLE = {}, {}
+
+
+def crop(case):
+    Wd, H = case["crop"]
+    return Wd, H
+
+
+def oracle_forward(name, seed):
+    key = (name, seed)
+    if key not in _FORWARD:
+        case = CASES[name]
+        s = case.get("scene_fn", P.scene_of)(case, seed)
+        is_ = case["raster"]
+        Rm, tm, dm = P.camera(case["B"], case["per_sample_cam"])
+        kw = dict(R=Rm, t=tm, dist_coeffs=dm, orig_size=is_, image_size=is_, anti_aliasing=False, near=0.1, far=100, eps=1e-3,
+                  num_threads=8, keep_saved=True)
+        t0 = time.perf_counter()
+        flows, renders, factors = W.get_opticalflow(R, [s["verts1"], s["verts2"]], s["faces"], [s["K1"], s["K2"]], kw, orig_img_size=crop(case),
+                                                    ignore_face_idxs=synth.HAND_IGNORE_FACES, return_renders=True, return_masks=True)
+        for f in flows:
+            f.setflags(write=False)
+        _FORWARD[key] = dict(scene=s, kw=kw, flows=flows, renders=renders, factors=factors, seconds=time.perf_counter() - t0)
+    return _FORWARD[key]
+
+
+def images(case, seed, compact):
+    """(image_ref, image, jitter_ref, jitter) as numpy fp32; ``compact``: the images rounded to bf16 (what the compact batch holds)"""
+    Wd, H = crop(case)
+    if "images_fn" in case:
+        im_ref, im, jm_ref, jm = case["images_fn"](case, seed)
+    else:
+        im_ref, im, jm_ref, jm = synth.random_images(case["B"], H, Wd, seed + 1)
+    Cj = case["jitter_channels"]
+    jm_ref, jm = np.ascontiguousarray(jm_ref[:, :Cj]), np.ascontiguousarray(jm[:, :Cj])
+    if compact:
+        im_ref, im = (torch.from_numpy(x).bfloat16().float().numpy() for x in (im_ref, im))
+    return im_ref, im, jm_ref, jm
+
+
+def oracle(name, seed, crit="l1", compact=False):
+    key = (name, seed, crit, compact)
+    if key not in _ORACLE:
+        case = CASES[name]
+        fwd = oracle_forward(name, seed)
+        s, B = fwd["scene"], case["B"]
+        ims = images(case, seed, compact)
+        t0 = time.perf_counter()
+        _, masks, _, _, (lf, lb) = W.pair_consist(fwd["flows"], *ims, True, criterion=crit)
+        wf, wb, ws = weights(B)
+        # total = sum wf lf + sum wb lb + sum ws (lf + lb) + WM mean(lf + lb)
+        cf, cb = wf + ws + np.float32(WM / B), wb + ws + np.float32(WM / B)
+        g21 = W.pair_consist_grad(fwd["flows"], *ims, cf, False, criterion=crit)[1]
+        g12 = W.pair_consist_grad(fwd["flows"], *ims, cb, True, criterion=crit)[0]
+        args = (R, [s["verts1"], s["verts2"]], s["faces"], [s["K1"], s["K2"]], fwd["kw"], [g12, g21], crop(case), synth.HAND_IGNORE_FACES)
+        gv1, gv2 = W.get_opticalflow_vertex_grad(*args, forward=(fwd["renders"], fwd["factors"]))
+        nh = synth.HAND_VERTS
+        _ORACLE[key] = dict(lf=lf.astype(np.float64), lb=lb.astype(np.float64), grads=(gv1[:, :nh], gv1[:, nh:], gv2[:, :nh], gv2[:, nh:]),
+                            full_masks=[m["full_mask"] for m in masks], grad_args=args, seconds=fwd["seconds"] + time.perf_counter() - t0)
+    return _ORACLE[key]
+
+
+# ---------------------------------------------------------------------------------------------------
+# the device run
+# ---------------------------------------------------------------------------------------------------
+
+
+def clear_caches():
+    from handobjectconsist_amd.neurender import rasterize
+    from handobjectconsist_amd.warping import imgflowarp, opticalflow, pairstep
+
+    for cache in (pairstep._PLANS, pairstep._FACES64, opticalflow._FACES2_CACHE, opticalflow._LUT_CACHE, opticalflow._LUT_BY_ID,
+                  rasterize._BG_CACHE, imgflowarp._GRID_CACHE):
+        cache.clear()
+
+
+class Run:
+    """one case on the device: guarded inputs, a renderer, the four leaves"""
+
+    def __init__(self, cuda, monkeypatch, name):
+        from handobjectconsist_amd.neurender.renderer import Renderer
+
+        self.cuda, self.mp, self.name, self.case = cuda, monkeypatch, name, CASES[name]
+        clear_caches()
+        self.alloc = G.GuardedAllocator(cuda)
+        self.alloc.install(monkeypatch)
+        case, is_ = self.case, self.case["raster"]
+        Rm, tm, dm = P.camera(case["B"], case["per_sample_cam"])
+        self.ren = Renderer(image_size=is_, R=self.up(Rm), t=self.up(tm), K=self.up(np.ones((1, 3, 3), np.float32)), dist_coeffs=self.up(dm),
+                            orig_size=is_, anti_aliasing=False, fill_back=True, near=0.1, no_light=True, light_intensity_ambient=0.8)
+        cus = torch.cuda.get_device_properties(cuda).multi_processor_count
+        print(f"{tag(case)} {name}: {cus} compute units" + ("" if cus == 256 else
+              " -- NOT 256: the plan branches the host tests prove do not describe this run"))
+
+    def up(self, a, grad=False):
+        """a test-made input in guarded storage"""
+        with self.alloc.paused():
+            x = torch.from_numpy(np.ascontiguousarray(a)).to(self.cuda).clone()
+        x = self.alloc.guard(x)
+        return x.requires_grad_(True) if grad else x
+
+    def close(self):
+        damage = self.alloc.check()
+        self.alloc.uninstall()
+        clear_caches()
+        assert not damage, "\n".join(damage)
+
+    def batch(self, seed, compact):
+        im_ref, im, jm_ref, jm = images(self.case, seed, False)
+        if compact == "widened":
+            im_ref, im = (torch.from_numpy(x).bfloat16().float().numpy() for x in (im_ref, im))
+        out = [self.up(x) for x in (im_ref, im, jm_ref, jm)]
+        if compact is True:
+            with self.alloc.paused():
+                out = [out[0].bfloat16(), out[1].bfloat16(), out[2].to(torch.uint8), out[3].to(torch.uint8)]
+            out = [self.alloc.guard(x) for x in out]
+        return out
+
+    def total(self, lf, lb, lsum, mean):
+        wf, wb, ws = (self.up(w) for w in weights(self.case["B"]))
+        return (lf * wf).sum() + (lb * wb).sum() + (lsum * ws).sum() + WM * mean
+
+    def fused(self, seed, path, crit_code, compact=False, poison=True):
+        """flow_pair_loss on (hand, object) parts: (result or None, leaves)"""
+        from handobjectconsist_amd.warping import opticalflow
+
+        self.mp.setattr(opticalflow, "DEBUG_POISON_RENDER_OUTPUTS", poison)
+        self.mp.setattr(opticalflow, "USE_PAIR_STEP", path == "step")
+        case, s = self.case, oracle_forward(self.name, seed)["scene"]
+        B = case["B"]
+        hand_faces = s["hand_faces"][None].repeat(B, 0) if case["hand_batched"] else s["hand_faces"]
+        leaves = [self.up(s[k], grad=True) for k in ("hand_verts1", "obj_verts1", "hand_verts2", "obj_verts2")]
+        res = opticalflow.flow_pair_loss([(leaves[0], leaves[1]), (leaves[2], leaves[3])], (self.up(hand_faces), self.up(s["obj_faces"])),
+                                         [self.up(s["K1"]), self.up(s["K2"])], self.ren, crop(case), *self.batch(seed, compact),
+                                         ignore_face_idxs=synth.HAND_IGNORE_FACES, with_sum=True, with_mean="sum", criterion=crit_code)
+        return res, leaves
+
+    def composed(self, seed, crit_name):
+        """get_opticalflow + pair_consist on the concatenated mesh: ((lf, lb, flows, lsum, mean), [verts1, verts2])"""
+        from handobjectconsist_amd.optim.pyramidloss import PyramidCriterion
+        from handobjectconsist_amd.warping import imgflowarp, opticalflow
+
+        self.mp.setattr(opticalflow, "DEBUG_POISON_RENDER_OUTPUTS", True)
+        case, s = self.case, oracle_forward(self.name, seed)["scene"]
+        v1, v2 = self.up(s["verts1"], grad=True), self.up(s["verts2"], grad=True)
+        flows = opticalflow.get_opticalflow([v1, v2], self.up(s["faces"]), [self.up(s["K1"]), self.up(s["K2"])], self.ren, orig_img_size=crop(case),
+                                            ignore_face_idxs=synth.HAND_IGNORE_FACES)
+        batch = self.batch(seed, False)
+        crit = PyramidCriterion(crit_name)
+        both = imgflowarp.pair_consist(flows, *batch, crit, use_backward=True, outputs="loss")[0]
+        lf = imgflowarp.pair_consist(flows, *batch, crit, use_backward=False, outputs="loss")[0]
+        return (lf, both - lf, flows, both, both.mean()), [v1, v2]
+
+
+def units(err, tol):
+    """the largest error in units of its tolerance (an error where the tolerance is zero: inf)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = np.where(tol > 0, err / np.where(tol > 0, tol, 1.0), np.where(err > 0, np.inf, 0.0))
+    return float(u.max()) if u.size else 0.0
+
+
+def check_values(name, what, res, ref_flows, orc, crit, sparse, zero_samples=()):
+    """flows (pattern, uncovered tiles, values) and the four loss outputs against the oracle; prints the figures.
+    ``zero_samples``: samples whose losses are exactly zero in the oracle and have to be on the device"""
+    lf, lb, flows, lsum, mean = res
+    case = CASES[name]
+    B, is_ = case["B"], case["raster"]
+    Wd, H = crop(case)
+    ref = np.concatenate(ref_flows, 0)
+    if sparse:
+        base = flows[0]._base
+        hit = base._hoc_coverage[0]
+        words = hit.contiguous().view(torch.int32).view(2 * B, (is_ + 7) // 8, (is_ + 31) // 32).cpu().numpy() != 0
+        yy, xx = np.mgrid[0:H, 0:Wd]
+        defined = words[:, (is_ - 1 - yy) >> 3, xx >> 5]
+        got = base.detach().cpu().numpy()
+        assert np.isnan(got[~defined]).all(), f"{what}: something is written under uncovered tiles"
+        assert not (ref[~defined] != 0).any(), f"{what}: the oracle has a flow under a tile the render left uncovered"
+    else:
+        got = np.concatenate([f.detach().cpu().numpy() for f in flows], 0)
+        defined = np.ones(got.shape[:3], bool)
+    assert tuple(got.shape) == ref.shape
+    assert np.isfinite(got[defined]).all(), f"{what}: non-finite flow under a covered tile"
+    differ = int(((got != 0) != (ref != 0))[defined].sum())
+    assert differ == 0, f"{what}: the flows' non-zero pattern differs from the oracle's at {differ} of {int((ref != 0).sum())} elements"
+    assert (ref != 0).any()
+    err = np.abs(got - ref)[defined]
+    flow_units = units(err, np.full(err.shape, 1e-4 * max(float(np.abs(ref).max()), 1.0)))
+    n = lambda x: x.detach().double().cpu().numpy()
+    rf, rb = orc["lf"], orc["lb"]
+    pairs = (("loss_fwd", n(lf), rf), ("loss_fwd + loss_bwd", n(lf) + n(lb), rf + rb), ("the node's sum", n(lsum), rf + rb),
+             ("the node's mean", n(mean).reshape(1), np.array([(rf + rb).mean()])))
+    loss_units = 0.0
+    for label, g, r in pairs:
+        assert np.isfinite(g).all(), f"{what}: {label} is not finite"
+        tol = (1e-5 * np.abs(r) + 1e-7) if crit == "l2" else np.full(r.shape, 2e-5 * max(1.0, float(np.abs(r).max())))
+        loss_units = max(loss_units, units(np.abs(g - r), tol))
+        for b in zero_samples:
+            if g.shape[0] == B:
+                assert r[b] == 0 and g[b] == 0, f"{what}: {label} of sample {b} must be exactly zero (oracle {r[b]!r}, device {g[b]!r})"
+    print(f"{tag(case)} {what}: flows {flow_units:.3f}, losses {loss_units:.3f} (units of their rules); loss_fwd {rf.mean():.4f} loss_bwd {rb.mean():.4f}")
+    assert rf.max() > 0 and rb.max() > 0
+    assert flow_units <= 1.0, f"{what}: flow values"
+    assert loss_units <= 1.0, f"{what}: losses"
+
+
+# case -> (fp32 chain's error, bound) in units of the rule, where DESIGN section 2's factor applies (see check_grads)
+FP32_CHAIN = {}
+
+
+def check_grads(name, what, grads, orc, zero_samples=()):
+    """each vertex gradient against the float64 oracle: 1e-4 relative + 1e-5 x the largest |gradient| of the same sample and leaf.
+    ``zero_samples``: samples whose gradient is all zero in the oracle and has to be, exactly, on the device"""
+    worst = 0.0
+    for got, ref, leaf in zip(grads, orc["grads"], LEAVES):
+        if ref.shape[1] == 0:
+            assert got is None or got.numel() == 0
+            continue
+        g = got.detach().double().cpu().numpy()
+        assert g.shape == ref.shape and np.isfinite(g).all(), (what, leaf)
+        for b in zero_samples:
+            assert not ref[b].any() and not g[b].any(), f"{what}: d/d {leaf} of sample {b} must be exactly zero"
+        scale = np.abs(ref).max(axis=(1, 2), keepdims=True)
+        assert scale.max() > 0, (what, leaf)
+        u = units(np.abs(g - ref), 1e-4 * np.abs(ref) + 1e-5 * scale)
+        print(f"{tag(CASES[name])} {what}: d/d {leaf}: {u:.3f} of the rule (largest |gradient| {scale.max():.3e})")
+        worst = max(worst, u)
+    bound = 1.0
+    if worst > 1.0:
+        # the same oracle chain with its existing fp32 pieces (R.backward_textures, fp32 sums) against the float64 chain: what an
+        # fp32 evaluation in the reference's order is off by under this rule (printed; a case whose bound it sets is in FP32_CHAIN)
+        f32 = W.get_opticalflow_vertex_grad(*orc["grad_args"], fp32=True)
+        nh = synth.HAND_VERTS
+        chain = 0.0
+        for g, ref in zip((f32[0][:, :nh], f32[0][:, nh:], f32[1][:, :nh], f32[1][:, nh:]), orc["grads"]):
+            if ref.shape[1]:
+                chain = max(chain, units(np.abs(g.astype(np.float64) - ref), 1e-4 * np.abs(ref) + 1e-5 * np.abs(ref).max(axis=(1, 2), keepdims=True)))
+        print(f"{tag(CASES[name])} {what}: the oracle's fp32 chain is {chain:.3f} of the rule off its float64 chain")
+        if name in FP32_CHAIN:
+            bound = FP32_CHAIN[name][1]
+    assert worst <= bound, f"{what}: vertex gradients at {worst:.3f} of the rule (bound {bound})"
+
+
+def crit_code(crit):
+    from handobjectconsist_amd import _lib
+
+    return {"l1": _lib.CRITERION_L1, "l2": _lib.CRITERION_L2}[crit]
+
+
+def fused_case(cuda, monkeypatch, name, path, crit="l1", zero_samples=()):
+    from handobjectconsist_amd.warping import pairstep
+
+    case = CASES[name]
+    run = Run(cuda, monkeypatch, name)
+    try:
+        for call, seed in enumerate((case["seed"], case["seed"] + SECOND_SEED)[:2 if path == "step" else 1]):
+            what = f"{name} {path} {crit} call {call}"
+            orc = oracle(name, seed, crit)
+            print(f"{tag(case)} {what}: oracle {orc['seconds']:.1f} s")
+            # (the second call: no poison, so that the plan vouches for its list header and the scratch keeps the first seed's values)
+            res, leaves = run.fused(seed, path, crit_code(crit), poison=call == 0)
+            assert res is not None, f"{what}: the fused path must take this case"
+            lf, lb, flows, lsum, mean = res
+            check_values(name, what, res, oracle_forward(name, seed)["flows"], orc, crit, sparse=True, zero_samples=zero_samples)
+            grads = torch.autograd.grad(run.total(lf, lb, lsum, mean), leaves)
+            check_grads(name, what, grads, orc, zero_samples)
+            if path == "step":
+                assert len(pairstep._PLANS) == 1, "both calls go through one plan"
+                plan = next(iter(pairstep._PLANS.values()))
+                assert bool(plan.st.flags & pairstep.LIST_CLEAN) == (call == 1), "the second call runs on the list header the first one left clean"
+    finally:
+        run.close()
+
+
+def compact_case(cuda, monkeypatch, name):
+    """bf16 images and u8 masks as they are: losses, flows and coverage bit for bit those of the widened fp32 batch (as
+    test_gpu_compact_batch.py asserts for the one scene), which in turn meets the oracle on the rounded images"""
+    case = CASES[name]
+    run = Run(cuda, monkeypatch, name)
+    try:
+        seed = case["seed"]
+        orc = oracle(name, seed, "l1", compact=True)
+        out = {}
+        for kind in ("widened", True):
+            what = f"{name} step l1 {'compact' if kind is True else 'widened'}"
+            res, leaves = run.fused(seed, "step", crit_code("l1"), compact=kind)
+            assert res is not None, what
+            lf, lb, flows, lsum, mean = res
+            check_values(name, what, res, oracle_forward(name, seed)["flows"], orc, "l1", sparse=True)
+            check_grads(name, what, torch.autograd.grad(run.total(lf, lb, lsum, mean), leaves), orc)
+            base = flows[0]._base
+            hit = base._hoc_coverage[0].clone()
+            out[kind] = [x.detach().clone() for x in (lf, lb, lsum, mean.reshape(1))] + [torch.nan_to_num(base.detach(), nan=-7.0), hit]
+        for x, y, label in zip(out[True], out["widened"], ("loss_fwd", "loss_bwd", "loss_bwd + loss_fwd", "batch mean", "flows", "coverage bytes")):
+            assert torch.equal(x, y), label
+        assert not torch.equal(run.batch(seed, "widened")[1], run.batch(seed, False)[1]), "the images must actually lose bits in bf16"
+    finally:
+        run.close()
+
+
+def composed_case(cuda, monkeypatch, name, fused_takes_it=False):
+    """get_opticalflow + pair_consist against the same oracle; ``fused_takes_it`` False: flow_pair_loss must answer None first"""
+    case = CASES[name]
+    run = Run(cuda, monkeypatch, name)
+    try:
+        seed = case["seed"]
+        what = f"{name} composed l1"
+        orc = oracle(name, seed, "l1")
+        print(f"{tag(case)} {what}: oracle {orc['seconds']:.1f} s")
+        if not fused_takes_it:
+            for path in ("step", "node"):
+                res, _ = run.fused(seed, path, crit_code("l1"))
+                assert res is None, f"{name}: flow_pair_loss must hand this pair to the composed path ({path})"
+        res, (v1, v2) = run.composed(seed, "l1")
+        check_values(name, what, res, oracle_forward(name, seed)["flows"], orc, "l1", sparse=False)
+        g1, g2 = torch.autograd.grad(run.total(res[0], res[1], res[3], res[4]), [v1, v2])
+        nh = synth.HAND_VERTS
+        check_grads(name, what, (g1[:, :nh], g1[:, nh:], g2[:, :nh], g2[:, nh:]), orc)
+    finally:
+        run.close()
