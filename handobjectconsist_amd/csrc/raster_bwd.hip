@@ -2580,7 +2580,10 @@ int mr::launch_unit_scatter_tiles(const UnitScatterArgs& a, hipStream_t s) {
     sp.split = a.batch_size / 2; sp.H = a.height; sp.W = a.width;
     sp.unit_grad = a.unit_grad; sp.unit_max = a.unit_grad_max; sp.sums = a.sums; sp.gl_fwd = a.grad_loss_fwd; sp.gl_bwd = a.grad_loss_bwd;
     sp.gl_sum = a.grad_loss_sum; sp.gl_mean = a.grad_mean; sp.mean_div = (float)(a.batch_size / 2); sp.mean_of = a.mean_of;
-    const bool args_ok = a.unit_grad && a.unit_grad_max && a.sums && (a.grad_loss_fwd || a.grad_loss_sum || a.grad_mean) && a.tile_hit &&
+    // (any of the four incoming gradients makes a call, loss_bwd's alone included: the kernels read each behind its null check,
+    // and a direction none of them reaches has a zero coefficient)
+    const bool args_ok = a.unit_grad && a.unit_grad_max && a.sums && (a.grad_loss_fwd || a.grad_loss_bwd || a.grad_loss_sum || a.grad_mean) &&
+                         a.tile_hit &&
                          a.height > 0 && a.width >= 2 && a.height <= a.image_size && a.width <= a.image_size &&
                          (int64_t)a.height * a.width <= (1LL << 29);
     // (the covered-tile lists need the workgroup split's head room, grid > images: every launch has ST_G or more per image)

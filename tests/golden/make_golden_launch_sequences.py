@@ -18,7 +18,9 @@ hashes of those launches differ.  The ``build.source_hash()`` of the recorded tr
 The file is not regenerated from later code: a line that differs is a launch whose kernel, grid, LDS size or arguments changed.  When a decision is MEANT to change, record the file again from the commit
 before the change, check that the test passes there, make the change, record once more and review the diff of the two
 files line by line: it is the list of launches that moved.  tests/test_launch_sequences_host.py imports the builder and the
-runner from this file.
+runner from this file.  (Recorded that way since: the pair step's "bwd-only" case, a backward call with grad_loss_bwd as its
+one incoming gradient -- `R -1` before launch_unit_scatter_tiles accepted it, the scatter and the vertex launch after; no other
+line moved.)
 
 The sizes of a kernel's explicit arguments come from the code-object metadata (``.args``) of the device assembly
 (``--cuda-device-only -S``); objects and argument tables are cached under tests/host/build/, one per source, keyed on the

@@ -6,11 +6,83 @@
 // output rows: key=value pairs, `sides` = the side of every part (pair_part_range), comma-separated
 #include "../../handobjectconsist_amd/csrc/launch_plan.hpp"
 
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
+#include <vector>
 
 using namespace mr;
 
-int main() {
+// `launch_plan_cases scatter`: the pair step's backward scatter (unit_scatter_tiles_kernel, raster_bwd.hip) at given counts of
+// covered 32 x 8 tiles per image, on a device of 256 compute units: how many workgroups every image gets and, for every
+// workgroup, the `terms` and `headroom` the kernel computes.  tests/test_pair_upstream_cases_host.py feeds it the oracle's
+// coverage.
+// input rows:  B2 V is n_0 ... n_(B2-1)
+// output rows: groups=<plan's workgroups per image> grid= q= used= per_image=<workgroups of image 0,1,..> wgs=<image.tiles.terms.headroom;...> max_headroom=
+//
+// Restated from raster_bwd.hip (scatter_tiles_body; constants beside it):
+//   constexpr int ST_FIX_BITS = 37, ST_SUM_BITS = 50;
+// the WORK split -- q tiles per workgroup, at least one per wave, such that sum ceil(n_b / q) fits the grid:
+//   int q = ST_WAVES, used = 0, N = 0;   ... N += n_b; used += (n_b + ST_WAVES - 1) / ST_WAVES;
+//   if (used > grid) { const int room = max(grid - B2, 1); q = max(ST_WAVES, (N + room - 1) / room); used = sum (n_b + q - 1) / q;
+//                      if (used > grid) used = grid; }
+//   const int parts = (n + q - 1) / q;   (image b takes slots [base, base + parts) of the `used` slots; every slot below `used`
+//                                         is taken by one workgroup: the XCD shares [x used / 8, (x + 1) used / 8) tile [0, used))
+//   const int each = nb / pb, rem = nb % pb;   n_hits = each + (part < rem ? 1 : 0);   part = 0; G = 1;
+// and the three lines in front of pass 2:
+//   const int rem = n_hits - part * ST_WAVES;
+//   const long long terms = 3LL * ST_TW * ST_TH * ((rem / (G * ST_WAVES)) * ST_WAVES + min(rem % (G * ST_WAVES), ST_WAVES));
+//   int headroom = 0;   while ((terms >> headroom) >= (1LL << (ST_SUM_BITS - ST_FIX_BITS))) headroom++;
+static int scatter_cases() {
+    constexpr int FIX_BITS = 37, SUM_BITS = 50;
+    int B2, V, is;
+    while (std::scanf("%d %d %d", &B2, &V, &is) == 3) {
+        if (B2 <= 0 || B2 > 4096) return 1;
+        std::vector<int> ncov(B2);
+        for (int b = 0; b < B2; b++)
+            if (std::scanf("%d", &ncov[b]) != 1 || ncov[b] < 0) return 1;
+        const ScatterPlan s = plan_scatter_tiles(B2, V, is, false, true);
+        if (s.status != 0) { std::printf("status=%d\n", s.status); continue; }
+        const int grid = (int)s.wgs, T = s.tiles_x * s.tiles_y;
+        int q = ST_WAVES, used = 0, N = 0;
+        for (int n : ncov) {
+            if (n > T) return 1;
+            N += n; used += (n + ST_WAVES - 1) / ST_WAVES;
+        }
+        if (used > grid) {
+            const int room = std::max(grid - B2, 1);
+            q = std::max(ST_WAVES, (N + room - 1) / room);
+            used = 0;
+            for (int n : ncov) used += (n + q - 1) / q;
+            if (used > grid) used = grid;
+        }
+        std::printf("status=0 groups=%d grid=%d q=%d used=%d per_image=", s.groups, grid, q, used);
+        for (int b = 0; b < B2; b++) std::printf("%s%d", b ? "," : "", (ncov[b] + q - 1) / q);
+        std::printf(" wgs=");
+        int base = 0, max_headroom = 0;
+        bool first = true;
+        for (int b = 0; b < B2; b++) {
+            const int nb = ncov[b], pb = (nb + q - 1) / q;
+            for (int part = 0; part < pb && base + part < used; part++) {
+                const int each = nb / pb, rem_b = nb % pb;
+                const int n_hits = each + (part < rem_b ? 1 : 0);
+                const int G = 1, rem = n_hits;  // (part = 0; G = 1)
+                const long long terms = 3LL * ST_TW * ST_TH * ((rem / (G * ST_WAVES)) * ST_WAVES + std::min(rem % (G * ST_WAVES), ST_WAVES));
+                int headroom = 0;
+                while ((terms >> headroom) >= (1LL << (SUM_BITS - FIX_BITS))) headroom++;
+                std::printf("%s%d.%d.%lld.%d", first ? "" : ";", b, n_hits, terms, headroom);
+                first = false;
+                max_headroom = std::max(max_headroom, headroom);
+            }
+            base += pb;
+        }
+        std::printf(" max_headroom=%d\n", max_headroom);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "scatter") == 0) return scatter_cases();
     int B2, V, Fh, Fo, fill_back, is;
     while (std::scanf("%d %d %d %d %d %d", &B2, &V, &Fh, &Fo, &fill_back, &is) == 6) {
         // the request of mr_pair_step_forward's render (raster_fwd.hip: launch_bins under launch_flow_render)

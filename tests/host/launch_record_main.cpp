@@ -276,6 +276,8 @@ void pair_step_cases(bool all) {
     { MrPairStep s = pair_step(8, 778, 1000, 1538, 2000, 256, 0, 0, 0); s.want_grad = 0; both("no gradient", s); }
     { MrPairStep s = pair_step(8, 778, 1000, 1538, 2000, 256, 0, 0, 0); s.grad_loss_fwd = nullptr; s.grad_loss_bwd = nullptr; s.grad_mean = P(28);
       s.mean_of = 8; both("mean", s); }
+    // (a loss that uses loss_bwd alone: the backward call is made with that one incoming gradient, and launches)
+    { MrPairStep s = pair_step(8, 778, 1000, 1538, 2000, 256, 0, 0, 0); s.grad_loss_fwd = nullptr; both("bwd-only", s); }
     // one argument off each (named by what is off: the forward and the backward call do not refuse the same ones)
     { MrPairStep s = pair_step(8, 778, 1000, 1538, 2000, 256, 0, 0, 0); s.scratch_bytes -= 1; both("scratch-1", s); }
     { MrPairStep s = pair_step(8, 778, 1000, 1538, 2000, 256, 0, 0, 0); s.saved_bytes -= 1; both("saved-1", s); }

@@ -1,8 +1,9 @@
 """What the pair-step test files share (a helper module: nothing pytest collects): the CPU oracle of a case, computed once per
 (case, seed) and never written to; ``Run``, one case on the device with guarded inputs, poisoned render outputs and an empty
-plan cache; ``check_values`` and ``check_grads``, the rules; ``fused_case`` / ``composed_case``, the test bodies.
+plan cache; ``check_values`` and ``check_grads``, the rules; ``fused_case`` / ``composed_case``, the test bodies; ``Upstream``,
+the upstream gradient of the four outputs as a parameter of the oracle, ``Run.total`` and ``fused_case`` (default: ``weights``).
 
-``CASES``: tests/pair_mesh_cases.py's and tests/pair_border_cases.py's, by name.  A case may bring its own scene
+``CASES``: tests/pair_mesh_cases.py's, tests/pair_border_cases.py's and tests/pair_upstream_cases.py's, by name.  A case may bring its own scene
 (``scene_fn(case, seed)``; default ``pair_mesh_cases.scene_of``), its own images and jitter masks (``images_fn(case, seed)``;
 default ``synth.random_images``) and the tag its printed lines start with.
 
@@ -27,9 +28,10 @@ from oracle import warp_ref as W
 from tests import guarded_alloc as G
 from tests import pair_border_cases as PB
 from tests import pair_mesh_cases as P
+from tests import pair_upstream_cases as PU
 
-CASES = {**P.CASES, **PB.CASES}
-assert len(CASES) == len(P.CASES) + len(PB.CASES)
+CASES = {**P.CASES, **PB.CASES, **PU.CASES}
+assert len(CASES) == len(P.CASES) + len(PB.CASES) + len(PU.CASES)
 
 LEAVES = ("hand 1", "object 1", "hand 2", "object 2")
 SECOND_SEED = 100  # added to a case's seed for the second call through its plan
@@ -40,6 +42,41 @@ def weights(B):
     """per-sample weights of loss_fwd, loss_bwd and their sum (distinct per sample), as numpy fp32"""
     lin = lambda a, b: np.linspace(a, b, B).astype(np.float32)
     return lin(0.5, 1.5), lin(2.0, 0.25), lin(-0.5, 0.75)
+
+
+class Upstream:
+    """The upstream gradient of the four outputs: the loss is sum wf loss_fwd + sum wb loss_bwd + sum ws (loss_fwd + loss_bwd)
+    + wm x the node's mean.  ``wf`` / ``wb`` / ``ws``: per-sample fp32 arrays, ``wm``: a scalar; None: that output is not in the
+    loss.  ``with_mean``: what the node's mean is over -- "sum" (loss_fwd + loss_bwd) or "fwd" (loss_fwd alone)."""
+
+    def __init__(self, wf=None, wb=None, ws=None, wm=None, with_mean="sum"):
+        assert with_mean in ("sum", "fwd")
+        f = lambda w: None if w is None else np.asarray(w, np.float32)
+        self.wf, self.wb, self.ws, self.wm, self.with_mean = f(wf), f(wb), f(ws), None if wm is None else float(wm), with_mean
+
+    def terms(self, B):
+        """the fp32 terms of every sample's two coefficients, absent ones left out: ([B] lists for cf, [B] lists for cb).  The
+        mean's share is fl(wm / B), formed in fp32 as the device and torch.mean's backward form it"""
+        share = None if self.wm is None else np.float32(self.wm) / np.float32(B)
+        tf = [[np.float32(w[b]) for w in (self.wf, self.ws) if w is not None] + ([share] if share is not None else []) for b in range(B)]
+        tb = [[np.float32(w[b]) for w in (self.wb, self.ws) if w is not None] + ([share] if share is not None and self.with_mean == "sum" else [])
+              for b in range(B)]
+        return tf, tb
+
+    def coefficients(self, B):
+        """(cf, cb), float64 [B]: the per-sample coefficients of loss_fwd and loss_bwd"""
+        tf, tb = self.terms(B)
+        return (np.array([sum(map(np.float64, t), np.float64(0)) for t in tf]), np.array([sum(map(np.float64, t), np.float64(0)) for t in tb]))
+
+    def scaled(self, k):
+        m = lambda w: None if w is None else w * np.float32(k)
+        return Upstream(m(self.wf), m(self.wb), m(self.ws), None if self.wm is None else self.wm * k, self.with_mean)
+
+
+def default_upstream(B):
+    """``weights(B)`` and WM as an Upstream (what every test without a spec of its own runs)"""
+    wf, wb, ws = weights(B)
+    return Upstream(wf, wb, ws, WM, "sum")
 
 
 def tag(case):
@@ -89,7 +126,11 @@ def images(case, seed, compact):
     return im_ref, im, jm_ref, jm
 
 
-def oracle(name, seed, crit="l1", compact=False):
+def oracle(name, seed, crit="l1", compact=False, upstream=None):
+    """``upstream`` None: the default weights, the gradient as one chain on their fp32 coefficients (the numbers every test had
+    before the upstream became a parameter).  An Upstream: ``oracle_units``' two unit results times the spec's coefficients."""
+    if upstream is not None:
+        return oracle_upstream(name, seed, upstream, crit, compact)
     key = (name, seed, crit, compact)
     if key not in _ORACLE:
         case = CASES[name]
@@ -109,6 +150,45 @@ def oracle(name, seed, crit="l1", compact=False):
         _ORACLE[key] = dict(lf=lf.astype(np.float64), lb=lb.astype(np.float64), grads=(gv1[:, :nh], gv1[:, nh:], gv2[:, :nh], gv2[:, nh:]),
                             full_masks=[m["full_mask"] for m in masks], grad_args=args, seconds=fwd["seconds"] + time.perf_counter() - t0)
     return _ORACLE[key]
+
+
+_UNITS = {}
+
+
+def oracle_units(name, seed, crit="l1", compact=False):
+    """(Gf, Gb): the four leaves' gradients (float64 [B,V*,3], read-only) of sum_b loss_fwd[b] and of sum_b loss_bwd[b].  A
+    sample's losses depend on that sample's vertices alone and the chain from a loss to the vertices is linear in the loss's
+    coefficient, so the gradient of ANY weighted loss is cf[b] Gf[b] + cb[b] Gb[b] -- formed in float64 at any magnitude of the
+    coefficients, where a chain run on the coefficients themselves would leave fp32's range inside W.pair_consist_grad.
+    (tests/test_pair_upstream_cases_host.py checks the combination against the one-chain oracle at the default weights.)"""
+    key = (name, seed, crit, compact)
+    if key not in _UNITS:
+        orc = oracle(name, seed, crit, compact)
+        case, fwd = CASES[name], oracle_forward(name, seed)
+        ims = images(case, seed, compact)
+        one = np.ones(case["B"], np.float32)
+        g21 = W.pair_consist_grad(fwd["flows"], *ims, one, False, criterion=crit)[1]
+        g12 = W.pair_consist_grad(fwd["flows"], *ims, one, True, criterion=crit)[0]
+        a = orc["grad_args"]
+        nh = synth.HAND_VERTS
+        out = []
+        for pair in ([np.zeros_like(g12), g21], [g12, np.zeros_like(g21)]):
+            gv1, gv2 = W.get_opticalflow_vertex_grad(*a[:5], pair, *a[6:], forward=(fwd["renders"], fwd["factors"]))
+            leaves = (gv1[:, :nh], gv1[:, nh:], gv2[:, :nh], gv2[:, nh:])
+            for g in leaves:
+                g.setflags(write=False)
+            out.append(leaves)
+        _UNITS[key] = tuple(out)
+    return _UNITS[key]
+
+
+def oracle_upstream(name, seed, upstream, crit="l1", compact=False):
+    """the oracle's dict with the gradients of ``upstream``'s loss (finite coefficients); losses and masks are the shared ones"""
+    orc = oracle(name, seed, crit, compact)
+    Gf, Gb = oracle_units(name, seed, crit, compact)
+    cf, cb = upstream.coefficients(CASES[name]["B"])
+    assert np.isfinite(cf).all() and np.isfinite(cb).all(), "a non-finite coefficient has no oracle: the test replaces it"
+    return dict(orc, grads=tuple(cf[:, None, None] * f + cb[:, None, None] * b for f, b in zip(Gf, Gb)), grad_args=None)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -167,12 +247,19 @@ class Run:
             out = [self.alloc.guard(x) for x in out]
         return out
 
-    def total(self, lf, lb, lsum, mean):
-        wf, wb, ws = (self.up(w) for w in weights(self.case["B"]))
-        return (lf * wf).sum() + (lb * wb).sum() + (lsum * ws).sum() + WM * mean
+    def total(self, lf, lb, lsum, mean, upstream=None):
+        """the loss of ``upstream`` (None: the default weights); an output whose weight is None stays out of the graph.  None
+        when no output is in the loss"""
+        if upstream is None:
+            wf, wb, ws = (self.up(w) for w in weights(self.case["B"]))
+            return (lf * wf).sum() + (lb * wb).sum() + (lsum * ws).sum() + WM * mean
+        terms = [(out * self.up(w)).sum() for out, w in ((lf, upstream.wf), (lb, upstream.wb), (lsum, upstream.ws)) if w is not None]
+        if upstream.wm is not None:
+            terms.append(upstream.wm * mean)
+        return sum(terms[1:], terms[0]) if terms else None
 
-    def fused(self, seed, path, crit_code, compact=False, poison=True):
-        """flow_pair_loss on (hand, object) parts: (result or None, leaves)"""
+    def fused(self, seed, path, crit_code, compact=False, poison=True, with_mean="sum", want=LEAVES):
+        """flow_pair_loss on (hand, object) parts: (result or None, leaves); ``want``: the leaves that require a gradient"""
         from handobjectconsist_amd.warping import opticalflow
 
         self.mp.setattr(opticalflow, "DEBUG_POISON_RENDER_OUTPUTS", poison)
@@ -180,10 +267,10 @@ class Run:
         case, s = self.case, oracle_forward(self.name, seed)["scene"]
         B = case["B"]
         hand_faces = s["hand_faces"][None].repeat(B, 0) if case["hand_batched"] else s["hand_faces"]
-        leaves = [self.up(s[k], grad=True) for k in ("hand_verts1", "obj_verts1", "hand_verts2", "obj_verts2")]
+        leaves = [self.up(s[k], grad=leaf in want) for k, leaf in zip(("hand_verts1", "obj_verts1", "hand_verts2", "obj_verts2"), LEAVES)]
         res = opticalflow.flow_pair_loss([(leaves[0], leaves[1]), (leaves[2], leaves[3])], (self.up(hand_faces), self.up(s["obj_faces"])),
                                          [self.up(s["K1"]), self.up(s["K2"])], self.ren, crop(case), *self.batch(seed, compact),
-                                         ignore_face_idxs=synth.HAND_IGNORE_FACES, with_sum=True, with_mean="sum", criterion=crit_code)
+                                         ignore_face_idxs=synth.HAND_IGNORE_FACES, with_sum=True, with_mean=with_mean, criterion=crit_code)
         return res, leaves
 
     def composed(self, seed, crit_name):
@@ -210,9 +297,10 @@ def units(err, tol):
     return float(u.max()) if u.size else 0.0
 
 
-def check_values(name, what, res, ref_flows, orc, crit, sparse, zero_samples=()):
+def check_values(name, what, res, ref_flows, orc, crit, sparse, zero_samples=(), mean_of="sum"):
     """flows (pattern, uncovered tiles, values) and the four loss outputs against the oracle; prints the figures.
-    ``zero_samples``: samples whose losses are exactly zero in the oracle and have to be on the device"""
+    ``zero_samples``: samples whose losses are exactly zero in the oracle and have to be on the device; ``mean_of``: what the
+    node's mean is over ("sum": loss_fwd + loss_bwd, "fwd": loss_fwd)"""
     lf, lb, flows, lsum, mean = res
     case = CASES[name]
     B, is_ = case["B"], case["raster"]
@@ -240,7 +328,7 @@ def check_values(name, what, res, ref_flows, orc, crit, sparse, zero_samples=())
     n = lambda x: x.detach().double().cpu().numpy()
     rf, rb = orc["lf"], orc["lb"]
     pairs = (("loss_fwd", n(lf), rf), ("loss_fwd + loss_bwd", n(lf) + n(lb), rf + rb), ("the node's sum", n(lsum), rf + rb),
-             ("the node's mean", n(mean).reshape(1), np.array([(rf + rb).mean()])))
+             ("the node's mean", n(mean).reshape(1), np.array([(rf + rb).mean() if mean_of == "sum" else rf.mean()])))
     loss_units = 0.0
     for label, g, r in pairs:
         assert np.isfinite(g).all(), f"{what}: {label} is not finite"
@@ -259,16 +347,26 @@ def check_values(name, what, res, ref_flows, orc, crit, sparse, zero_samples=())
 FP32_CHAIN = {}
 
 
-def check_grads(name, what, grads, orc, zero_samples=()):
+def check_grads(name, what, grads, orc, zero_samples=(), samples=None, leaves=None):
     """each vertex gradient against the float64 oracle: 1e-4 relative + 1e-5 x the largest |gradient| of the same sample and leaf.
-    ``zero_samples``: samples whose gradient is all zero in the oracle and has to be, exactly, on the device"""
+    ``zero_samples``: samples whose gradient is all zero in the oracle and has to be, exactly, on the device.  ``samples``: the
+    samples the rule is applied to (None: all; the caller checks the others by a rule of its own).  ``leaves``: the leaves that
+    wanted a gradient (None: all four); the others' entries of ``grads`` have to be None.  Returns the largest error in units
+    of the rule."""
     worst = 0.0
     for got, ref, leaf in zip(grads, orc["grads"], LEAVES):
+        if leaves is not None and leaf not in leaves:
+            assert got is None, f"{what}: d/d {leaf} was not asked for"
+            continue
         if ref.shape[1] == 0:
             assert got is None or got.numel() == 0
             continue
         g = got.detach().double().cpu().numpy()
-        assert g.shape == ref.shape and np.isfinite(g).all(), (what, leaf)
+        assert g.shape == ref.shape, (what, leaf)
+        if samples is not None:
+            g, ref = g[list(samples)], ref[list(samples)]
+            assert not zero_samples
+        assert np.isfinite(g).all(), (what, leaf)
         for b in zero_samples:
             assert not ref[b].any() and not g[b].any(), f"{what}: d/d {leaf} of sample {b} must be exactly zero"
         scale = np.abs(ref).max(axis=(1, 2), keepdims=True)
@@ -277,7 +375,7 @@ def check_grads(name, what, grads, orc, zero_samples=()):
         print(f"{tag(CASES[name])} {what}: d/d {leaf}: {u:.3f} of the rule (largest |gradient| {scale.max():.3e})")
         worst = max(worst, u)
     bound = 1.0
-    if worst > 1.0:
+    if worst > 1.0 and orc["grad_args"] is not None:
         # the same oracle chain with its existing fp32 pieces (R.backward_textures, fp32 sums) against the float64 chain: what an
         # fp32 evaluation in the reference's order is off by under this rule (printed; a case whose bound it sets is in FP32_CHAIN)
         f32 = W.get_opticalflow_vertex_grad(*orc["grad_args"], fp32=True)
@@ -290,6 +388,7 @@ def check_grads(name, what, grads, orc, zero_samples=()):
         if name in FP32_CHAIN:
             bound = FP32_CHAIN[name][1]
     assert worst <= bound, f"{what}: vertex gradients at {worst:.3f} of the rule (bound {bound})"
+    return worst
 
 
 def crit_code(crit):
@@ -298,29 +397,34 @@ def crit_code(crit):
     return {"l1": _lib.CRITERION_L1, "l2": _lib.CRITERION_L2}[crit]
 
 
-def fused_case(cuda, monkeypatch, name, path, crit="l1", zero_samples=()):
+def fused_case(cuda, monkeypatch, name, path, crit="l1", zero_samples=(), upstream=None, grad_zero_samples=(), calls=2):
+    """``upstream``: an Upstream (None: the default weights); ``grad_zero_samples``: samples whose GRADIENT alone is exactly
+    zero (a zero coefficient; ``zero_samples``: the losses too).  Returns the largest gradient error in units of the rule."""
     from handobjectconsist_amd.warping import pairstep
 
     case = CASES[name]
     run = Run(cuda, monkeypatch, name)
+    worst = 0.0
     try:
-        for call, seed in enumerate((case["seed"], case["seed"] + SECOND_SEED)[:2 if path == "step" else 1]):
+        for call, seed in enumerate((case["seed"], case["seed"] + SECOND_SEED)[:calls if path == "step" else 1]):
             what = f"{name} {path} {crit} call {call}"
-            orc = oracle(name, seed, crit)
+            orc = oracle(name, seed, crit, upstream=upstream)
             print(f"{tag(case)} {what}: oracle {orc['seconds']:.1f} s")
             # (the second call: no poison, so that the plan vouches for its list header and the scratch keeps the first seed's values)
-            res, leaves = run.fused(seed, path, crit_code(crit), poison=call == 0)
+            res, leaves = run.fused(seed, path, crit_code(crit), poison=call == 0, with_mean=upstream.with_mean if upstream else "sum")
             assert res is not None, f"{what}: the fused path must take this case"
             lf, lb, flows, lsum, mean = res
-            check_values(name, what, res, oracle_forward(name, seed)["flows"], orc, crit, sparse=True, zero_samples=zero_samples)
-            grads = torch.autograd.grad(run.total(lf, lb, lsum, mean), leaves)
-            check_grads(name, what, grads, orc, zero_samples)
+            check_values(name, what, res, oracle_forward(name, seed)["flows"], orc, crit, sparse=True, zero_samples=zero_samples,
+                         mean_of=upstream.with_mean if upstream else "sum")
+            grads = torch.autograd.grad(run.total(lf, lb, lsum, mean, upstream), leaves)
+            worst = max(worst, check_grads(name, what, grads, orc, tuple(zero_samples) + tuple(grad_zero_samples)))
             if path == "step":
                 assert len(pairstep._PLANS) == 1, "both calls go through one plan"
                 plan = next(iter(pairstep._PLANS.values()))
                 assert bool(plan.st.flags & pairstep.LIST_CLEAN) == (call == 1), "the second call runs on the list header the first one left clean"
     finally:
         run.close()
+    return worst
 
 
 def compact_case(cuda, monkeypatch, name):
