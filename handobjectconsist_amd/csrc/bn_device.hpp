@@ -71,6 +71,12 @@ struct BnAffine {
     const float* var;
     float eps;
 };
+// (value-initialised, then filled: the four bytes behind eps are kernel-argument bytes of every block that holds one)
+static inline BnAffine bn_affine(const float* weight, const float* bias, const float* mean, const float* var, float eps) {
+    BnAffine f{};
+    f.weight = weight; f.bias = bias; f.mean = mean; f.var = var; f.eps = eps;
+    return f;
+}
 // CONTRACT: invstd = 1.0f / sqrtf(var + eps) and a = weight * invstd, exactly these operations; the kernels then form
 // d = x - mean and z = d * a + b.  The finish kernel multiplies by the same invstd expression.
 __device__ __forceinline__ float bn_invstd(const float* var, float eps, int c) { return 1.0f / sqrtf(var[c] + eps); }
@@ -162,6 +168,14 @@ struct BnFinishOut {
     const float* var;   float eps;   float* grad_weight;   float* grad_bias;
     const float* var_d; float eps_d; float* grad_weight_d; float* grad_bias_d;   // K = 3 only
 };
+// (value-initialised, then filled, like bn_affine)
+static inline BnFinishOut bn_finish_out(const float* var, float eps, float* grad_weight, float* grad_bias, const float* var_d = nullptr,
+                                        float eps_d = 0.0f, float* grad_weight_d = nullptr, float* grad_bias_d = nullptr) {
+    BnFinishOut o{};
+    o.var = var; o.eps = eps; o.grad_weight = grad_weight; o.grad_bias = grad_bias;
+    o.var_d = var_d; o.eps_d = eps_d; o.grad_weight_d = grad_weight_d; o.grad_bias_d = grad_bias_d;
+    return o;
+}
 template <int K>
 __global__ __launch_bounds__(256) void bn_finish_kernel(const float* __restrict__ partial, int64_t slots, int C, BnFinishOut o) {
     static_assert(K == 2 || K == 3, "two or three sums per channel");

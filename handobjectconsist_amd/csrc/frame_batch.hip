@@ -312,7 +312,7 @@ extern "C" int mr_frames_to_batch_typed(const uint8_t* frames, const double* coe
     if (!coeffs || !image || !workspace) return MR_ERR_BADARG;
     if (num_frames > 65535 || height > 32767 || width > 32767 || src_height > 32767 || src_width > 32767)
         return MR_ERR_BADARG;
-    FrameBatchParams p;
+    FrameBatchParams p{};
     if (workspace_bytes < batch_work(workspace, num_frames, height, width, p)) return MR_ERR_BADARG;
     if (misaligned({workspace, image, jittermask}, 15)) return MR_ERR_BADARG;
     p.frames = frames; p.coeffs = coeffs; p.flip = flip;

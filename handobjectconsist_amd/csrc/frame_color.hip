@@ -309,7 +309,7 @@ extern "C" int mr_frames_color_augment(const uint8_t* frames_in, uint8_t* frames
     if (num_frames == 0 || src_height == 0 || src_width == 0) return MR_OK;
     if (!frames_in || !frames_out || !blur_radius || !op_codes || !op_values || !workspace) return MR_ERR_BADARG;
     if (misaligned({frames_in, frames_out}, 3) || misaligned({workspace}, 15)) return MR_ERR_BADARG;
-    ColorParams p;
+    ColorParams p{};  // (padding bytes are kernel-argument bytes too)
     if (workspace_bytes < color_work(workspace, num_frames, src_height, src_width, p)) return MR_ERR_BADARG;
     if (num_frames > 65535) return MR_ERR_NOTIMPL;  // a frame is a grid row (gridDim.y)
     std::vector<ColorPlan> plans((size_t)num_frames);

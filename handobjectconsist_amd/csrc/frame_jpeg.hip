@@ -239,7 +239,7 @@ extern "C" int mr_jpeg_reconstruct(const unsigned char* packed, int num_frames, 
     if (!packed || !frames_out || !workspace) return MR_ERR_BADARG;
     if (misaligned({packed, workspace}, 15) || misaligned({frames_out}, 3)) return MR_ERR_BADARG;
     if (workspace_bytes < jpeg_work_bytes(num_frames, g)) return MR_ERR_BADARG;
-    JpegParams p;
+    JpegParams p{};
     p.packed = packed;
     p.planes = static_cast<uint8_t*>(workspace);
     p.out = frames_out;

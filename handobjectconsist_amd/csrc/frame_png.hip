@@ -185,7 +185,7 @@ extern "C" int mr_png_unfilter(const unsigned char* packed, int num_frames, int 
     if (misaligned({packed}, 15) || misaligned({frames_out}, 3)) return MR_ERR_BADARG;
     // a frame's byte offsets are 32-bit and a reconstructed row lives in LDS: 4 * 10752 bytes at most
     if (width > MR_PNG_MAX_SIDE || height > MR_PNG_MAX_SIDE) return MR_ERR_NOTIMPL;
-    PngParams p;
+    PngParams p{};
     p.packed = packed;
     p.out = frames_out;
     p.frame_bytes = mr_png_packed_bytes(width, height, channels);

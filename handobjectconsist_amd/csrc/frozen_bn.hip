@@ -224,7 +224,7 @@ static void bn_launch(const BnParams& p, int act_dtype, int channels_last, bool 
 static BnParams bn_fill(const void* x, const void* residual, const float* weight, const float* bias, const float* mean,
                         const float* var, float eps, int relu, int N, int C, int plane) {
     BnParams p{};
-    p.x = x; p.residual = residual; p.bn = BnAffine{weight, bias, mean, var, eps};
+    p.x = x; p.residual = residual; p.bn = bn_affine(weight, bias, mean, var, eps);
     p.relu = relu; p.N = N; p.C = C; p.HW = plane; p.split = bn_split(N, C);
     return p;
 }
@@ -288,7 +288,7 @@ extern "C" int mr_bn_act_backward(const void* grad_y, const void* grad_y2, const
     bn_launch<true>(p, act_dtype, channels_last, plane % 4 == 0 && all_aligned, (int)slots, (hipStream_t)stream);
     MR_CHECK_LAUNCH();
     if (!want_params) return MR_OK;
-    return launch_bn_finish<2>(p.partial, slots, channels, BnFinishOut{running_var, eps, grad_weight, grad_bias}, (hipStream_t)stream);
+    return launch_bn_finish<2>(p.partial, slots, channels, bn_finish_out(running_var, eps, grad_weight, grad_bias), (hipStream_t)stream);
 }
 
 namespace mr {
@@ -319,8 +319,8 @@ extern "C" int mr_bn_add_bn_act_forward(const void* x, const void* xd, const flo
         !running_var_d || !y)
         return MR_ERR_BADARG;
     if (!aligned4(x, act_dtype) || !aligned4(xd, act_dtype) || !aligned4(y, act_dtype)) return MR_ERR_BADARG;
-    BnAddParams p = bn_add_fill(x, xd, BnAffine{weight, bias, running_mean, running_var, eps},
-                                BnAffine{weight_d, bias_d, running_mean_d, running_var_d, eps_d}, batch_size, channels, plane);
+    BnAddParams p = bn_add_fill(x, xd, bn_affine(weight, bias, running_mean, running_var, eps),
+                                bn_affine(weight_d, bias_d, running_mean_d, running_var_d, eps_d), batch_size, channels, plane);
     p.y = y;
     bn_add_launch<false>(p, act_dtype, nhwc_blocks((int64_t)batch_size * plane, channels, BN_NHWC_BLOCKS), (hipStream_t)stream);
     MR_CHECK_LAUNCH();
@@ -355,8 +355,8 @@ extern "C" int mr_bn_add_bn_act_backward(const void* grad_y, const void* grad_y2
     if (!aligned4(x, act_dtype) || !aligned4(xd, act_dtype) || !aligned4(grad_y, act_dtype) || !aligned4(grad_y2, act_dtype) ||
         !aligned4(grad_x, act_dtype) || !aligned4(grad_xd, act_dtype))
         return MR_ERR_BADARG;
-    BnAddParams p = bn_add_fill(x, xd, BnAffine{weight, bias, running_mean, running_var, eps},
-                                BnAffine{weight_d, bias_d, running_mean_d, running_var_d, eps_d}, batch_size, channels, plane);
+    BnAddParams p = bn_add_fill(x, xd, bn_affine(weight, bias, running_mean, running_var, eps),
+                                bn_affine(weight_d, bias_d, running_mean_d, running_var_d, eps_d), batch_size, channels, plane);
     p.grad_y = grad_y; p.grad_y2 = grad_y2; p.grad_x = grad_x; p.grad_xd = grad_xd;
     p.partial = want_params ? static_cast<float*>(workspace) : nullptr;
     const int64_t slots = bn_add_slots(channels, (int64_t)batch_size * plane);
@@ -364,6 +364,6 @@ extern "C" int mr_bn_add_bn_act_backward(const void* grad_y, const void* grad_y2
     MR_CHECK_LAUNCH();
     if (!want_params) return MR_OK;
     return launch_bn_finish<3>(p.partial, slots, channels,
-                               BnFinishOut{running_var, eps, grad_weight, grad_bias, running_var_d, eps_d, grad_weight_d, grad_bias_d},
+                               bn_finish_out(running_var, eps, grad_weight, grad_bias, running_var_d, eps_d, grad_weight_d, grad_bias_d),
                                (hipStream_t)stream);
 }

@@ -695,8 +695,9 @@ extern "C" int mr_mano_forward_full(const float* pose, const float* betas, const
     if (misaligned({pose, betas, trans, post_trans, post_rot, post_trans2, verts_out, jtr_out}, 3)) return MR_ERR_BADARG;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
-    const ManoFull mf{trans, trans ? 3 * batch_size : 0, mano_work(workspace, batch_size).tflag, out_scale, post_trans,
-                      post_rot, post_trans2};
+    ManoFull mf{};  // (value-initialised, then filled: its padding bytes are kernel-argument bytes)
+    mf.trans = trans; mf.ntrans = trans ? 3 * batch_size : 0; mf.tflag = mano_work(workspace, batch_size).tflag;
+    mf.out_scale = out_scale; mf.post_trans = post_trans; mf.post_rot = post_rot; mf.post_trans2 = post_trans2;
     return mano_launch_forward(mc, mf, pose_form, workspace, pose, betas, verts_out, jtr_out, batch_size,
                                (hipStream_t)stream);
 }
@@ -716,7 +717,8 @@ extern "C" int mr_mano_backward_full(const float* comps, const float* hands_mean
     if (misaligned({grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans}, 3)) return MR_ERR_BADARG;
     const ManoConst mc = mano_const(comps, hands_mean, js, jt, blend, v_template, weights, parents, tips, reorder, ncomps,
                                     center);
-    const ManoFull mf{nullptr, 0, mano_work(workspace, batch_size).tflag, 1.0f, nullptr, nullptr, nullptr};
+    ManoFull mf{};
+    mf.tflag = mano_work(workspace, batch_size).tflag; mf.out_scale = 1.0f;
     return mano_launch_backward(mc, mf, pose_form, workspace, grad_verts, grad_jtr, grad_pose, grad_betas, grad_trans,
                                 batch_size, (hipStream_t)stream);
 }

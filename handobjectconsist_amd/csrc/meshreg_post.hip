@@ -214,6 +214,17 @@ __global__ void __launch_bounds__(64) post_backward_finish_kernel(PostParams p, 
 
 using namespace mr;
 
+// (value-initialised, then filled: the four bytes behind Vo are kernel-argument bytes like any other)
+static PostParams post_params(const float* verts_mm, const float* joints_mm, const float* scaletrans, const float* st_obj, const float* K,
+                              const float* canverts, float trans_factor, float scale_factor, float off_z, float res_w, float res_h, int B,
+                              int Vh, int J, int Vo) {
+    PostParams p{};
+    p.verts_mm = verts_mm; p.joints_mm = joints_mm; p.scaletrans = scaletrans; p.st_obj = st_obj; p.K = K; p.canverts = canverts;
+    p.trans_factor = trans_factor; p.scale_factor = scale_factor; p.off_z = off_z; p.res_w = res_w; p.res_h = res_h;
+    p.B = B; p.Vh = Vh; p.J = J; p.Vo = Vo;
+    return p;
+}
+
 static int post_check(const PostParams& p) {
     if (p.B < 0 || p.Vh < 0 || p.J < 0 || p.Vo < 0) return MR_ERR_BADARG;
     if (p.B > 65535) return MR_ERR_BADARG;
@@ -229,8 +240,8 @@ extern "C" int mr_meshreg_post_forward(const float* verts_mm, const float* joint
                                        float* joints3d, float* joints2d, float* objverts3d, float* objverts2d,
                                        int batch_size, int num_hand_verts, int num_joints, int num_obj_verts,
                                        mr_stream_t stream) {
-    PostParams p{verts_mm, joints_mm, scaletrans, st_obj, K, canverts, trans_factor, scale_factor, off_z, res_w, res_h,
-                 batch_size, num_hand_verts, num_joints, num_obj_verts};
+    const PostParams p = post_params(verts_mm, joints_mm, scaletrans, st_obj, K, canverts, trans_factor, scale_factor, off_z, res_w, res_h,
+                                     batch_size, num_hand_verts, num_joints, num_obj_verts);
     const int rc = post_check(p);
     if (rc != MR_OK || batch_size == 0) return rc;
     if ((num_hand_verts > 0 && !handverts3d) || (num_joints > 0 && (!joints3d || !joints2d)) ||
@@ -253,8 +264,8 @@ extern "C" int mr_meshreg_post_backward(const float* verts_mm, const float* join
                                         float* grad_joints_mm, float* grad_scaletrans, float* grad_st_obj,
                                         int batch_size, int num_hand_verts, int num_joints, int num_obj_verts,
                                         mr_stream_t stream) {
-    PostParams p{verts_mm, joints_mm, scaletrans, st_obj, K, canverts, trans_factor, scale_factor, off_z, res_w, res_h,
-                 batch_size, num_hand_verts, num_joints, num_obj_verts};
+    const PostParams p = post_params(verts_mm, joints_mm, scaletrans, st_obj, K, canverts, trans_factor, scale_factor, off_z, res_w, res_h,
+                                     batch_size, num_hand_verts, num_joints, num_obj_verts);
     const int rc = post_check(p);
     if (rc != MR_OK || batch_size == 0) return rc;
     if (!workspace || !grad_scaletrans || !grad_st_obj || (num_hand_verts > 0 && !grad_verts_mm) ||

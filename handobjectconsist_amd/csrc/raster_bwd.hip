@@ -2273,6 +2273,7 @@ static int launch_pixel_map(const PixelMapPlan& plan, const PixelMapParams& p, v
                        plan.shape.strips, cap);
     MR_CHECK_LAUNCH();
     if (plan.status_grid != MR_OK) return plan.status_grid;
+    if constexpr (IMG) {  // (only mr_render_backward has a gather to fuse: no raster-orientation instantiations)
     if (plan.fused) {
         auto fused_kernel = strip_l == 4 ? strip_gather_for<IMG, 4>(plan.gather)
                                          : (strip_l == 2 ? strip_gather_for<IMG, 2>(plan.gather) : strip_gather_for<IMG, 1>(plan.gather));
@@ -2281,6 +2282,7 @@ static int launch_pixel_map(const PixelMapPlan& plan, const PixelMapParams& p, v
                            plan.gather_groups);
         MR_CHECK_LAUNCH();
         return MR_OK;
+    }
     }
     auto kernel = strip_l == 4 ? pixel_map_strip_kernel<IMG, 4> : (strip_l == 2 ? pixel_map_strip_kernel<IMG, 2> : pixel_map_strip_kernel<IMG, 1>);
     hipLaunchKernelGGL(kernel, dim3(plan.wgs), dim3(PS_T), plan.lds, s, p, (const unsigned*)ol0.img_count,

@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256) void stem_pool_rec_sums_kernel(StemParams p) {
 static int stem_fill(StemParams& p, const void* x, const float* weight, const float* bias, const float* mean,
                      const float* var, float eps, int N, int C, int H, int W) {
     if (N < 0 || C < 0 || H < 0 || W < 0) return MR_ERR_BADARG;
-    p.x = x; p.bn = BnAffine{weight, bias, mean, var, eps};
+    p.x = x; p.bn = bn_affine(weight, bias, mean, var, eps);
     p.N = N; p.C = C; p.H = H; p.W = W;
     p.OH = H > 0 ? (H - 1) / 2 + 1 : 0;
     p.OW = W > 0 ? (W - 1) / 2 + 1 : 0;
@@ -572,7 +572,7 @@ extern "C" int mr_stem_pool_backward(const void* grad_y, const void* grad_y2, co
     stem_launch<true>(p, act_dtype, layout, layout ? slots : slots * channels, (hipStream_t)stream);
     MR_CHECK_LAUNCH();
     if (!want_params) return MR_OK;
-    return launch_bn_finish<2>(p.partial, slots, channels, BnFinishOut{running_var, eps, grad_weight, grad_bias}, (hipStream_t)stream);
+    return launch_bn_finish<2>(p.partial, slots, channels, bn_finish_out(running_var, eps, grad_weight, grad_bias), (hipStream_t)stream);
 }
 
 // grad_weight / grad_bias of the layout-2 backward alone (stem_pool_rec_sums_kernel): no x, no grad_x.  Workspace as for
@@ -604,5 +604,5 @@ extern "C" int mr_stem_pool_param_grads(const void* grad_y, const void* grad_y2,
         hipLaunchKernelGGL(stem_pool_rec_sums_kernel<T>, grid, block, 0, (hipStream_t)stream, p);
     });
     MR_CHECK_LAUNCH();
-    return launch_bn_finish<2>(p.partial, slots, channels, BnFinishOut{running_var, eps, grad_weight, grad_bias}, (hipStream_t)stream);
+    return launch_bn_finish<2>(p.partial, slots, channels, bn_finish_out(running_var, eps, grad_weight, grad_bias), (hipStream_t)stream);
 }

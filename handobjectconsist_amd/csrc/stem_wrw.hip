@@ -314,7 +314,7 @@ extern "C" int mr_stem_conv_wrw(const float* grad_y, const float* grad_y2, const
     p.grad_y = grad_y; p.grad_y2 = grad_y2;
     p.rec_d = reinterpret_cast<const float*>(records);
     p.rec_code = records + (int64_t)p.N * p.OH * p.OW * SW_C * 4;
-    p.bn = BnAffine{weight, bias, running_mean, running_var, eps};
+    p.bn = bn_affine(weight, bias, running_mean, running_var, eps);
     p.image = image;
     p.partial = static_cast<float*>(workspace);
     hipLaunchKernelGGL(stem_conv_wrw_kernel, dim3(SW_BLOCKS), dim3(256), 0, s, p);

@@ -22,6 +22,10 @@ runner from this file.  (Recorded that way since: the pair step's "bwd-only" cas
 one incoming gradient -- `R -1` before launch_unit_scatter_tiles accepted it, the scatter and the vertex launch after; no other
 line moved.)
 
+The driver links the other nine sources too (UNRECORDED_SOURCES), for its cases that are run and not recorded
+(``--unrecorded``; with ``--stream HEX`` every case hands that stream over and the recorder reports calls on any other:
+tests/test_stream_record_host.py).  Neither option changes a line of the recorded table.
+
 The sizes of a kernel's explicit arguments come from the code-object metadata (``.args``) of the device assembly
 (``--cuda-device-only -S``); objects and argument tables are cached under tests/host/build/, one per source, keyed on the
 source's content hash the way build.py keys the library's objects.
@@ -43,7 +47,12 @@ PATH = os.path.join(HERE, "launch_sequences.json")
 HOST = os.path.join(ROOT, "tests", "host")
 CACHE = os.path.join(HOST, "build")  # git-ignored
 SOURCES = ["raster_fwd.hip", "raster_bwd.hip", "warp.hip", "pair_step.hip", "vertex_stage.hip"]
+# linked as well, host-only like the five, for the cases that are run but not recorded (launch_record --unrecorded: every
+# entry point on the caller's stream, tests/test_stream_record_host.py); their launch geometry is in no golden file
+UNRECORDED_SOURCES = ["mano_lbs.hip", "meshreg_post.hip", "frozen_bn.hip", "stem_pool.hip", "stem_wrw.hip", "frame_batch.hip",
+                      "frame_color.hip", "frame_jpeg.hip", "frame_png.hip"]
 RUNS = {"cus256": ["--cus", "256"], "cus64": ["--cus", "64"]}
+SOURCE_TABLES = {}  # source -> its kernel argument table, filled by build_driver
 
 
 def _host_compiler():
@@ -90,13 +99,14 @@ def build_driver(verbose=False):
             hh.update(fh.read())
     procs, objs, tables = [], [], []
     tmp = ".%d.tmp" % os.getpid()  # (written under a name of this process, then renamed: concurrent builders do not collide)
-    for src in SOURCES:
+    for src in SOURCES + UNRECORDED_SOURCES:
         with open(os.path.join(build.CSRC, src), "rb") as fh:
             key = hashlib.sha256(" ".join(build.COMPILE_FLAGS).encode() + hh.digest() + fh.read()).hexdigest()[:16]
         stem = os.path.join(CACHE, "%s.%s" % (os.path.splitext(src)[0], key))
         obj, table, asm = stem + ".host.o", stem + ".args.txt", stem + ".s"
         objs.append(obj)
         tables.append(table)
+        SOURCE_TABLES[src] = table
         for target, extra in ((obj, ["--cuda-host-only", "-c"]), (table, ["--cuda-device-only", "-S"])):
             if os.path.exists(target):
                 continue

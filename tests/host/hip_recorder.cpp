@@ -8,6 +8,19 @@
 //   A <bytes> / F <base>                       hipMallocAsync / hipFreeAsync
 //   S <kernel> <attribute> <value> d<device>   hipFuncSetAttribute
 //
+// The stream of the four stream-ordered calls is kept as well.  Once the driver has named the stream it hands to the entry
+// points (rec_expect_stream), a call on any OTHER stream -- a launch or memset that would race on a side stream and be
+// missing from a captured graph -- gets one more line in front of its usual one:
+//
+//   X <L|M|A|F> <kernel, or base+offset, or base> <stream>
+//
+// and rec_report_unlaunched prints, for every function the objects registered that was never launched,
+//
+//   U <kernel>
+//
+// Without an expectation there are no X lines, and U lines come only on request: the L, M, A, F and S lines are the same
+// either way.
+//
 // The bytes of an argument come from the code-object metadata of the device assembly (kernel -> sizes of the explicit
 // arguments, a table the build hands over through rec_load_args); hidden arguments are not looked at.
 #include <cstdint>
@@ -22,7 +35,7 @@
 namespace {
 
 struct Dim3 { unsigned x, y, z; };
-struct Kernel { std::string name; std::vector<int> sizes; bool known = false; };
+struct Kernel { std::string name; std::vector<int> sizes; bool known = false, launched = false; };
 
 // (the registration constructors of the objects run before this file's statics would be built: function-local)
 std::map<const void*, Kernel>& kernels() { static std::map<const void*, Kernel> m; return m; }
@@ -33,6 +46,8 @@ std::vector<Config>& configs() { static std::vector<Config> v; return v; }
 
 int g_device = 0, g_cus = 256, g_devices = 1;
 uint64_t g_next_alloc = 0x7f0;
+bool g_expecting = false;
+void* g_expected = nullptr;
 
 std::string short_name(const char* mangled) {
     int status = 0;
@@ -79,6 +94,10 @@ void region(uintptr_t p, char* out, size_t n) {
     std::snprintf(out, n, "%llx+%llu", (unsigned long long)(p >> 40), (unsigned long long)(p & ((1ULL << 40) - 1)));
 }
 
+void on_stream(char kind, const char* what, void* stream) {
+    if (g_expecting && stream != g_expected) std::printf("X %c %s %p\n", kind, what, stream);
+}
+
 }  // namespace
 
 // ---- what the driver sets ------------------------------------------------------------------------------------------
@@ -98,6 +117,15 @@ extern "C" void rec_load_args(const char* path) {
 extern "C" void rec_set_device(int device, int devices) { g_device = device; g_devices = devices; }
 extern "C" void rec_set_cus(int cus) { g_cus = cus; }
 extern "C" void rec_begin(void) { g_next_alloc = 0x7f0; configs().clear(); }
+extern "C" void rec_expect_stream(void* stream) { g_expecting = true; g_expected = stream; }
+extern "C" void rec_report_unlaunched(void) {
+    for (auto& kv : kernels())
+        if (!kv.second.launched) std::printf("U %s\n", kv.second.known ? kv.second.name.c_str() : short_name(kv.second.name.c_str()).c_str());
+}
+// "K <mangled name> <name as the L lines show it>" for every kernel of the argument table: which source a name belongs to
+extern "C" void rec_print_kernel_names(void) {
+    for (auto& kv : arg_sizes()) std::printf("K %s %s\n", kv.first.c_str(), short_name(kv.first.c_str()).c_str());
+}
 
 // ---- the runtime's entry points ------------------------------------------------------------------------------------
 extern "C" {
@@ -122,8 +150,10 @@ int __hipPopCallConfiguration(Dim3* grid, Dim3* block, size_t* lds, void** strea
     return 0;
 }
 
-int hipLaunchKernel(const void* f, Dim3 grid, Dim3 block, void** args, size_t lds, void*) {
-    const Kernel& k = kernel_of(f);
+int hipLaunchKernel(const void* f, Dim3 grid, Dim3 block, void** args, size_t lds, void* stream) {
+    Kernel& k = kernel_of(f);
+    k.launched = true;
+    on_stream('L', k.name.c_str(), stream);
     uint64_t h = 0xcbf29ce484222325ULL;  // FNV-1a over the explicit arguments, in order
     for (size_t i = 0; i < k.sizes.size(); i++) {
         const unsigned char* b = static_cast<const unsigned char*>(args[i]);
@@ -134,19 +164,26 @@ int hipLaunchKernel(const void* f, Dim3 grid, Dim3 block, void** args, size_t ld
     return 0;
 }
 
-int hipMemsetAsync(void* p, int value, size_t bytes, void*) {
+int hipMemsetAsync(void* p, int value, size_t bytes, void* stream) {
     char r[64];
     region(reinterpret_cast<uintptr_t>(p), r, sizeof r);
+    on_stream('M', r, stream);
     std::printf("M %s %d %zu\n", r, value, bytes);
     return 0;
 }
 
-int hipMallocAsync(void** p, size_t bytes, void*) {
+int hipMallocAsync(void** p, size_t bytes, void* stream) {
+    char r[32];
+    std::snprintf(r, sizeof r, "%llx", (unsigned long long)g_next_alloc);
+    on_stream('A', r, stream);
     *p = reinterpret_cast<void*>(static_cast<uintptr_t>(g_next_alloc++) << 40);
     std::printf("A %zu\n", bytes);
     return 0;
 }
-int hipFreeAsync(void* p, void*) {
+int hipFreeAsync(void* p, void* stream) {
+    char r[32];
+    std::snprintf(r, sizeof r, "%llx", (unsigned long long)(reinterpret_cast<uintptr_t>(p) >> 40));
+    on_stream('F', r, stream);
     std::printf("F %llx\n", (unsigned long long)(reinterpret_cast<uintptr_t>(p) >> 40));
     return 0;
 }

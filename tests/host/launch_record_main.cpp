@@ -1,7 +1,12 @@
 // launch_record_main.cpp -- calls the raster and warp entry points over a table of cases on top of tests/host/hip_recorder.cpp
 // and prints, case by case, what each asked of the runtime: a device-free record of every launcher's decisions.
 //
-//   launch_record <kernel argument table> [--cus N] [--stack-fill BYTE] [--two-devices]
+//   launch_record <kernel argument table> [--cus N] [--stack-fill BYTE] [--two-devices] [--stream HEX] [--unrecorded]
+//
+// --stream: the value every case passes as its mr_stream_t (NULL without it), announced to the recorder, which then reports
+// every call on another stream; nothing else of the output changes.  --unrecorded: the recorded table in full, then the
+// cases no golden file holds (every other entry point of all fourteen sources), a self-test of the stream check, and the
+// kernels no case launched.  --kernel-names: the table's kernels under the names the L lines show.
 //
 // Pointers are made up (argument k of a call sits at k << 40, nothing is ever dereferenced), so the argument hashes are
 // the same from run to run.  tests/golden/make_golden_launch_sequences.py builds and runs this; the cases are named by their
@@ -22,9 +27,15 @@ void rec_load_args(const char* path);
 void rec_set_device(int device, int devices);
 void rec_set_cus(int cus);
 void rec_begin(void);
+void rec_expect_stream(void* stream);
+void rec_report_unlaunched(void);
+void rec_print_kernel_names(void);
 }
 
 namespace {
+
+// The stream every case hands to the entry point it calls: NULL as recorded, or the value of --stream (never dereferenced).
+mr_stream_t g_stream = nullptr;
 
 template <typename T = float>
 T* P(int k) { return reinterpret_cast<T*>(static_cast<uintptr_t>(k) << 40); }
@@ -77,12 +88,12 @@ struct Fwd {
 int render_forward(const Fwd& c) {
     const int64_t ws = mr_render_workspace_bytes(c.B, c.F0, c.is) - c.ws_short;
     return mr_render_forward(P(1), P(2), P(3), c.bg_stride, P(4), P(5), P(6), P<int32_t>(7), P(8), c.inv_map ? P(9) : nullptr, P<void>(10), ws,
-                             c.B, c.F0, c.is, c.ts, NEAR, FAR, c.eps, 1, 1, 1, c.flags, nullptr);
+                             c.B, c.F0, c.is, c.ts, NEAR, FAR, c.eps, 1, 1, 1, c.flags, g_stream);
 }
 int render_vc_forward(const Fwd& c) {
     const int64_t ws = mr_render_workspace_bytes(c.B, c.fill ? 2 * c.F0 : c.F0, c.is) - c.ws_short;
     return mr_render_vc_forward(P(1), P<int32_t>(2), P(3), P(4), c.bg_stride, P(5), P(6), P(7), P<int32_t>(8), P(9), P<void>(10), ws, c.B, c.V,
-                                c.F0, c.fill, c.is, NEAR, FAR, c.eps, 1, 1, 1, c.flags, c.texel, nullptr);
+                                c.F0, c.fill, c.is, NEAR, FAR, c.eps, 1, 1, 1, c.flags, c.texel, g_stream);
 }
 int render_flow_forward(const Fwd& c) {
     const int64_t ws = mr_render_workspace_bytes(c.B, c.fill ? 2 * c.F0 : c.F0, c.is) - c.ws_short;
@@ -90,7 +101,7 @@ int render_flow_forward(const Fwd& c) {
     return mr_render_flow_forward(P(1), P<int32_t>(2), P(3), P(4), c.bg_stride, c.lut ? P(5) : nullptr, c.lut ? 4 : 0, 0.5f, P(6), P(7), P(8),
                                   P(9), P(10), P<int32_t>(11), hit ? P<uint8_t>(12) : nullptr, P<void>(13), ws, c.B, c.V, c.F0, c.fill, c.is,
                                   NEAR, FAR, c.eps, c.flags, c.vid ? P<int32_t>(14) : nullptr, c.tile_bound, P<uint32_t>(15),
-                                  c.zero_fill ? P(16) : nullptr, c.zero_fill ? (int64_t)c.B * c.V * 3 : 0, c.texel, nullptr);
+                                  c.zero_fill ? P(16) : nullptr, c.zero_fill ? (int64_t)c.B * c.V * 3 : 0, c.texel, g_stream);
 }
 
 void fwd_case(const char* which, const Fwd& c) {
@@ -195,31 +206,31 @@ void forward_refusals() {
     begin("flow refused: sparse tiles without coverage bytes");
     end(mr_render_flow_forward(P(1), P<int32_t>(2), P(3), P(4), 3, nullptr, 0, 0.5f, P(6), P(7), P(8), P(9), P(10), P<int32_t>(11), nullptr,
                                P<void>(13), mr_render_workspace_bytes(2, 3076, 256), 2, 2000, 1538, 1, 256, NEAR, FAR, EPS,
-                               MR_FLAG_SPARSE_TILES, nullptr, -1, nullptr, nullptr, 0, MR_TEXEL_LAYOUT_DEFAULT, nullptr));
+                               MR_FLAG_SPARSE_TILES, nullptr, -1, nullptr, nullptr, 0, MR_TEXEL_LAYOUT_DEFAULT, g_stream));
     begin("flow refused: vertex ids without weights");
     end(mr_render_flow_forward(P(1), P<int32_t>(2), P(3), P(4), 3, nullptr, 0, 0.5f, P(6), P(7), P(8), P(9), nullptr, P<int32_t>(11), nullptr,
                                P<void>(13), mr_render_workspace_bytes(2, 3076, 256), 2, 2000, 1538, 1, 256, NEAR, FAR, EPS, 0,
-                               P<int32_t>(14), 0, nullptr, nullptr, 0, MR_TEXEL_LAYOUT_DEFAULT, nullptr));
+                               P<int32_t>(14), 0, nullptr, nullptr, 0, MR_TEXEL_LAYOUT_DEFAULT, g_stream));
     begin("flow refused: lookup table without entries");
     end(mr_render_flow_forward(P(1), P<int32_t>(2), P(3), P(4), 3, P(5), 0, 0.5f, P(6), P(7), P(8), P(9), P(10), P<int32_t>(11), nullptr,
                                P<void>(13), mr_render_workspace_bytes(2, 3076, 256), 2, 2000, 1538, 1, 256, NEAR, FAR, EPS, 0, nullptr, 0,
-                               nullptr, nullptr, 0, MR_TEXEL_LAYOUT_DEFAULT, nullptr));
+                               nullptr, nullptr, 0, MR_TEXEL_LAYOUT_DEFAULT, g_stream));
     begin("flow refused: zero fill without a buffer");
     end(mr_render_flow_forward(P(1), P<int32_t>(2), P(3), P(4), 3, nullptr, 0, 0.5f, P(6), P(7), P(8), P(9), P(10), P<int32_t>(11), nullptr,
                                P<void>(13), mr_render_workspace_bytes(2, 3076, 256), 2, 2000, 1538, 1, 256, NEAR, FAR, EPS, 0, nullptr, 0,
-                               nullptr, nullptr, 5, MR_TEXEL_LAYOUT_DEFAULT, nullptr));
+                               nullptr, nullptr, 5, MR_TEXEL_LAYOUT_DEFAULT, g_stream));
     begin("render refused: no face index map");
     end(mr_render_forward(P(1), P(2), P(3), 3, P(4), P(5), P(6), nullptr, P(8), nullptr, P<void>(10), mr_render_workspace_bytes(2, 10, 36), 2, 10,
-                          36, 2, NEAR, FAR, EPS, 1, 1, 1, 0, nullptr));
+                          36, 2, NEAR, FAR, EPS, 1, 1, 1, 0, g_stream));
     begin("render refused: alpha without an image");
     end(mr_render_forward(P(1), P(2), P(3), 3, P(4), nullptr, P(6), P<int32_t>(7), P(8), nullptr, P<void>(10),
-                          mr_render_workspace_bytes(2, 10, 36), 2, 10, 36, 2, NEAR, FAR, EPS, 1, 1, 1, 0, nullptr));
+                          mr_render_workspace_bytes(2, 10, 36), 2, 10, 36, 2, NEAR, FAR, EPS, 1, 1, 1, 0, g_stream));
     begin("vc refused: depth without an image");
     end(mr_render_vc_forward(P(1), P<int32_t>(2), P(3), P(4), 3, P(5), P(6), nullptr, P<int32_t>(8), P(9), P<void>(10),
-                             mr_render_workspace_bytes(2, 20, 36), 2, 30, 10, 1, 36, NEAR, FAR, EPS, 1, 1, 1, 0, MR_TEXEL_LAYOUT_DEFAULT, nullptr));
+                             mr_render_workspace_bytes(2, 20, 36), 2, 30, 10, 1, 36, NEAR, FAR, EPS, 1, 1, 1, 0, MR_TEXEL_LAYOUT_DEFAULT, g_stream));
     begin("vc refused: no vertices");
     end(mr_render_vc_forward(nullptr, P<int32_t>(2), P(3), P(4), 3, P(5), P(6), P(7), P<int32_t>(8), P(9), P<void>(10),
-                             mr_render_workspace_bytes(2, 20, 36), 2, 30, 10, 1, 36, NEAR, FAR, EPS, 1, 1, 1, 0, MR_TEXEL_LAYOUT_DEFAULT, nullptr));
+                             mr_render_workspace_bytes(2, 20, 36), 2, 30, 10, 1, 36, NEAR, FAR, EPS, 1, 1, 1, 0, MR_TEXEL_LAYOUT_DEFAULT, g_stream));
 }
 
 // ---- the pair step ---------------------------------------------------------------------------------------------------
@@ -252,10 +263,10 @@ void pair_step_cases(bool all) {
     auto both = [&](const char* what, MrPairStep s) {
         begin("pair_step_forward %s B%d V%d+%d F%d+%d is%d fl%x crit%d dt%x tb%lld", what, s.batch_size, s.num_verts_a, s.num_verts_b,
               s.num_hand_faces, s.num_obj_faces, s.image_size, (unsigned)s.flags, s.criterion, (unsigned)s.reserved, (long long)s.tile_bound);
-        end(mr_pair_step_forward(&s, nullptr));
+        end(mr_pair_step_forward(&s, g_stream));
         begin("pair_step_backward %s B%d V%d+%d F%d+%d is%d fl%x crit%d dt%x", what, s.batch_size, s.num_verts_a, s.num_verts_b, s.num_hand_faces,
               s.num_obj_faces, s.image_size, (unsigned)s.flags, s.criterion, (unsigned)s.reserved);
-        end(mr_pair_step_backward(&s, nullptr));
+        end(mr_pair_step_backward(&s, g_stream));
     };
     for (const Mesh& m : meshes)
         for (int B : {0, 1, 8, 32, 64})
@@ -290,9 +301,9 @@ void pair_step_cases(bool all) {
     both("vertices-2778", pair_step(8, 778, 2000, 1538, 2000, 256, 0, 0, 0));
     both("batch--1", pair_step(-1, 778, 1000, 1538, 2000, 256, 0, 0, 0));
     begin("pair_step_forward refused: null block");
-    end(mr_pair_step_forward(nullptr, nullptr));
+    end(mr_pair_step_forward(nullptr, g_stream));
     begin("pair_step_backward refused: null block");
-    end(mr_pair_step_backward(nullptr, nullptr));
+    end(mr_pair_step_backward(nullptr, g_stream));
 }
 
 // ---- the generic backward ---------------------------------------------------------------------------------------------
@@ -305,7 +316,7 @@ struct Bwd {
 int render_backward(const Bwd& c) {
     const int64_t ws = c.ws == 2 ? mr_render_backward_workspace_bytes(c.B, c.F, c.is) : c.ws == 1 ? mr_render_backward_list_workspace_bytes(c.B, c.F) : 0;
     return mr_render_backward(P(1), P(2), P<int32_t>(3), P(4), P(5), P(6), P(7), P(8), c.grad_faces ? P(9) : nullptr, c.tex ? P(10) : nullptr,
-                              c.ws ? P<void>(11) : nullptr, ws, c.B, c.F, c.is, c.ts, NEAR, FAR, c.eps, c.rr, c.ra, c.rd, c.flags, nullptr);
+                              c.ws ? P<void>(11) : nullptr, ws, c.B, c.F, c.is, c.ts, NEAR, FAR, c.eps, c.rr, c.ra, c.rd, c.flags, g_stream);
 }
 void bwd_case(const Bwd& c) {
     begin("render_backward B%d F%d is%d ts%d rgb%d a%d d%d tex%d gf%d ws%d fl%x eps%g", c.B, c.F, c.is, c.ts, c.rr, c.ra, c.rd, (int)c.tex,
@@ -348,27 +359,27 @@ void backward_cases() {
     { Bwd c; c.is = 0; bwd_case(c); }
     { Bwd c; c.ts = 1; bwd_case(c); }
     begin("render_backward refused: no faces");
-    end(mr_render_backward(nullptr, P(2), P<int32_t>(3), P(4), P(5), P(6), P(7), P(8), P(9), P(10), nullptr, 0, 2, 10, 36, 2, NEAR, FAR, EPS, 1, 1, 1, 0, nullptr));
+    end(mr_render_backward(nullptr, P(2), P<int32_t>(3), P(4), P(5), P(6), P(7), P(8), P(9), P(10), nullptr, 0, 2, 10, 36, 2, NEAR, FAR, EPS, 1, 1, 1, 0, g_stream));
 
     for (int rr = 0; rr < 2; rr++)
         for (int ra = 0; ra < 2; ra++)
             for (int is : {1, 2, 36, 256, 480, 8192}) {
                 begin("backward_pixel_map B2 F1538 is%d rgb%d a%d", is, rr, ra);
-                end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), 2, 1538, is, EPS, rr, ra, nullptr));
+                end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), 2, 1538, is, EPS, rr, ra, g_stream));
             }
     for (int B : {0, 16})
         for (int F : {0, 7104}) {
             begin("backward_pixel_map B%d F%d is256 rgb1 a1", B, F);
-            end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), B, F, 256, EPS, 1, 1, nullptr));
+            end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), B, F, 256, EPS, 1, 1, g_stream));
         }
     begin("backward_pixel_map refused: no gradient array");
-    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), nullptr, 2, 10, 36, EPS, 1, 1, nullptr));
+    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), nullptr, 2, 10, 36, EPS, 1, 1, g_stream));
     begin("backward_pixel_map refused: rgb without its maps");
-    end(mr_backward_pixel_map(P(1), P<int32_t>(2), nullptr, P(4), P(5), P(6), P(7), 2, 10, 36, EPS, 1, 1, nullptr));
+    end(mr_backward_pixel_map(P(1), P<int32_t>(2), nullptr, P(4), P(5), P(6), P(7), 2, 10, 36, EPS, 1, 1, g_stream));
     begin("backward_pixel_map refused: alpha without its maps");
-    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), nullptr, P(7), 2, 10, 36, EPS, 1, 1, nullptr));
+    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), nullptr, P(7), 2, 10, 36, EPS, 1, 1, g_stream));
     begin("backward_pixel_map refused: raster 0");
-    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), 2, 10, 0, EPS, 1, 1, nullptr));
+    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), 2, 10, 0, EPS, 1, 1, g_stream));
 }
 
 // ---- the vertex-colour and tile-scatter backwards ----------------------------------------------------------------------
@@ -377,7 +388,7 @@ void vc_backward_cases() {
         begin("render_vc_backward B%d V%d F%d is%d fl%x stored%d eps%g tx%x out%d", B, V, F0, is, (unsigned)flags, (int)stored, (double)eps,
               (unsigned)texel, (int)out);
         end(mr_render_vc_backward(P(1), P<int32_t>(2), P<int32_t>(3), stored ? P(4) : nullptr, stored ? P(5) : nullptr, P(6), out ? P(7) : nullptr, B,
-                                  V, F0, 1, is, eps, flags, texel, nullptr));
+                                  V, F0, 1, is, eps, flags, texel, g_stream));
     };
     const int T = MR_TEXEL_LAYOUT_DEFAULT;
     for (int V : {0, 1, 2000, 2560, 2561, 5000})  // (2560 vertices: the last table inside the LDS limit)
@@ -408,7 +419,7 @@ void scatter_cases() {
         const int H = c.H ? c.H : c.is, W = c.W ? c.W : c.is;
         end(mr_render_flow_backward(c.ok ? P(1) : nullptr, P<int32_t>(2), P<int32_t>(3), P<uint32_t>(4), P(5), c.ok ? P(6) : nullptr,
                                     c.flowgrad ? nullptr : P(7), P(8), P(9), P(10), P(11), c.B / 2, P(12), H, W, P(13), c.B, c.V, c.F0, 1, c.is, c.eps,
-                                    c.flags, c.vid ? P<int32_t>(14) : nullptr, c.texel, P(15), nullptr));
+                                    c.flags, c.vid ? P<int32_t>(14) : nullptr, c.texel, P(15), g_stream));
     };
     auto pair_tiles = [&](S c, bool crit_entry) {
         name(crit_entry ? "flow_pair_backward_tiles_crit" : "flow_pair_backward_tiles", c);
@@ -416,18 +427,18 @@ void scatter_cases() {
         if (crit_entry)
             end(mr_flow_pair_backward_tiles_crit(P<int32_t>(1), P<uint32_t>(2), P(3), c.vid ? P<int32_t>(4) : nullptr, c.ok ? P(5) : nullptr, P(6), P(7),
                                                  P(8), P(9), 3, P(10), P(11), P(12), P(13), P(14), P(15), P(16), P(17), H, W, P(18), c.B, c.V, c.F0, 1,
-                                                 c.is, c.eps, 0.5f, c.flags, c.texel, nullptr, c.crit));
+                                                 c.is, c.eps, 0.5f, c.flags, c.texel, g_stream, c.crit));
         else
             end(mr_flow_pair_backward_tiles(P<int32_t>(1), P<uint32_t>(2), P(3), c.vid ? P<int32_t>(4) : nullptr, c.ok ? P(5) : nullptr, P(6), P(7), P(8),
                                             P(9), 3, P(10), P(11), P(12), P(13), P(14), P(15), P(16), P(17), H, W, P(18), c.B, c.V, c.F0, 1, c.is,
-                                            c.eps, 0.5f, c.flags, c.texel, nullptr));
+                                            c.eps, 0.5f, c.flags, c.texel, g_stream));
     };
     auto unit_tiles = [&](S c) {
         name("flow_pair_backward_unit_tiles", c);
         const int H = c.H ? c.H : c.is, W = c.W ? c.W : c.is;
         end(mr_flow_pair_backward_unit_tiles(P<int32_t>(1), P<uint32_t>(2), P(3), c.vid ? P<int32_t>(4) : nullptr, c.ok ? P(5) : nullptr, P(6), P(7),
                                              P(8), P(9), H, W, P(10), c.B, c.V, c.F0, 1, c.is, c.eps, c.flags, c.texel,
-                                             c.work ? P<void>(11) : nullptr, nullptr));
+                                             c.work ? P<void>(11) : nullptr, g_stream));
     };
     for (int is : {256, 480, 640})
         for (int vid = 0; vid < 2; vid++)
@@ -463,10 +474,10 @@ void scatter_cases() {
     { S c; c.crit = 2; pair_tiles(c, true); }
     begin("flow_pair_backward_unit_tiles refused: no loss gradient");
     end(mr_flow_pair_backward_unit_tiles(P<int32_t>(1), P<uint32_t>(2), P(3), P<int32_t>(4), P(5), P(6), P(7), nullptr, P(9), 256, 256, P(10), 4, 2000,
-                                         1538, 1, 256, EPS, 0, T, nullptr, nullptr));
+                                         1538, 1, 256, EPS, 0, T, nullptr, g_stream));
     begin("render_flow_backward refused: no output");
     end(mr_render_flow_backward(P(1), P<int32_t>(2), P<int32_t>(3), P<uint32_t>(4), P(5), P(6), nullptr, P(8), P(9), P(10), P(11), 2, P(12), 256, 256,
-                                nullptr, 4, 2000, 1538, 1, 256, EPS, 0, P<int32_t>(14), T, P(15), nullptr));
+                                nullptr, 4, 2000, 1538, 1, 256, EPS, 0, P<int32_t>(14), T, P(15), g_stream));
 }
 
 // ---- the warp half: listed forward launches, occlusion, pair loss ---------------------------------------------------------
@@ -493,13 +504,13 @@ void pair_forward_cases() {
 #define FWD_HEAD P(1), P(2), f12, P(4), bs, P(5), P(6), P(7), P(8), P(9), P(10), P<uint8_t>(11), P<uint8_t>(12)
 #define FWD_TAIL c.Cj, P<void>(17), ws, P(18), P(19), P(20), c.B, c.is, H, W, 0.05f, 1.0f, 0.5f, P<void>(21), P<void>(22), cap, c.tile_bound
         switch (which) {
-        case 0: end(mr_flow_pair_forward_tiles(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, nullptr)); break;
-        case 1: end(mr_flow_pair_forward_tiles_crit(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, nullptr, c.crit)); break;
-        case 2: end(mr_flow_pair_forward_tiles_typed(FWD_HEAD, P<void>(13), P<void>(14), P<void>(15), P<void>(16), FWD_TAIL, nullptr, c.crit, c.idt, c.mdt)); break;
-        case 3: end(mr_flow_pair_forward_grad_tiles(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, P(23), P(24), P(25), P<void>(26), nullptr)); break;
-        case 4: end(mr_flow_pair_forward_grad_tiles_crit(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, P(23), P(24), P(25), P<void>(26), nullptr, c.crit)); break;
+        case 0: end(mr_flow_pair_forward_tiles(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, g_stream)); break;
+        case 1: end(mr_flow_pair_forward_tiles_crit(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, g_stream, c.crit)); break;
+        case 2: end(mr_flow_pair_forward_tiles_typed(FWD_HEAD, P<void>(13), P<void>(14), P<void>(15), P<void>(16), FWD_TAIL, g_stream, c.crit, c.idt, c.mdt)); break;
+        case 3: end(mr_flow_pair_forward_grad_tiles(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, P(23), P(24), P(25), P<void>(26), g_stream)); break;
+        case 4: end(mr_flow_pair_forward_grad_tiles_crit(FWD_HEAD, P(13), P(14), P(15), P(16), FWD_TAIL, P(23), P(24), P(25), P<void>(26), g_stream, c.crit)); break;
         default: end(mr_flow_pair_forward_grad_tiles_typed(FWD_HEAD, P<void>(13), P<void>(14), P<void>(15), P<void>(16), FWD_TAIL, P(23), P(24), P(25),
-                                                           P<void>(26), nullptr, c.crit, c.idt, c.mdt)); break;
+                                                           P<void>(26), g_stream, c.crit, c.idt, c.mdt)); break;
         }
 #undef FWD_HEAD
 #undef FWD_TAIL
@@ -538,7 +549,7 @@ void pair_forward_cases() {
     begin("flow_pair_forward_grad_tiles refused: no unit gradient");
     end(mr_flow_pair_forward_grad_tiles(P(1), P(2), P(3), P(4), 3 * 65536, P(5), P(6), P(7), P(8), P(9), P(10), P<uint8_t>(11), P<uint8_t>(12), P(13),
                                         P(14), P(15), P(16), 3, P<void>(17), mr_pair_consist_tiles_workspace_bytes(4, 256), P(18), P(19), P(20), 4, 256,
-                                        256, 256, 0.05f, 1.0f, 0.5f, P<void>(21), P<void>(22), 2048, -1, nullptr, P(24), P(25), P<void>(26), nullptr));
+                                        256, 256, 0.05f, 1.0f, 0.5f, P<void>(21), P<void>(22), 2048, -1, nullptr, P(24), P(25), P<void>(26), g_stream));
 
     // occlusion over the list, and the pair loss's own entry points (plane form and listed form, both criteria)
     auto occlusion = [&](Pair c) {
@@ -546,7 +557,7 @@ void pair_forward_cases() {
         const int H = c.H ? c.H : c.is, W = c.W ? c.W : c.is;
         end(mr_occlusion_flow_tiles(P(1), P(2), c.ok ? P(3) : nullptr, P(4), 3LL * c.is * c.is - c.bstride_short, P(5), P(6), P(7), P(8), P(9), P(10),
                                     P<uint8_t>(11), P<uint8_t>(12), c.B, c.is, H, W, 0.05f, 1.0f, P<void>(13), P<void>(14), pair_cap(c), c.tile_bound,
-                                    nullptr));
+                                    g_stream));
     };
     auto consist = [&](Pair c, bool listed, bool hit) {
         const int H = c.H ? c.H : c.is, W = c.W ? c.W : c.is;
@@ -556,34 +567,34 @@ void pair_forward_cases() {
             name("pair_consist_forward_tiles_crit", c);
             end(mr_pair_consist_forward_tiles_crit(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P<void>(7), mr_pair_consist_tiles_workspace_bytes(c.B, c.is) - c.ws_short,
                                                    P(8), P(9), P(10), c.B, H, W, 0.5f, P<uint8_t>(21), P<uint8_t>(22), c.is, P<void>(23), P<void>(24), pair_cap(c),
-                                                   c.tile_bound, nullptr, c.crit));
+                                                   c.tile_bound, g_stream, c.crit));
             name("pair_consist_backward_tiles_crit", c);
             end(mr_pair_consist_backward_tiles_crit(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P(8), P(9), P(10), P(11), P(12), c.B, H, W, 0.5f, P<uint8_t>(21),
-                                                    P<uint8_t>(22), c.is, P(13), P<void>(23), P<void>(24), pair_cap(c), c.tile_bound, nullptr, c.crit));
+                                                    P<uint8_t>(22), c.is, P(13), P<void>(23), P<void>(24), pair_cap(c), c.tile_bound, g_stream, c.crit));
             if (c.crit == 0) {
                 name("pair_consist_forward_tiles", c);
                 end(mr_pair_consist_forward_tiles(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P<void>(7), mr_pair_consist_tiles_workspace_bytes(c.B, c.is) - c.ws_short,
                                                   P(8), P(9), P(10), c.B, H, W, 0.5f, P<uint8_t>(21), P<uint8_t>(22), c.is, P<void>(23), P<void>(24), pair_cap(c),
-                                                  c.tile_bound, nullptr));
+                                                  c.tile_bound, g_stream));
                 name("pair_consist_backward_tiles", c);
                 end(mr_pair_consist_backward_tiles(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P(8), P(9), P(10), P(11), P(12), c.B, H, W, 0.5f, P<uint8_t>(21),
-                                                   P<uint8_t>(22), c.is, P(13), P<void>(23), P<void>(24), pair_cap(c), c.tile_bound, nullptr));
+                                                   P<uint8_t>(22), c.is, P(13), P<void>(23), P<void>(24), pair_cap(c), c.tile_bound, g_stream));
             }
             return;
         }
         begin("pair_consist_forward_crit B%d hw%dx%d is%d crit%d cj%d hit%d ws-%lld ok%d", c.B, H, W, c.is, c.crit, c.Cj, (int)hit, (long long)c.ws_short, (int)c.ok);
         end(mr_pair_consist_forward_crit(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P<void>(7), mr_pair_consist_workspace_bytes(c.B, H, W) - c.ws_short, P(8), P(9),
-                                         P(10), P<uint8_t>(11), P<uint8_t>(12), P(13), P(14), P(15), P(16), P(17), P(18), c.B, H, W, 0.5f, h1, h2, c.is, nullptr,
+                                         P(10), P<uint8_t>(11), P<uint8_t>(12), P(13), P(14), P(15), P(16), P(17), P(18), c.B, H, W, 0.5f, h1, h2, c.is, g_stream,
                                          c.crit));
         begin("pair_consist_backward_crit B%d hw%dx%d is%d crit%d cj%d hit%d ws-%lld ok%d", c.B, H, W, c.is, c.crit, c.Cj, (int)hit, (long long)c.ws_short, (int)c.ok);
-        end(mr_pair_consist_backward_crit(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P(8), P(9), P(10), P(11), P(12), c.B, H, W, 0.5f, h1, h2, c.is, P(13), nullptr,
+        end(mr_pair_consist_backward_crit(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P(8), P(9), P(10), P(11), P(12), c.B, H, W, 0.5f, h1, h2, c.is, P(13), g_stream,
                                           c.crit));
         if (c.crit == 0) {
             begin("pair_consist_forward B%d hw%dx%d is%d cj%d hit%d ws-%lld ok%d", c.B, H, W, c.is, c.Cj, (int)hit, (long long)c.ws_short, (int)c.ok);
             end(mr_pair_consist_forward(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P<void>(7), mr_pair_consist_workspace_bytes(c.B, H, W) - c.ws_short, P(8), P(9), P(10),
-                                        P<uint8_t>(11), P<uint8_t>(12), P(13), P(14), P(15), P(16), P(17), P(18), c.B, H, W, 0.5f, h1, h2, c.is, nullptr));
+                                        P<uint8_t>(11), P<uint8_t>(12), P(13), P(14), P(15), P(16), P(17), P(18), c.B, H, W, 0.5f, h1, h2, c.is, g_stream));
             begin("pair_consist_backward B%d hw%dx%d is%d cj%d hit%d ws-%lld ok%d", c.B, H, W, c.is, c.Cj, (int)hit, (long long)c.ws_short, (int)c.ok);
-            end(mr_pair_consist_backward(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P(8), P(9), P(10), P(11), P(12), c.B, H, W, 0.5f, h1, h2, c.is, P(13), nullptr));
+            end(mr_pair_consist_backward(f12, P(2), P(3), P(4), P(5), P(6), c.Cj, P(8), P(9), P(10), P(11), P(12), c.B, H, W, 0.5f, h1, h2, c.is, P(13), g_stream));
         }
     };
     for (int B : {0, 4, 64})
@@ -616,20 +627,234 @@ void pair_forward_cases() {
     { Pair c; c.bstride_short = 256 * 256 + 1; occlusion(c); }
 }
 
+// ---- run, not recorded: every other entry point that takes a stream (--unrecorded) -----------------------------------------
+// No golden file holds these cases' launch geometry; tests/test_stream_record_host.py runs them with --stream and asks that
+// every runtime call they make is on that stream, and that between them and the recorded table every kernel is launched.
+void unrecorded_cases() {
+    const float E5 = 1e-5f;
+    // the nine sources the recorded table does not touch
+    for (int full = 0; full < 2; full++)
+        for (int center : {-1, 9, 17}) {
+            if (!full && center == 17) continue;
+            const int64_t ws = full ? mr_mano_full_workspace_floats(3) : mr_mano_workspace_floats(3);
+            begin("unrecorded mano_forward full%d center%d ws%lld", full, center, (long long)ws);
+            if (full)
+                end(mr_mano_forward_full(P(1), P(2), center == 9 ? P(20) : nullptr, P(3), P(4), P(5), P(6), P(7), P(8), P(9), P<int32_t>(10), P<int32_t>(11),
+                                         P<int32_t>(12), center == 17 ? MR_MANO_POSE_AXISANG : MR_MANO_POSE_PCA, 30, center, 0.001f,
+                                         center == 17 ? P(21) : nullptr, center == 17 ? P(22) : nullptr, center == 17 ? P(23) : nullptr, P(13), P(14), P(15), 3,
+                                         g_stream));
+            else
+                end(mr_mano_forward(P(1), P(2), P(3), P(4), P(5), P(6), P(7), P(8), P(9), P<int32_t>(10), P<int32_t>(11), P<int32_t>(12), 30, center, P(13),
+                                    P(14), P(15), 3, g_stream));
+            begin("unrecorded mano_backward full%d center%d", full, center);
+            if (full)
+                end(mr_mano_backward_full(P(3), P(4), P(5), P(6), P(7), P(8), P(9), P<int32_t>(10), P<int32_t>(11), P<int32_t>(12),
+                                          center == 17 ? MR_MANO_POSE_AXISANG : MR_MANO_POSE_PCA, 30, center, P(13), P(16), P(17), P(18), P(19),
+                                          center == 9 ? P(24) : nullptr, 3, g_stream));
+            else
+                end(mr_mano_backward(P(3), P(4), P(5), P(6), P(7), P(8), P(9), P<int32_t>(10), P<int32_t>(11), P<int32_t>(12), 30, center, P(13), P(16), P(17),
+                                     P(18), P(19), 3, g_stream));
+        }
+    for (int B : {0, 3}) {
+        begin("unrecorded meshreg_post_forward B%d", B);
+        end(mr_meshreg_post_forward(P(1), P(2), P(3), P(4), P(5), P(6), 100.0f, 0.0001f, 0.4f, 256.0f, 256.0f, P(7), P(8), P(9), P(10), P(11), B, 778, 21,
+                                    1002, g_stream));
+        begin("unrecorded meshreg_post_backward B%d", B);
+        end(mr_meshreg_post_backward(P(1), P(2), P(3), P(4), P(5), P(6), 100.0f, 0.0001f, 0.4f, 256.0f, 256.0f, P(7), P(8), P(9), P(10), P(11), P(12), P(13),
+                                     P(14), P(15), P(16), B, 778, 21, 1002, g_stream));
+    }
+    for (int dt = 0; dt < 2; dt++)
+        for (int cl = 0; cl < 2; cl++)
+            for (int res = 0; res < 2; res++)
+                for (int relu = 0; relu < 2; relu++)
+                    for (int plane : {49, 3136}) {
+                        begin("unrecorded bn_act_forward dt%d cl%d res%d relu%d plane%d", dt, cl, res, relu, plane);
+                        end(mr_bn_act_forward(P<void>(1), res ? P<void>(2) : nullptr, P(3), P(4), P(5), P(6), E5, relu, dt, cl, P<void>(7), 2, 64, plane, g_stream));
+                        for (int params = 0; params < 2; params++) {
+                            begin("unrecorded bn_act_backward dt%d cl%d res%d relu%d plane%d params%d", dt, cl, res, relu, plane, params);
+                            end(mr_bn_act_backward(P<void>(8), res ? P<void>(9) : nullptr, P<void>(1), res ? P<void>(2) : nullptr, P(3), P(4), P(5), P(6), E5, relu,
+                                                   dt, cl, P<void>(10), res ? P<void>(11) : nullptr, params ? P(12) : nullptr, params ? P(13) : nullptr,
+                                                   P<void>(14), mr_bn_act_backward_workspace_bytes(2, 64), 2, 64, plane, g_stream));
+                        }
+                    }
+    for (int dt = 0; dt < 2; dt++)
+        for (int plane : {49, 784}) {
+            begin("unrecorded bn_add_bn_act_forward dt%d plane%d", dt, plane);
+            end(mr_bn_add_bn_act_forward(P<void>(1), P<void>(2), P(3), P(4), P(5), P(6), E5, P(7), P(8), P(9), P(10), E5, dt, P<void>(11), 2, 128, plane,
+                                         g_stream));
+            for (int params = 0; params < 2; params++) {
+                begin("unrecorded bn_add_bn_act_backward dt%d plane%d params%d", dt, plane, params);
+                end(mr_bn_add_bn_act_backward(P<void>(12), params ? P<void>(13) : nullptr, P<void>(1), P<void>(2), P(3), P(4), P(5), P(6), E5, P(7), P(8), P(9),
+                                              P(10), E5, dt, P<void>(14), P<void>(15), params ? P(16) : nullptr, params ? P(17) : nullptr,
+                                              params ? P(18) : nullptr, params ? P(19) : nullptr, P<void>(20),
+                                              mr_bn_add_bn_act_backward_workspace_bytes(2, 128), 2, 128, plane, g_stream));
+            }
+        }
+    for (int dt = 0; dt < 2; dt++)
+        for (int layout = 0; layout < 3; layout++)
+            for (int hw : {13, 112}) {
+                begin("unrecorded stem_pool_forward dt%d layout%d hw%d", dt, layout, hw);
+                end(mr_stem_pool_forward(P<void>(1), P(2), P(3), P(4), P(5), E5, dt, layout, P<void>(6), layout ? P<unsigned char>(7) : nullptr, 2, 64, hw, hw,
+                                         g_stream));
+                for (int params = 0; params < 2; params++) {
+                    begin("unrecorded stem_pool_backward dt%d layout%d hw%d params%d", dt, layout, hw, params);
+                    end(mr_stem_pool_backward(P<void>(8), params ? P<void>(9) : nullptr, layout == 2 ? nullptr : P<void>(1),
+                                              layout ? P<unsigned char>(7) : nullptr, P(2), P(3), P(4), P(5), E5, dt, layout, P<void>(10),
+                                              params ? P(11) : nullptr, params ? P(12) : nullptr, P<void>(13),
+                                              mr_stem_pool_backward_workspace_bytes(2, 64, hw, hw), 2, 64, hw, hw, g_stream));
+                }
+                if (layout != 2) continue;
+                begin("unrecorded stem_pool_param_grads dt%d hw%d", dt, hw);
+                end(mr_stem_pool_param_grads(P<void>(8), P<void>(9), P<unsigned char>(7), P(2), P(3), P(4), P(5), E5, dt, P(11), P(12), P<void>(13),
+                                             mr_stem_pool_backward_workspace_bytes(2, 64, hw, hw), 2, 64, hw, hw, g_stream));
+            }
+    for (int wcl = 0; wcl < 2; wcl++)
+        for (int hw : {26, 224}) {
+            begin("unrecorded stem_conv_wrw wcl%d hw%d", wcl, hw);
+            end(mr_stem_conv_wrw(P(1), wcl ? P(2) : nullptr, P<unsigned char>(3), P(4), P(5), P(6), P(7), E5, P(8), P(9), wcl, P<void>(10),
+                                 mr_stem_conv_wrw_workspace_bytes(2, 64, hw, hw), 2, 64, hw, hw, 3, 7, 2, 3, g_stream));
+        }
+    for (int idt : {MR_DTYPE_F32, MR_DTYPE_BF16})
+      for (int mdt : {MR_DTYPE_F32, MR_DTYPE_U8})
+        for (int mc : {0, 1, 3}) {
+            begin("unrecorded frames_to_batch_typed dt%d/%d mc%d", idt, mdt, mc);
+            end(mr_frames_to_batch_typed(P<uint8_t>(1), P<double>(2), mc == 1 ? nullptr : P<uint8_t>(3), 0.5f, 0.5f, 0.5f, 1.0f, 1.0f, 1.0f, P<void>(4),
+                                         mr_frames_to_batch_workspace_bytes(3, 64, 48), P<void>(5), mc ? P<void>(6) : nullptr, mc ? mc : 3, 3, 90, 120, 64, 48,
+                                         g_stream, idt, mdt));
+        }
+    begin("unrecorded frames_to_batch");
+    end(mr_frames_to_batch(P<uint8_t>(1), P<double>(2), P<uint8_t>(3), 0.5f, 0.5f, 0.5f, 1.0f, 1.0f, 1.0f, P<void>(4), mr_frames_to_batch_workspace_bytes(3, 64, 48),
+                           P(5), P(6), 3, 3, 90, 120, 64, 48, g_stream));
+    {
+        // (the plans are host arrays, read before the call returns: blur or none, every op, a frame with no op at all)
+        const uint8_t flip[3] = {0, 1, 0};
+        const float radius[3] = {0.0f, 1.5f, 6.0f};
+        const int codes[12] = {MR_COLOR_OP_BRIGHTNESS, MR_COLOR_OP_SATURATION, MR_COLOR_OP_HUE, MR_COLOR_OP_CONTRAST,
+                               MR_COLOR_OP_CONTRAST, MR_COLOR_OP_HUE, MR_COLOR_OP_NONE, MR_COLOR_OP_NONE,
+                               MR_COLOR_OP_NONE, MR_COLOR_OP_NONE, MR_COLOR_OP_NONE, MR_COLOR_OP_NONE};
+        const float values[12] = {1.25f, 0.5f, 17.0f, 1.5f, 0.75f, -30.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int in_place = 0; in_place < 2; in_place++) {
+            begin("unrecorded frames_color_augment in_place%d", in_place);
+            end(mr_frames_color_augment(P<uint8_t>(1), in_place ? P<uint8_t>(1) : P<uint8_t>(2), in_place ? nullptr : flip, radius, codes, values, P<void>(3),
+                                        mr_frames_color_augment_workspace_bytes(3, 90, 120), 3, 90, 120, g_stream));
+        }
+    }
+    for (int geo = 0; geo < 4; geo++) {
+        const int comps = geo ? 3 : 1, lh = geo >= 2 ? 2 : 1, lv = geo == 3 ? 2 : 1;
+        begin("unrecorded jpeg_reconstruct c%d %dx%d", comps, lh, lv);
+        end(mr_jpeg_reconstruct(P<unsigned char>(1), 3, 61, 45, comps, lh, lv, P<unsigned char>(2), P<void>(3),
+                                mr_jpeg_reconstruct_workspace_bytes(3, 61, 45, comps, lh, lv), g_stream));
+    }
+    for (int ch = 1; ch <= 4; ch++) {
+        begin("unrecorded png_unfilter ch%d", ch);
+        end(mr_png_unfilter(P<unsigned char>(1), 3, 61, 45, ch, P<unsigned char>(2), nullptr, g_stream));
+    }
+
+    // the entry points of the five recorded sources that the recorded table never calls
+    for (int mode = 0; mode < 2; mode++) {
+        begin("unrecorded warp_forward mode%d", mode);
+        end(mr_warp_forward(P(1), P(2), P(3), P(4), 2, 3, 60, 44, 1.0f, mode, g_stream));
+        for (int which = 0; which < 3; which++) {
+            begin("unrecorded warp_backward mode%d which%d", mode, which);
+            end(mr_warp_backward(P(1), P(2), P(5), which != 1 ? P(6) : nullptr, which != 2 ? P(7) : nullptr, 2, 3, 60, 44, 1.0f, mode, g_stream));
+        }
+    }
+    for (int scale = 0; scale < 2; scale++) {
+        begin("unrecorded occlusion_mask scale%d", scale);
+        end(mr_occlusion_mask(P(1), P(2), P(3), P(4), 3LL * 64 * 64, scale ? P(5) : nullptr, scale ? P(6) : nullptr, P(7), P(8), 2, 64, 64, 0.05f, 1.0f,
+                              g_stream));
+        for (int hit = 0; hit < 2; hit++) {
+            begin("unrecorded occlusion_flow scale%d hit%d", scale, hit);
+            end(mr_occlusion_flow(P(1), P(2), P(3), P(4), 3LL * 64 * 64, scale ? P(5) : nullptr, scale ? P(6) : nullptr, P(7), P(8), P(9), P(10),
+                                  hit ? P<uint8_t>(11) : nullptr, hit ? P<uint8_t>(12) : nullptr, 2, 64, 64, 60, 44, 0.05f, 1.0f, g_stream));
+        }
+    }
+    for (int lut = 0; lut < 2; lut++) {
+        begin("unrecorded flow_mask lut%d", lut);
+        end(mr_flow_mask(P(1), P<int32_t>(2), lut ? P(3) : nullptr, lut ? 40 : 0, 0.5f, P(4), 2, 64, g_stream));
+    }
+    begin("unrecorded flow_finalize_forward");
+    end(mr_flow_finalize_forward(P(1), P(2), P(3), P(4), P(5), 2, 64, 60, 44, g_stream));
+    begin("unrecorded flow_finalize_backward");
+    end(mr_flow_finalize_backward(P(5), P(2), P(3), P(4), P(6), 2, 64, 60, 44, g_stream));
+    for (int cam = 0; cam < 2; cam++) {
+        begin("unrecorded flow_vertices_forward cam%d", cam);
+        end(mr_flow_vertices_forward(P(1), P(2), P(3), P(4), P(5), P(6), P(7), cam, 256.0f, P(8), P(9), P(10), P(11), 2, 1778, g_stream));
+        begin("unrecorded flow_vertices_parts_forward cam%d", cam);
+        end(mr_flow_vertices_parts_forward(P(1), P(12), P(2), P(13), 778, 1000, P(3), P(4), P(5), P(6), P(7), cam, 256.0f, P(8), P(9), P(10), P(11), 2, g_stream));
+        for (int clear = 0; clear < 2; clear++) {
+            begin("unrecorded flow_pair_prologue_parts cam%d clear%d", cam, clear);
+            end(mr_flow_pair_prologue_parts(P(1), P(12), P(2), P(13), 778, 1000, P(3), P(4), P(5), P(6), P(7), cam, 256.0f, P(8), P(9), P(10), P(11),
+                                            P<int64_t>(14), cam, P<int64_t>(15), P<int32_t>(16), 1538, 2000, 2, clear ? P<void>(17) : nullptr,
+                                            clear ? mr_render_clear_bytes(4, 2 * 3538, 256) : 0, g_stream));
+        }
+    }
+    begin("unrecorded flow_vertices_backward");
+    end(mr_flow_vertices_backward(P(1), P(2), P(3), P(4), P(5), P(6), P(7), P(8), 2, 1778, g_stream));
+    begin("unrecorded flow_vertices_parts_backward");
+    end(mr_flow_vertices_parts_backward(P(1), P(12), P(2), P(13), 778, 1000, P(3), P(4), P(5), P(6), P(7), P(8), P(9), P(10), 2, g_stream));
+    for (int batched = 0; batched < 2; batched++) {
+        begin("unrecorded stack_pair_faces batched%d", batched);
+        end(mr_stack_pair_faces(P<int64_t>(1), batched, P<int64_t>(2), 778, P<int32_t>(3), 2, 1538, 2000, g_stream));
+    }
+    // the upstream-compatible raster entry points
+    for (int rd = 0; rd < 2; rd++) {
+        begin("unrecorded forward_face_index_map depth%d", rd);
+        end(mr_forward_face_index_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), 2, 1538, 64, NEAR, FAR, 1, 1, rd, g_stream));
+    }
+    begin("unrecorded forward_texture_sampling");
+    end(mr_forward_texture_sampling(P(1), P(2), P<int32_t>(3), P(4), P(5), P(6), P<int32_t>(7), P(8), 2, 1538, 64, 2, EPS, g_stream));
+    begin("unrecorded backward_textures");
+    end(mr_backward_textures(P<int32_t>(1), P(2), P<int32_t>(3), P(4), P(5), 2, 1538, 64, 2, g_stream));
+    begin("unrecorded backward_depth_map");
+    end(mr_backward_depth_map(P(1), P(2), P<int32_t>(3), P(4), P(5), P(6), P(7), 2, 1538, 64, g_stream));
+    // kernel D by strips of two lines (rasters 263..525) and of one (526..1421) in the forms the recorded rasters do not
+    // reach: alone (no texture, no depth term), with the texture gather only, with the depth gather only; and the
+    // upstream-compatible entry point's one-line strips
+    for (int is : {480, 1024})
+        for (int form = 0; form < 3; form++) {
+            Bwd c; c.is = is; c.tex = form == 1; c.rd = form == 2;
+            begin("unrecorded render_backward is%d tex%d d%d", is, (int)c.tex, c.rd);
+            end(render_backward(c));
+        }
+    begin("unrecorded backward_pixel_map is1024");
+    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), 2, 1538, 1024, EPS, 1, 1, g_stream));
+    begin("unrecorded face_inv_map");
+    end(mr_face_inv_map(P(1), P<int32_t>(2), P(3), 2, 1538, 64, g_stream));
+    begin("unrecorded selftest_division");
+    end(mr_selftest_division(P(1), P(2), P(3), P(4), 1000, g_stream));
+}
+
+// The check checks: an entry point that makes all four kinds of stream-ordered call (launches, memsets, an allocation and its
+// release), handed one stream while the recorder expects another.  Every one of its calls must show as off the stream.
+void stream_selftest_case() {
+    void* const other = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(g_stream) ^ 0x10);
+    rec_expect_stream(other);
+    begin("selftest: expectation differs from the stream handed over");
+    end(mr_backward_pixel_map(P(1), P<int32_t>(2), P(3), P(4), P(5), P(6), P(7), 2, 1538, 256, EPS, 0, 1, g_stream));
+    rec_expect_stream(g_stream);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s <kernel argument table> [--cus N] [--stack-fill BYTE] [--two-devices]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <kernel argument table> [--cus N] [--stack-fill BYTE] [--two-devices] [--stream HEX] [--unrecorded] [--kernel-names]\n", argv[0]);
         return 2;
     }
     rec_load_args(argv[1]);
     int cus = 256;
-    bool two_devices = false;
+    bool two_devices = false, unrecorded = false;
     for (int i = 2; i < argc; i++) {
         if (!std::strcmp(argv[i], "--cus") && i + 1 < argc) cus = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--stack-fill") && i + 1 < argc) g_stack_fill = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--two-devices")) two_devices = true;
+        else if (!std::strcmp(argv[i], "--unrecorded")) unrecorded = true;
+        else if (!std::strcmp(argv[i], "--kernel-names")) { rec_print_kernel_names(); return 0; }
+        else if (!std::strcmp(argv[i], "--stream") && i + 1 < argc) {
+            g_stream = reinterpret_cast<mr_stream_t>(static_cast<uintptr_t>(std::strtoull(argv[++i], nullptr, 16)));
+            rec_expect_stream(g_stream);
+        }
     }
     rec_set_cus(cus);
     if (two_devices) {
@@ -645,6 +870,16 @@ int main(int argc, char** argv) {
         return 0;
     }
     rec_set_device(0, 1);
+    if (unrecorded) {
+        // (with the recorded table in front, so that the kernels still unlaunched at the end are unlaunched by ALL cases)
+        forward_cases(true); pair_step_cases(true); forward_refusals(); backward_cases(); vc_backward_cases(); scatter_cases();
+        pair_forward_cases();
+        unrecorded_cases();
+        stream_selftest_case();
+        std::printf("# never launched\n");
+        rec_report_unlaunched();
+        return 0;
+    }
     forward_cases(cus == 256);
     pair_step_cases(cus == 256);
     if (cus != 256) return 0;  // (only the binning pass looks at the device, for its parts: the cases it decides)
