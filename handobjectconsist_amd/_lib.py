@@ -78,6 +78,10 @@ SIGNATURES = {
     "mr_mano_backward_full": (_I, [_P] * 10 + [_I, _I, _I] + [_P] * 6 + [_I, _P]),
     "mr_meshreg_post_forward": (_I, [_P] * 6 + [_F] * 5 + [_P] * 5 + [_I, _I, _I, _I, _P]),
     "mr_meshreg_post_backward": (_I, [_P] * 6 + [_F] * 5 + [_P] * 10 + [_I, _I, _I, _I, _P]),
+    # MeshRegNet's ManoAdaptor (csrc/mano_adapt.hip): additions to ABI 9
+    "mr_mano_adapt_workspace_floats": (_I, [_I, _I]),
+    "mr_mano_adapt_forward": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "mr_mano_adapt_backward": (_I, [_P, _P, _I] + [_P] * 5 + [_I, _I, _I, _P]),
     "mr_warp_forward": (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_warp_backward": (_I, [_P] * 5 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_occlusion_mask": (_I, [_P] * 4 + [_L, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),

@@ -478,6 +478,35 @@ MR_API int mr_meshreg_post_backward(const float* verts_mm, const float* joints_m
                                     int num_hand_verts, int num_joints, int num_obj_verts,
                                     mr_stream_t stream);
 
+/* MeshRegNet's ManoAdaptor (meshregnet.py:23-51, used at :192-198): a dense regressor
+ * applied to the POSED hand vertices, then joints and vertices re-centred on one adapted joint.
+ * An addition to ABI 9.  All tensors fp32 and dense, units the caller's:
+ *   verts[B,V,3], weight[J,V], center in {-1, 0..J-1}
+ *   j[b,k,:] = sum_i weight[k,i] * verts[b,i,:],   c[b] = j[b,center]  (0 for center == -1)
+ *   joints_out[B,J,3] = j - c,                      verts_out[B,V,3] = verts - c
+ * One launch, one workgroup per sample, no atomics: two calls give the same bits, and a sample's
+ * results do not depend on the batch it is in.
+ * mr_mano_adapt_backward: g_verts[B,V,3] / g_joints[B,J,3] are the gradients of verts_out /
+ * joints_out; either may be NULL (zeros).  grad_verts[B,V,3] in one launch; work
+ * (mr_mano_adapt_workspace_floats(B, J) floats) receives gt[B,J,3] = g_joints with row `center`
+ * reduced by sum_k g_joints[b,k] + sum_i g_verts[b,i].  grad_weight[J,V], computed iff non-NULL by a
+ * second launch: sum_b sum_r gt[b,k,r] * verts[b,i,r], b in order (no memset, no atomics).
+ * B == 0: MR_OK, nothing launched.  B < 0, V < 1, J < 1, center outside -1..J-1, a NULL or
+ * misaligned required pointer: MR_ERR_BADARG.  J > 32 or V > 4096: MR_ERR_NOTIMPL -- a sample's
+ * vertices and joints stay in LDS, (3 V + 3 J + 15) floats = 49 596 bytes of a workgroup's 64 KB
+ * at the limit.  All of it before any launch.
+ * mr_mano_adapt_workspace_floats returns an int (3 B J; a count beyond INT_MAX, B < 0 or J < 1:
+ * MR_ERR_BADARG): the int64_t sizing entry points are the closed set that
+ * tests/golden/workspace_sizes.json records, and that record is not regenerated. */
+MR_API int mr_mano_adapt_workspace_floats(int batch_size, int num_joints);
+MR_API int mr_mano_adapt_forward(const float* verts, const float* weight, int center,
+                                 float* verts_out, float* joints_out, int batch_size,
+                                 int num_verts, int num_joints, mr_stream_t stream);
+MR_API int mr_mano_adapt_backward(const float* verts, const float* weight, int center,
+                                  const float* g_verts, const float* g_joints, float* work,
+                                  float* grad_verts, float* grad_weight, int batch_size,
+                                  int num_verts, int num_joints, mr_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * 3. Warping (meshreg/warping/imgflowarp.py)
  * ---------------------------------------------------------------------------------- */
