@@ -46,6 +46,9 @@ constexpr int ST_G_MAX = 32;
 constexpr int ST_WAVES = 8;   // waves per workgroup
 constexpr int ST_TW = 32, ST_TH = 8;  // the forward's tile
 constexpr int ST_MAX_TILES = 4096;    // tiles per image the covered-tile list in LDS can hold (1024 x 1024 pixels)
+// fixed point of the per-workgroup sums: terms below 2^ST_FIX_BITS in magnitude (2^-37 of the workgroup's largest gradient
+// per term: 13 bits below the last bit of an fp32 value of that size), sums below 2^ST_SUM_BITS (st_headroom)
+constexpr int ST_FIX_BITS = 37, ST_SUM_BITS = 50;
 
 constexpr int PS_T = 256;      // kernel D by strips: threads per workgroup
 constexpr int PS_QCAP = 1024;  // queued entries; a round of PS_T faces adds at most 3 * PS_T
@@ -491,6 +494,59 @@ inline ScatterPlan plan_scatter_tiles(int B, int V, int is, bool colour_space, b
     p.lds = (size_t)table_bytes;
     return p;
 }
+
+// The scalar arithmetic of the scatter's kernels (scatter_tiles_body): what a workgroup derives from the images' counts of
+// covered tiles, its index and the launch's grid.  The kernel does the sums over the images with wave scans and calls these per
+// element; tests/host/launch_plan_cases.cpp calls them in plain loops.
+//
+// The split (WORK): q = tiles per workgroup, at least one per wave, such that sum st_parts(n_b, q) fits the grid.  First try
+// q = ST_WAVES; where that needs more workgroups than the launch has, st_second_q and a second sum, clamped by st_used.
+MR_PLAN_HD inline int st_parts(int n, int q) { return (n + q - 1) / q; }  // workgroups of an image with n covered tiles
+MR_PLAN_HD inline int st_second_q(int N, int grid, int B2) {  // N = the launch's covered tiles
+    const int room = grid - B2 > 1 ? grid - B2 : 1;           // (sum ceil(n_b / q) <= N / q + B2)
+    const int q = (N + room - 1) / room;
+    return q > ST_WAVES ? q : ST_WAVES;
+}
+// (grid <= images: cannot be; the surplus images would go without a gradient)
+MR_PLAN_HD inline int st_used(int used, int grid) { return used > grid ? grid : used; }
+// Logical index -> slot of the `used` workgroups with work, where the grid is a multiple of 8 (else the index is the slot).
+// xcd_remap gave XCD x the logical indices [x grid / 8, (x + 1) grid / 8): it takes the slots [x used / 8, (x + 1) used / 8) with
+// the first of them -- every XCD the same share of the work, images in list order (as the forward's tile list hands them to the
+// XCDs), divisions by 8 only.  Index lidx is the j-th of its XCD, which has n slots from k0 on: slot k0 + j, none when j >= n.
+struct StSlot {
+    int k0, j, n;
+};
+MR_PLAN_HD inline StSlot st_slot(int lidx, int grid, int used) {
+    const int per = grid >> 3, x = lidx / per;
+    const int k0 = (int)(((long long)x * used) >> 3), k1 = (int)(((long long)(x + 1) * used) >> 3);
+    return StSlot{k0, lidx - x * per, k1 - k0};
+}
+// workgroup `part` of the pb that share an image's list of nb tiles takes the tiles [first, first + n)
+struct StShare {
+    int first, n;
+};
+MR_PLAN_HD inline StShare st_share(int nb, int pb, int part) {
+    const int each = nb / pb, rem = nb % pb;
+    return StShare{part * each + (part < rem ? part : rem), each + (part < rem ? 1 : 0)};
+}
+// The fixed point.  A table cell receives at most 3 terms per pixel (a face may name one vertex three times) of every tile the
+// workgroup walks -- workgroup `part` of G, a wave per tile, over a list of n_hits --, each below 2^ST_FIX_BITS in magnitude:
+// 2^13 of them fit the 51-bit field of the sums.  A workgroup with more (beyond ten covered tiles: large rasters, screen-filling
+// meshes) gives up one bit of the 37 per doubling -- at 256 tiles per workgroup that is still 2^-32 of the largest gradient per
+// term.
+MR_PLAN_HD inline int st_tiles_walked(int n_hits, int part, int G) {
+    const int rem = n_hits - part * ST_WAVES;
+    const int rounds = rem / (G * ST_WAVES), tail = rem % (G * ST_WAVES);  // full rounds of the G workgroups' waves, and the last
+    return rounds * ST_WAVES + (tail < ST_WAVES ? tail : ST_WAVES);
+}
+MR_PLAN_HD inline long long st_terms(int n_hits, int part, int G) { return 3LL * ST_TW * ST_TH * st_tiles_walked(n_hits, part, G); }
+MR_PLAN_HD inline int st_headroom(long long terms) {
+    int headroom = 0;
+    while ((terms >> headroom) >= (1LL << (ST_SUM_BITS - ST_FIX_BITS))) headroom++;
+    return headroom;
+}
+// ... and the binary point of the terms: bm = the float bits of the workgroup's largest |gradient|
+MR_PLAN_HD inline int st_shift(int headroom, unsigned bm) { return ST_FIX_BITS - headroom - ((int)(bm >> 23) - 126); }
 
 // ---- the listed pair-loss forward (warp.hip: launch_flow_pair_forward) -----------------------------------------------------
 // the form -- records / unit gradient / loss only --, the criterion and the batch's element types are chosen once per launch

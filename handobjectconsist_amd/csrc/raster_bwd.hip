@@ -723,9 +723,6 @@ __global__ void __launch_bounds__(SV_WAVES * MR_WAVE) scatter_vc_kernel(ScatterV
 // 4 x 8 waves fit a compute unit, so all 1024 workgroups of a 128-image launch are resident at once.
 // (ST_G workgroups per image or more, ST_WAVES waves each, ST_TW x ST_TH tiles, ST_MAX_TILES of them per image: launch_plan.hpp)
 static_assert(ST_TW == TILE_W && ST_TH == TILE_H, "the scatter walks the forward's tiles");
-// fixed point of the per-workgroup sums: terms below 2^ST_FIX_BITS in magnitude (2^-37 of the workgroup's largest gradient
-// per term: 13 bits below the last bit of an fp32 value of that size), sums below 2^ST_SUM_BITS (see scatter_tiles_body)
-constexpr int ST_FIX_BITS = 37, ST_SUM_BITS = 50;
 
 struct ScatterTilesParams {
     GatherVCParams g;
@@ -810,6 +807,123 @@ __device__ __forceinline__ void st_load_grad(const ScatterTilesParams& sp, int b
     }
 }
 
+// ---- phases of scatter_tiles_body, each over what it is handed.  The stretches that stay in the body are there because every
+// function form tried for them changed the compiled kernels (profiles/scatter_phases_isa.txt).
+
+// flush: the table's sums, back to floats and added to the image's gradient
+template <int NCH>
+__device__ __forceinline__ void st_flush(const long long* vtab, int V, int shift, float* out) {
+    for (int k = threadIdx.x; k < V * NCH; k += blockDim.x) {
+        const long long tsum = (long long)((unsigned long long)vtab[k] << (64 - ST_SUM_BITS - 1)) >> (64 - ST_SUM_BITS - 1);
+        if (tsum != 0) {
+            const float v = (float)ldexp((double)tsum, -shift);
+            if (v != 0.0f) atomicAdd(&out[(k / NCH) * 3 + k % NCH], v);
+        }
+    }
+}
+
+// bound, PAIR (pass 1): the pair loss's backward for the tiles of workgroup `part` of the G that share the image's list
+// (pair_consist_backward_tiles_kernel's arithmetic, one pixel per thread, two tiles at a time), times the epilogue masks as
+// st_load_grad forms them, into the stash; the largest |gradient| comes out on the way, in mx.  A final flow with a zero x
+// component (everything the masks or the occlusion check removed) has a zero gradient: no taps.
+template <bool WORK, PairCrit CRIT, typename TileAt>
+__device__ __forceinline__ void st_pair_pass1(const ScatterTilesParams& sp, int b, int part, int G, int n_hits, int T, TileAt tile_at, unsigned& mx) {
+    const int is = sp.g.is;
+    const int n_mine = st_tiles_walked(n_hits, part, G);
+    const int half = threadIdx.x >> 8, tid = threadIdx.x & 255;
+    const int dir = b >= sp.split ? 1 : 0, pb = b - dir * sp.split;
+    const float cnt = sp.sums[pb * 4 + (dir ? 1 : 3)];
+    const float* gl = dir ? sp.gl_fwd : sp.gl_bwd;
+    const float coef = gl ? pair_coef(gl[pb], cnt) : 0.0f;
+    const float* src = dir ? sp.image_ref : sp.image;
+    const float* tgt = dir ? sp.image : sp.image_ref;
+    const float* jit = dir ? sp.jitter : sp.jitter_ref;
+    const int64_t hw_img = (int64_t)sp.H * sp.W;
+    for (int m = half; m < n_mine; m += 2) {
+        const int t = tile_at(part * ST_WAVES + (m % ST_WAVES) + (m / ST_WAVES) * G * ST_WAVES);
+        const int x = (t % sp.tiles_x) * ST_TW + (tid & 31), ry = (t / sp.tiles_x) * ST_TH + (tid >> 5);
+        const int y = is - 1 - ry;
+        if (x >= sp.W || ry >= is || y >= sp.H) continue;
+        const int64_t pixc = (int64_t)y * sp.W + x;
+        float2 gq = make_float2(0.0f, 0.0f);
+        // the coverage word, the flow and the epilogue masks of the pixel are requested TOGETHER (all inside their
+        // allocations; what an uncovered row pair holds there is never used): the taps are the only dependent trip
+        const uint32_t word = sp.tile_hit[(int64_t)b * T + t];
+        const int64_t o = ((int64_t)b * is + y) * is + x;
+        float2 uv = *reinterpret_cast<const float2*>(sp.flow + ((int64_t)b * hw_img + pixc) * 2);
+        float a = sp.m_pre[o];
+        float mxo = (b < sp.split ? sp.m_x_lo[o] : sp.m_x_hi[o - (int64_t)sp.split * is * is]), oc = sp.occl[o];
+        pin(uv.x); pin(uv.y); pin(a); pin(mxo); pin(oc);
+        if (coef != 0.0f && ((word >> (8 * ((ry & 7) >> 1))) & 0xffu) != 0u) {
+            if (uv.x != 0.0f) {
+                const float post = mxo * oc;
+                // (pair_pixel's sequence, spelled out: see pair_pixel)
+                const DirTaps tp = pair_taps(uv, x, y, sp.H, sp.W);
+                DirRaw2 q{};
+                pair_load(tp, src, tgt, jit, jit, sp.Cj, false, pb, pixc, hw_img, q);
+                pin(q);
+                const DirRaw r = unpack(q, tp.a);
+                const DirOut e = pair_eval(tp, r, sp.H, sp.W, sp.pair_thresh, false);
+                const float2 gp = pair_grad<CRIT>(tp, r, e, sp.H, sp.W, coef);
+                gq = make_float2((gp.x * post) * a, (gp.y * post) * a);
+            }
+        }
+        *reinterpret_cast<float2*>(sp.stash + ((int64_t)b * hw_img + pixc) * 2) = gq;
+        mx = max(mx, abs_bits_max(gq));
+    }
+}
+
+// coefficient, UNIT: the image's scalars -- count, sum of the incoming loss gradients, bound of the unit gradient ...
+struct StUnit {
+    float cnt, gl, max;
+};
+__device__ __forceinline__ void st_unit_scalars(const ScatterTilesParams& sp, int b, StUnit& u) {
+    const int dir = b >= sp.split ? 1 : 0, pb = b - dir * sp.split;
+    const float* gl = dir ? sp.gl_fwd : sp.gl_bwd;
+    u.cnt = sp.sums[pb * 4 + (dir ? 1 : 3)];
+    u.gl = gl ? gl[pb] : 0.0f;
+    if (sp.gl_sum) u.gl += sp.gl_sum[pb];
+    if (sp.gl_mean && (dir || !sp.mean_of)) u.gl += sp.gl_mean[0] / sp.mean_div;
+    u.max = sp.unit_max[b];
+}
+// ... and its coefficient (pair_consist_backward_tiles_kernel's): every gradient of the image is unit * coefficient, and
+// |unit| <= unit_max rounds to at most fl(unit_max * |coefficient|) (rounding is monotone): the bound of the fixed point, left in
+// mx as float bits.  A zero coefficient leaves the image without a gradient whatever the unit gradient holds: mx stays 0.
+__device__ __forceinline__ float st_unit_coef(const ScatterTilesParams& sp, int b, const StUnit& u, unsigned& mx) {
+    const float* gl = (b >= sp.split) ? sp.gl_fwd : sp.gl_bwd;
+    const float ucoef = (gl || sp.gl_sum || sp.gl_mean) ? pair_coef(u.gl, u.cnt) : 0.0f;
+    if (ucoef != 0.0f) mx = __float_as_uint(u.max * ucoef) & 0x7fffffffu;
+    return ucoef;
+}
+
+// accumulate (pass 2), a lane's loads for its four pixels of a covered tile: gradient, weights, and the forward's records (REC)
+// or the depth
+template <bool FLOWGRAD, bool REC, bool PAIR, bool UNIT>
+__device__ __forceinline__ void st_tile_loads(const ScatterTilesParams& sp, int b, int yi, int x, float ucoef, float (&g)[4][3], float (&w)[4][3],
+                                              int (&vid)[4][3], float (&zp)[4]) {
+    const int is = sp.g.is;
+    st_load_grad<FLOWGRAD, PAIR, UNIT>(sp, b, yi, x, g, ucoef);
+    const float4* wq = reinterpret_cast<const float4*>(sp.weight + (((int64_t)b * is + yi) * is + x) * 3);
+    const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2];
+    w[0][0] = w0.x; w[0][1] = w0.y; w[0][2] = w0.z; w[1][0] = w0.w; w[1][1] = w1.x; w[1][2] = w1.y;
+    w[2][0] = w1.z; w[2][1] = w1.w; w[2][2] = w2.x; w[3][0] = w2.y; w[3][1] = w2.z; w[3][2] = w2.w;
+    if (REC) {
+        // per-pixel records of the forward: the winner's vertex ids next to its sampling weights -- every load
+        // of the pixel group is in flight at once, no index -> vertex chain
+        const int4* vq = reinterpret_cast<const int4*>(sp.vid_map + (((int64_t)b * is + yi) * is + x) * 3);
+        const int4 v0 = vq[0], v1 = vq[1], v2 = vq[2];
+        vid[0][0] = v0.x; vid[0][1] = v0.y; vid[0][2] = v0.z; vid[1][0] = v0.w; vid[1][1] = v1.x; vid[1][2] = v1.y;
+        vid[2][0] = v1.z; vid[2][1] = v1.w; vid[2][2] = v2.x; vid[3][0] = v2.y; vid[3][1] = v2.z; vid[3][2] = v2.w;
+    } else {
+        const float4 d4 = *reinterpret_cast<const float4*>(sp.depth + ((int64_t)b * is + (is - 1 - yi)) * is + x);
+        zp[0] = d4.x; zp[1] = d4.y; zp[2] = d4.z; zp[3] = d4.w;
+    }
+}
+
+// The body of the eight scatter kernels, phase by phase: 1. the workgroup's image and its list of covered tiles (WORK: a share
+// of the forward's list; else the listing into LDS), 2. the image's coefficient (UNIT), 3. the bound of the gradients (pass 1:
+// the caller's, the coefficient's, or a pass over the tiles -- PAIR: which forms the gradients on the way), 4. the scale of the
+// fixed point, 5. the additions into the table (pass 2), 6. the flush.  Every barrier and fence is in this function.
 template <bool FLOWGRAD, bool REC, bool PAIR, bool UNIT = false, bool WORK = false, PairCrit CRIT = PairCrit::L1>
 __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp) {
     extern __shared__ long long vtab[];  // [V * NCH] rounded up to an even count
@@ -826,7 +940,7 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     const int is = p.is;
     const int T = sp.tiles_x * sp.tiles_y;
     int n_hits = 0;
-    // WORK: the table is zeroed FIRST (it needs nothing but V), so that the barrier behind it can wait where the first LDS
+    // 1. WORK: the table is zeroed FIRST (it needs nothing but V), so that the barrier behind it can wait where the first LDS
     // atomic is about to be issued -- behind the tile's loads instead of in front of them
     if constexpr (WORK)
         for (int k = threadIdx.x; k < (p.V * NCH + 1) >> 1; k += blockDim.x) reinterpret_cast<int4*>(vtab)[k] = make_int4(0, 0, 0, 0);
@@ -834,20 +948,22 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     int t_first = 0;
     auto tile_at = [&](int h) -> int { return WORK ? (h == wave ? t_first : (int)cov_b[h]) : (int)hits[h]; };
     if constexpr (WORK) {
-        // WORK (round 5): the launch's workgroups are handed out over the images IN PROPORTION TO THEIR COVERED TILES.  With a
+        // The launch's workgroups are handed out over the images IN PROPORTION TO THEIR COVERED TILES.  With a
         // fixed number per image the images that cover more than G x ST_WAVES tiles need a second round of their waves while
         // the waves of the others idle: on the bench scene (45 covered tiles per image on average, 8 x 8 waves) a third of the
         // workgroups ran two rounds and the launch ended at 18.8 us with the average workgroup done at 12.5
         // (profiles/r05_bwd_timeline_before.txt).  Every wave derives the split from the per-image counts the forward's
         // finalize launch left: q = tiles per workgroup (at least one per wave) such that sum ceil(n_b / q) fits the grid,
         // image b gets ceil(n_b / q) workgroups sharing its n_b tiles evenly, and the workgroups in use are spread over the
-        // logical index range so that every XCD gets the same share.  No listing pass, no LDS list.
+        // logical index range so that every XCD gets the same share.  No listing pass, no LDS list.  (The scalar arithmetic of
+        // the split is launch_plan.hpp's, st_parts ... st_share, shared with the host test; the sums over the images are wave
+        // scans and stay here.)
         const int B2 = p.B, grid = (int)gridDim.x;
         const int* ncov = sp.work.n_cov;
         // (every quantity below is the same in all lanes: readlane keeps it in scalar registers; the scans are DPP row shifts,
         // six vector instructions each, no LDS crossbar)
         // First try: one tile per wave (q = ST_WAVES) -- it fits whenever the scene leaves the grid some room, and then ONE pass
-        // over the counts gives everything; else q = ceil(N / room) and a second pass.  The counts of the first 4 x 64 images
+        // over the counts gives everything; else st_second_q and a second pass.  The counts of the first 4 x 64 images
         // are requested TOGETHER and stay in registers for all passes (one round trip; further images: read again, from L1).
         constexpr int NC = 4;
         int nreg[NC];
@@ -858,37 +974,33 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
         for (int i = 0; i < NC; i++) {
             if (i * MR_WAVE >= B2) break;
             N += __builtin_amdgcn_readlane(wave_incl_sum(nreg[i], lane), MR_WAVE - 1);
-            used += __builtin_amdgcn_readlane(wave_incl_sum((nreg[i] + ST_WAVES - 1) / ST_WAVES, lane), MR_WAVE - 1);
+            used += __builtin_amdgcn_readlane(wave_incl_sum(st_parts(nreg[i], ST_WAVES), lane), MR_WAVE - 1);
         }
         for (int c = NC * MR_WAVE; c < B2; c += MR_WAVE) {
             const int n = c + lane < B2 ? ncov[c + lane] : 0;
             N += __builtin_amdgcn_readlane(wave_incl_sum(n, lane), MR_WAVE - 1);
-            used += __builtin_amdgcn_readlane(wave_incl_sum((n + ST_WAVES - 1) / ST_WAVES, lane), MR_WAVE - 1);
+            used += __builtin_amdgcn_readlane(wave_incl_sum(st_parts(n, ST_WAVES), lane), MR_WAVE - 1);
         }
         if (used > grid) {
-            const int room = max(grid - B2, 1);  // (sum ceil(n_b / q) <= N / q + B2)
-            q = max(ST_WAVES, (N + room - 1) / room);
+            q = st_second_q(N, grid, B2);
             used = 0;
 #pragma unroll
             for (int i = 0; i < NC; i++) {
                 if (i * MR_WAVE >= B2) break;
-                used += __builtin_amdgcn_readlane(wave_incl_sum((nreg[i] + q - 1) / q, lane), MR_WAVE - 1);
+                used += __builtin_amdgcn_readlane(wave_incl_sum(st_parts(nreg[i], q), lane), MR_WAVE - 1);
             }
             for (int c = NC * MR_WAVE; c < B2; c += MR_WAVE) {
                 const int n = c + lane < B2 ? ncov[c + lane] : 0;
-                used += __builtin_amdgcn_readlane(wave_incl_sum((n + q - 1) / q, lane), MR_WAVE - 1);
+                used += __builtin_amdgcn_readlane(wave_incl_sum(st_parts(n, q), lane), MR_WAVE - 1);
             }
-            if (used > grid) used = grid;  // (grid <= images: cannot be; the surplus images would go without a gradient)
+            used = st_used(used, grid);
         }
-        // logical index -> slot k of the `used` workgroups with work.  xcd_remap gave XCD x the logical indices [x grid / 8,
-        // (x + 1) grid / 8): it takes the slots [x used / 8, (x + 1) used / 8) with the first of them -- every XCD the same share
-        // of the work, images in list order (as the forward's tile list hands them to the XCDs), divisions by 8 only
+        // logical index -> slot k of the `used` workgroups with work, every XCD the same share of them (st_slot)
         int k;
         if ((grid & 7) == 0) {
-            const int per = grid >> 3, x = (int)lidx / per, j = (int)lidx - x * per;
-            const int k0 = (int)(((long long)x * used) >> 3), k1 = (int)(((long long)(x + 1) * used) >> 3);
-            if (j >= k1 - k0) return;
-            k = k0 + j;
+            const StSlot sl = st_slot((int)lidx, grid, used);
+            if (sl.j >= sl.n) return;
+            k = sl.k0 + sl.j;
         } else {
             if ((int)lidx >= used) return;
             k = (int)lidx;
@@ -899,7 +1011,7 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
             const int ci = c / MR_WAVE;
             const int n = ci == 0 ? nreg[0] : ci == 1 ? nreg[1] : ci == 2 ? nreg[2] : ci == 3 ? nreg[3]
                                                                                          : (c + lane < B2 ? ncov[c + lane] : 0);
-            const int parts = (n + q - 1) / q;
+            const int parts = st_parts(n, q);
             const int incl = wave_incl_sum(parts, lane);
             const unsigned long long mine = __ballot(k >= base + incl - parts && k < base + incl);
             if (mine != 0ull) {
@@ -913,10 +1025,9 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
         }
         if (b < 0) return;  // (cannot happen: k < used)
         // this workgroup's share of the image's list: tiles [first, first + n_hits); its waves take them round-robin
-        const int each = nb / pb, rem = nb % pb;
-        const int first = part * each + min(part, rem);
-        n_hits = each + (part < rem ? 1 : 0);
-        cov_b = sp.work.cov + (int64_t)b * T + first;
+        const StShare sh = st_share(nb, pb, part);
+        n_hits = sh.n;
+        cov_b = sp.work.cov + (int64_t)b * T + sh.first;
         part = 0; G = 1;
         // (the wave's first tile id is requested now: its round trip runs beside the image's scalars and the table zeroing)
         t_first = wave < n_hits ? (int)cov_b[wave] : 0;
@@ -926,24 +1037,17 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     const float* verts_b = p.verts + (int64_t)b * p.V * 3;
     const int32_t* fidx_b = p.fidx + (int64_t)b * p.F0 * 3;
 
-    // UNIT: the image's scalars (count, incoming loss gradient, bound of the unit gradient) are requested NOW, in front of
-    // the coverage words, not behind the list they do not depend on (one cold round trip less on the workgroup's chain)
-    float u_cnt = 1.0f, u_gl = 0.0f, u_max = 0.0f;
-    if constexpr (UNIT) {
-        const int dir = b >= sp.split ? 1 : 0, pb = b - dir * sp.split;
-        const float* gl = dir ? sp.gl_fwd : sp.gl_bwd;
-        u_cnt = sp.sums[pb * 4 + (dir ? 1 : 3)];
-        u_gl = gl ? gl[pb] : 0.0f;
-        if (sp.gl_sum) u_gl += sp.gl_sum[pb];
-        if (sp.gl_mean && (dir || !sp.mean_of)) u_gl += sp.gl_mean[0] / sp.mean_div;
-        u_max = sp.unit_max[b];
-    }
-    // the list of covered tiles (block-wide compaction of the coverage bytes); the waves that share an image then take
-    // them round-robin: every wave gets its share whatever part of the screen the mesh sits in.  (All coverage words
+    // 2. UNIT: the image's scalars are requested NOW, in front of the coverage words, not behind the list they do not depend
+    // on (one cold round trip less on the workgroup's chain); the coefficient is formed from them in 3.
+    StUnit unit{1.0f, 0.0f, 0.0f};
+    if constexpr (UNIT) st_unit_scalars(sp, b, unit);
+    // 1. !WORK: the list of covered tiles (block-wide compaction of the coverage bytes); the waves that share an image then
+    // take them round-robin: every wave gets its share whatever part of the screen the mesh sits in.  (All coverage words
     // requested up front and compacted behind one barrier -- eight predicated rounds unrolled -- measured SLOWER than
     // this loop at 1024 tiles per image: 1.98 against 1.54 us.)
     __shared__ int wcnt[ST_WAVES];
-    for (int t0 = 0; t0 < T && !WORK; t0 += blockDim.x) {
+    if constexpr (!WORK)
+    for (int t0 = 0; t0 < T; t0 += blockDim.x) {
         const int t = t0 + threadIdx.x;
         const bool hit = t < T && (sp.tile_hit ? sp.tile_hit[(int64_t)b * T + t] != 0u : true);
         const unsigned long long m = __ballot(hit);
@@ -957,69 +1061,19 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     }
 
     if (part * ST_WAVES >= n_hits) return;  // fewer covered tiles than waves before this workgroup: nothing to do
-    const int n2 = (p.V * NCH + 1) >> 1;
-    for (int k = threadIdx.x; k < n2 && !WORK; k += blockDim.x) reinterpret_cast<int4*>(vtab)[k] = make_int4(0, 0, 0, 0);
+    if constexpr (!WORK) {
+        const int n2 = (p.V * NCH + 1) >> 1;
+        for (int k = threadIdx.x; k < n2; k += blockDim.x) reinterpret_cast<int4*>(vtab)[k] = make_int4(0, 0, 0, 0);
+    }
 
-    // pass 1: largest |gradient| over the workgroup's covered tiles, as float bits -- or the caller's bound for the image
+    // 3. pass 1: largest |gradient| over the workgroup's covered tiles, as float bits -- or the caller's bound for the image
     unsigned mx = 0u;
     const bool bounded = PAIR || UNIT || (FLOWGRAD && sp.grad_bound != nullptr);
     if (bounded && !PAIR && !UNIT) mx = __float_as_uint(sp.grad_bound[b]) & 0x7fffffffu;
     float ucoef = 0.0f;
-    if constexpr (UNIT) {
-        // the image's coefficient (pair_consist_backward_tiles_kernel's): every gradient of the image is unit * ucoef, and
-        // |unit| <= unit_max rounds to at most fl(unit_max * |ucoef|) (rounding is monotone): the bound of the fixed point.
-        // A zero coefficient leaves the image without a gradient whatever the unit gradient holds.
-        const float* gl = (b >= sp.split) ? sp.gl_fwd : sp.gl_bwd;
-        ucoef = (gl || sp.gl_sum || sp.gl_mean) ? u_gl / ((u_cnt == 0.0f) ? 1.0f : u_cnt) : 0.0f;
-        if (ucoef != 0.0f) mx = __float_as_uint(u_max * ucoef) & 0x7fffffffu;
-    }
+    if constexpr (UNIT) ucoef = st_unit_coef(sp, b, unit, mx);
     if constexpr (PAIR) {
-        // ... PAIR: the pair loss's backward for the workgroup's tiles (pair_consist_backward_tiles_kernel's arithmetic, one
-        // pixel per thread, two tiles at a time), times the epilogue masks as st_load_grad forms them, into the stash;
-        // the maximum comes out on the way.  A final flow with a zero x component (everything the masks or the
-        // occlusion check removed) has a zero gradient: no taps.
-        const int rem1 = n_hits - part * ST_WAVES;
-        const int n_mine = (rem1 / (G * ST_WAVES)) * ST_WAVES + min(rem1 % (G * ST_WAVES), ST_WAVES);
-        const int half = threadIdx.x >> 8, tid = threadIdx.x & 255;
-        const int dir = b >= sp.split ? 1 : 0, pb = b - dir * sp.split;
-        const float cnt = sp.sums[pb * 4 + (dir ? 1 : 3)];
-        const float* gl = dir ? sp.gl_fwd : sp.gl_bwd;
-        const float coef = gl ? gl[pb] / ((cnt == 0.0f) ? 1.0f : cnt) : 0.0f;
-        const float* src = dir ? sp.image_ref : sp.image;
-        const float* tgt = dir ? sp.image : sp.image_ref;
-        const float* jit = dir ? sp.jitter : sp.jitter_ref;
-        const int64_t hw_img = (int64_t)sp.H * sp.W;
-        for (int m = half; m < n_mine; m += 2) {
-            const int t = tile_at(part * ST_WAVES + (m % ST_WAVES) + (m / ST_WAVES) * G * ST_WAVES);
-            const int x = (t % sp.tiles_x) * ST_TW + (tid & 31), ry = (t / sp.tiles_x) * ST_TH + (tid >> 5);
-            const int y = is - 1 - ry;
-            if (x >= sp.W || ry >= is || y >= sp.H) continue;
-            const int64_t pixc = (int64_t)y * sp.W + x;
-            float2 gq = make_float2(0.0f, 0.0f);
-            // the coverage word, the flow and the epilogue masks of the pixel are requested TOGETHER (all inside their
-            // allocations; what an uncovered row pair holds there is never used): the taps are the only dependent trip
-            const uint32_t word = sp.tile_hit[(int64_t)b * T + t];
-            const int64_t o = ((int64_t)b * is + y) * is + x;
-            float2 uv = *reinterpret_cast<const float2*>(sp.flow + ((int64_t)b * hw_img + pixc) * 2);
-            float a = sp.m_pre[o];
-            float mxo = (b < sp.split ? sp.m_x_lo[o] : sp.m_x_hi[o - (int64_t)sp.split * is * is]), oc = sp.occl[o];
-            pin(uv.x); pin(uv.y); pin(a); pin(mxo); pin(oc);
-            if (coef != 0.0f && ((word >> (8 * ((ry & 7) >> 1))) & 0xffu) != 0u) {
-                if (uv.x != 0.0f) {
-                    const float post = mxo * oc;
-                    const DirTaps tp = pair_taps(uv, x, y, sp.H, sp.W);
-                    DirRaw2 q{};
-                    pair_load(tp, src, tgt, jit, jit, sp.Cj, false, pb, pixc, hw_img, q);
-                    pin(q);
-                    const DirRaw r = unpack(q, tp.a);
-                    const DirOut e = pair_eval(tp, r, sp.H, sp.W, sp.pair_thresh, false);
-                    const float2 gp = pair_grad<CRIT>(tp, r, e, sp.H, sp.W, coef);
-                    gq = make_float2((gp.x * post) * a, (gp.y * post) * a);
-                }
-            }
-            *reinterpret_cast<float2*>(sp.stash + ((int64_t)b * hw_img + pixc) * 2) = gq;
-            mx = max(mx, max(__float_as_uint(gq.x) & 0x7fffffffu, __float_as_uint(gq.y) & 0x7fffffffu));
-        }
+        st_pair_pass1<WORK, CRIT>(sp, b, part, G, n_hits, T, tile_at, mx);
         __threadfence_block();  // the stash is read back by other waves of this workgroup after the barrier below
     }
     for (int h = part * ST_WAVES + wave; h < n_hits && !bounded; h += G * ST_WAVES) {
@@ -1048,16 +1102,9 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     }
     if (bm == 0u) return;                  // every gradient is +-0: nothing to add (block-uniform)
     const bool finite = bm < 0x7f800000u;  // else: fp32 global atomics, Inf / NaN propagate
-    // A table cell receives at most 3 terms per pixel (a face may name one vertex three times) of every tile this
-    // workgroup walks, each below 2^ST_FIX_BITS in magnitude: 2^13 of them fit the 51-bit field of the sums.  A workgroup
-    // with more (beyond ten covered tiles: large rasters, screen-filling meshes) gives up one bit of the 37 per doubling
-    // -- at 256 tiles per workgroup that is still 2^-32 of the largest gradient per term.
-    const int rem = n_hits - part * ST_WAVES;
-    const long long terms = 3LL * ST_TW * ST_TH * ((rem / (G * ST_WAVES)) * ST_WAVES + min(rem % (G * ST_WAVES), ST_WAVES));
-    int headroom = 0;
-    while ((terms >> headroom) >= (1LL << (ST_SUM_BITS - ST_FIX_BITS))) headroom++;
-    const int shift = ST_FIX_BITS - headroom - ((int)(bm >> 23) - 126);
-    // Round 5: float -> fixed point by the "magic number" addition, two double-precision instructions per value instead of
+    // 4. the scale: terms below 2^ST_FIX_BITS, one bit less per doubling of the workgroup's terms beyond 2^13 (launch_plan.hpp)
+    const int shift = st_shift(st_headroom(st_terms(n_hits, part, G)), bm);
+    // float -> fixed point by the "magic number" addition, two double-precision instructions per value instead of
     // eight (cvt, ldexp, trunc, ldexp, floor, fma, two conversions: the main pass was bound by them -- 24 values per lane, 8
     // waves per SIMD): v 2^shift + 1.5 x 2^52, rounded to an integer by that very addition, has v's fixed-point value in two's
     // complement in the low 51 bits of its mantissa field and a CONSTANT above them; the raw bit patterns are summed by the
@@ -1066,9 +1113,9 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
     const double fix_scale = ldexp(1.0, shift);
     float* out = p.grad_vcolors + (int64_t)b * p.V * 3;
 
-    // pass 2
+    // 5. pass 2
     // (WORK: every wave takes a FIRST trip, with or without a tile -- the workgroup's barrier sits inside it, at ONE place for
-    // all waves; rounds 5's form had the waves without a tile meet the others at a second barrier behind the loop)
+    // all waves)
     for (int h = part * ST_WAVES + wave, trip = 0; h < n_hits || (WORK && trip == 0); h += G * ST_WAVES, trip++) {
         const bool live = h < n_hits;
         const int t = live ? tile_at(h) : 0;
@@ -1089,19 +1136,9 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
             for (int k = 0; k < 3; k++) { g[j][k] = 0.0f; w[j][k] = 0.0f; }
         }
         if (inside) {
-            st_load_grad<FLOWGRAD, PAIR, UNIT>(sp, b, yi, x, g, ucoef);
-            const float4* wq = reinterpret_cast<const float4*>(sp.weight + (((int64_t)b * is + yi) * is + x) * 3);
-            const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2];
-            w[0][0] = w0.x; w[0][1] = w0.y; w[0][2] = w0.z; w[1][0] = w0.w; w[1][1] = w1.x; w[1][2] = w1.y;
-            w[2][0] = w1.z; w[2][1] = w1.w; w[2][2] = w2.x; w[3][0] = w2.y; w[3][1] = w2.z; w[3][2] = w2.w;
+            st_tile_loads<FLOWGRAD, REC, PAIR, UNIT>(sp, b, yi, x, ucoef, g, w, vid, zp);
             if (REC) {
-                // per-pixel records of the forward: the winner's vertex ids next to its sampling weights -- every load
-                // of the pixel group is in flight at once, no index -> vertex chain
-                const int4* vq = reinterpret_cast<const int4*>(sp.vid_map + (((int64_t)b * is + yi) * is + x) * 3);
-                const int4 v0 = vq[0], v1 = vq[1], v2 = vq[2];
-                vid[0][0] = v0.x; vid[0][1] = v0.y; vid[0][2] = v0.z; vid[1][0] = v0.w; vid[1][1] = v1.x; vid[1][2] = v1.y;
-                vid[2][0] = v1.z; vid[2][1] = v1.w; vid[2][2] = v2.x; vid[3][0] = v2.y; vid[3][1] = v2.z; vid[3][2] = v2.w;
-                // Round 5: the three (vertex, weight) pairs of a pixel are ROTATED by the lane's row in the tile (mod 3).  A
+                // The three (vertex, weight) pairs of a pixel are ROTATED by the lane's row in the tile (mod 3).  A
                 // face spans three or four rows, so the lanes above one another hold the same three vertex ids, and the LDS
                 // atomics of step k below all hit the same table cell -- 65 % of this kernel's LDS-active cycles were such
                 // collisions (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, profiles/r05_pmc_summary.txt), the LDS pipe the
@@ -1125,9 +1162,6 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
                     w[j][1] = rot == 0 ? b1 : (rot == 1 ? b2 : b0);
                     w[j][2] = rot == 0 ? b2 : (rot == 1 ? b0 : b1);
                 }
-            } else {
-                const float4 d4 = *reinterpret_cast<const float4*>(sp.depth + ((int64_t)b * is + (is - 1 - yi)) * is + x);
-                zp[0] = d4.x; zp[1] = d4.y; zp[2] = d4.z; zp[3] = d4.w;
             }
         }
         if (!REC) {
@@ -1144,7 +1178,7 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
 #pragma unroll
                 for (int k = 0; k < 3; k++) vz[j][k] = fn[j] >= 0 ? verts_b[(int64_t)vid[j][k] * 3 + 2] : 1.0f;
         }
-        // (Measured and dropped in round 5: forming the fixed-point value from the float's bits with 64-bit integer shifts
+        // (Measured and dropped: forming the fixed-point value from the float's bits with 64-bit integer shifts
         // instead of the double-precision ldexp + conversion -- main pass 5.2 -> 7.6 us per workgroup, the 64-bit shifts and
         // selects are slower than the conversion sequence; summing a lane's consecutive pixels of one face in registers
         // before the LDS atomic -- exact, a third fewer atomics, but 54 -> 82 vector registers: three workgroups per compute
@@ -1201,15 +1235,10 @@ __device__ __forceinline__ void scatter_tiles_body(const ScatterTilesParams& sp)
         };
         if (finite) add_all(std::true_type{}); else add_all(std::false_type{});
     }
+    // 6. the flush
     if (!finite) return;  // block-uniform
     __syncthreads();
-    for (int k = threadIdx.x; k < p.V * NCH; k += blockDim.x) {
-        const long long tsum = (long long)((unsigned long long)vtab[k] << (64 - ST_SUM_BITS - 1)) >> (64 - ST_SUM_BITS - 1);
-        if (tsum != 0) {
-            const float v = (float)ldexp((double)tsum, -shift);
-            if (v != 0.0f) atomicAdd(&out[(k / NCH) * 3 + k % NCH], v);
-        }
-    }
+    st_flush<NCH>(vtab, p.V, shift, out);
 }
 
 template <bool FLOWGRAD, bool REC>

@@ -482,8 +482,8 @@ __device__ __forceinline__ void pair_consist_backward_body(const PairBwdParams& 
         return;
     }
     const float c1 = p.sums[b * 4 + 1], c2 = p.sums[b * 4 + 3];
-    const float coef1 = p.grad_loss_fwd[b] / ((c1 == 0.0f) ? 1.0f : c1);
-    const float coef2 = p.grad_loss_bwd ? p.grad_loss_bwd[b] / ((c2 == 0.0f) ? 1.0f : c2) : 0.0f;
+    const float coef1 = pair_coef(p.grad_loss_fwd[b], c1);
+    const float coef2 = p.grad_loss_bwd ? pair_coef(p.grad_loss_bwd[b], c2) : 0.0f;
     const bool both = p.grad_loss_bwd != nullptr;
     const float2 uv1 = pair_flow(p.flow21, p.hit21, p.hit_is, p.hit_tiles_x, p.hit_stride, b, xx, yy, p.H, p.W);
     const float2 uv2 = both ? pair_flow(p.flow12, p.hit12, p.hit_is, p.hit_tiles_x, p.hit_stride, b, xx, yy, p.H, p.W) : uv1;
@@ -510,8 +510,8 @@ __device__ __forceinline__ void pair_consist_backward_body(const PairBwdParams& 
     }
     *reinterpret_cast<float2*>(p.grad_flow21 + ((int64_t)b * hw + pix) * 2) = g21;
     *reinterpret_cast<float2*>(p.grad_flow12 + ((int64_t)b * hw + pix) * 2) = g12;
-    u12 = max(__float_as_uint(g12.x) & 0x7fffffffu, __float_as_uint(g12.y) & 0x7fffffffu);
-    u21 = max(__float_as_uint(g21.x) & 0x7fffffffu, __float_as_uint(g21.y) & 0x7fffffffu);
+    u12 = abs_bits_max(g12);
+    u21 = abs_bits_max(g21);
     }();
     // the largest |gradient| per image and direction, for the consumer of these gradients that scales them into fixed
     // point (mr_render_flow_backward's grad_bound: it saves that kernel a pass over its inputs).  Wave maximum at a
@@ -649,15 +649,10 @@ __device__ __forceinline__ void pair_consist_forward_tiles_body(const PairTilesP
             // a pixel whose flow has a zero x component is invalid whatever the images hold (imgflowarp.py:93-100)
             if (uv.x != 0.0f) {
                 const PairDir d = pair_dir(p, t.dir);
-                const DirTaps tp = pair_taps(uv, t.x, t.y, p.H, p.W);
-                DirRaw2 q{};
-                pair_load(tp, d.src, d.tgt, d.jit, d.jit, p.Cj, false, t.b, pix, hw, q);
-                pin(q);
-                const DirRaw r = unpack(q, tp.a);
-                const DirOut e = pair_eval(tp, r, p.H, p.W, p.thresh, false);
-                if (e.valid) {
+                const DirPixel px = pair_pixel(uv, t.x, t.y, p.H, p.W, d.src, d.tgt, d.jit, p.Cj, t.b, pix, hw, p.thresh);
+                if (px.e.valid) {
 #pragma unroll
-                    for (int c = 0; c < 3; c++) sum += pair_term<CRIT>(e.s[c] - r.tgt[c]);
+                    for (int c = 0; c < 3; c++) sum += pair_term<CRIT>(px.e.s[c] - px.r.tgt[c]);
                     cnt = 3.0f;
                 }
             }
@@ -799,7 +794,7 @@ __device__ __forceinline__ void flow_pair_forward_tiles_body(const FlowPairFwdPa
                 }
                 if (GRAD) {
                     *reinterpret_cast<float2*>(q.unit_grad + ((int64_t)t.img * hw_img + pixc) * 2) = gq;
-                    gmx = max(__float_as_uint(gq.x) & 0x7fffffffu, __float_as_uint(gq.y) & 0x7fffffffu);
+                    gmx = abs_bits_max(gq);
                 }
             }
         }
@@ -974,11 +969,12 @@ __device__ __forceinline__ void pair_consist_backward_tiles_body(const PairTiles
             float2 g = make_float2(0.0f, 0.0f);
             const float c = p.sums[t.b * 4 + (t.dir ? 1 : 3)];
             const float* gl = t.dir ? p.grad_loss_fwd : p.grad_loss_bwd;
-            const float coef = gl ? gl[t.b] / ((c == 0.0f) ? 1.0f : c) : 0.0f;
+            const float coef = gl ? pair_coef(gl[t.b], c) : 0.0f;
             if (t.row_covered && coef != 0.0f) {
                 const float2 uv = pair_flow(p.flow[t.dir], t.b, t.x, t.y, p.H, p.W);
                 if (uv.x != 0.0f) {  // the gradient of an invalid pixel is 0 (see the forward kernel)
                     const PairDir d = pair_dir(p, t.dir);
+                    // (pair_pixel's sequence, and abs_bits_max below, spelled out: see pair_pixel)
                     const DirTaps tp = pair_taps(uv, t.x, t.y, p.H, p.W);
                     DirRaw2 q{};
                     pair_load(tp, d.src, d.tgt, d.jit, d.jit, p.Cj, false, t.b, pix, hw, q);

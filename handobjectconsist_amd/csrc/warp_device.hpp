@@ -625,6 +625,37 @@ __device__ __forceinline__ float2 pair_grad(const DirTaps& d, const DirRaw& r, c
     return make_float2(gu, gv);
 }
 
+// One direction at a pixel whose flow is known, start to end: taps, every load of the pixel in flight before anything waits,
+// masks and warped values.  The listed forward sums over it; the listed backward and the scatter's pass 1 keep the same five
+// calls spelled out: through this function their kernels compile to one or two instructions more or fewer
+// (profiles/scatter_phases_isa.txt).
+struct DirPixel {
+    DirTaps tp;
+    DirRaw r;
+    DirOut e;
+};
+__device__ __forceinline__ DirPixel pair_pixel(float2 uv, int xx, int yy, int H, int W, const float* __restrict__ src,
+                                               const float* __restrict__ tgt, const float* __restrict__ jit, int Cj, int b, int64_t pix,
+                                               int64_t hw, float thresh) {
+    DirPixel d;
+    d.tp = pair_taps(uv, xx, yy, H, W);
+    DirRaw2 q{};
+    pair_load(d.tp, src, tgt, jit, jit, Cj, false, b, pix, hw, q);
+    pin(q);
+    d.r = unpack(q, d.tp.a);
+    d.e = pair_eval(d.tp, d.r, H, W, thresh, false);
+    return d;
+}
+
+// an image's coefficient of the pair loss's gradient: the incoming gradient of its loss over its count of valid terms (the
+// loss is sum / count, an image without a valid pixel: sum / 1); a direction without an incoming gradient has none
+__device__ __forceinline__ float pair_coef(float gl, float cnt) { return gl / ((cnt == 0.0f) ? 1.0f : cnt); }
+
+// the larger |component| of a gradient as float bits (NaN > Inf > finite: a plain unsigned maximum orders them)
+__device__ __forceinline__ unsigned abs_bits_max(float2 g) {
+    return max(__float_as_uint(g.x) & 0x7fffffffu, __float_as_uint(g.y) & 0x7fffffffu);
+}
+
 // ---------------------------------------------------------------------------------------
 // listed launches: a workgroup's tile of the stacked render's tile list (see warp.hip, "Listed launches")
 // ---------------------------------------------------------------------------------------

@@ -20,21 +20,12 @@ using namespace mr;
 // input rows:  B2 V is n_0 ... n_(B2-1)
 // output rows: groups=<plan's workgroups per image> grid= q= used= per_image=<workgroups of image 0,1,..> wgs=<image.tiles.terms.headroom;...> max_headroom=
 //
-// Restated from raster_bwd.hip (scatter_tiles_body; constants beside it):
-//   constexpr int ST_FIX_BITS = 37, ST_SUM_BITS = 50;
-// the WORK split -- q tiles per workgroup, at least one per wave, such that sum ceil(n_b / q) fits the grid:
-//   int q = ST_WAVES, used = 0, N = 0;   ... N += n_b; used += (n_b + ST_WAVES - 1) / ST_WAVES;
-//   if (used > grid) { const int room = max(grid - B2, 1); q = max(ST_WAVES, (N + room - 1) / room); used = sum (n_b + q - 1) / q;
-//                      if (used > grid) used = grid; }
-//   const int parts = (n + q - 1) / q;   (image b takes slots [base, base + parts) of the `used` slots; every slot below `used`
-//                                         is taken by one workgroup: the XCD shares [x used / 8, (x + 1) used / 8) tile [0, used))
-//   const int each = nb / pb, rem = nb % pb;   n_hits = each + (part < rem ? 1 : 0);   part = 0; G = 1;
-// and the three lines in front of pass 2:
-//   const int rem = n_hits - part * ST_WAVES;
-//   const long long terms = 3LL * ST_TW * ST_TH * ((rem / (G * ST_WAVES)) * ST_WAVES + min(rem % (G * ST_WAVES), ST_WAVES));
-//   int headroom = 0;   while ((terms >> headroom) >= (1LL << (ST_SUM_BITS - ST_FIX_BITS))) headroom++;
+// Every figure comes from the functions the kernel itself calls (launch_plan.hpp: st_parts, st_second_q, st_used, st_share,
+// st_terms, st_headroom); what is written out here is only the kernel's sums over the images, which it does with wave scans, and
+// the walk over the workgroups: image b takes slots [base, base + parts) of the `used` slots, every slot below `used` is taken by
+// one workgroup (the XCD shares [x used / 8, (x + 1) used / 8) tile [0, used): st_slot, checked for every row), and a workgroup
+// walks its share as part 0 of 1.
 static int scatter_cases() {
-    constexpr int FIX_BITS = 37, SUM_BITS = 50;
     int B2, V, is;
     while (std::scanf("%d %d %d", &B2, &V, &is) == 3) {
         if (B2 <= 0 || B2 > 4096) return 1;
@@ -47,29 +38,33 @@ static int scatter_cases() {
         int q = ST_WAVES, used = 0, N = 0;
         for (int n : ncov) {
             if (n > T) return 1;
-            N += n; used += (n + ST_WAVES - 1) / ST_WAVES;
+            N += n; used += st_parts(n, ST_WAVES);
         }
         if (used > grid) {
-            const int room = std::max(grid - B2, 1);
-            q = std::max(ST_WAVES, (N + room - 1) / room);
+            q = st_second_q(N, grid, B2);
             used = 0;
-            for (int n : ncov) used += (n + q - 1) / q;
-            if (used > grid) used = grid;
+            for (int n : ncov) used += st_parts(n, q);
+            used = st_used(used, grid);
         }
+        // (the walk below relies on it: the logical indices of the grid take every slot below `used` exactly once -- a grid that
+        // is a multiple of 8 through st_slot, as the kernel does)
+        std::vector<int> taken(used, 0);
+        for (int l = 0; l < grid; l++) {
+            const StSlot sl = (grid & 7) == 0 ? st_slot(l, grid, used) : StSlot{0, l, used};
+            if (sl.j < sl.n && (sl.k0 + sl.j < 0 || sl.k0 + sl.j >= used || taken[sl.k0 + sl.j]++ != 0)) return 1;
+        }
+        if (std::count(taken.begin(), taken.end(), 1) != used) return 1;
         std::printf("status=0 groups=%d grid=%d q=%d used=%d per_image=", s.groups, grid, q, used);
-        for (int b = 0; b < B2; b++) std::printf("%s%d", b ? "," : "", (ncov[b] + q - 1) / q);
+        for (int b = 0; b < B2; b++) std::printf("%s%d", b ? "," : "", st_parts(ncov[b], q));
         std::printf(" wgs=");
         int base = 0, max_headroom = 0;
         bool first = true;
         for (int b = 0; b < B2; b++) {
-            const int nb = ncov[b], pb = (nb + q - 1) / q;
+            const int nb = ncov[b], pb = st_parts(nb, q);
             for (int part = 0; part < pb && base + part < used; part++) {
-                const int each = nb / pb, rem_b = nb % pb;
-                const int n_hits = each + (part < rem_b ? 1 : 0);
-                const int G = 1, rem = n_hits;  // (part = 0; G = 1)
-                const long long terms = 3LL * ST_TW * ST_TH * ((rem / (G * ST_WAVES)) * ST_WAVES + std::min(rem % (G * ST_WAVES), ST_WAVES));
-                int headroom = 0;
-                while ((terms >> headroom) >= (1LL << (SUM_BITS - FIX_BITS))) headroom++;
+                const int n_hits = st_share(nb, pb, part).n;
+                const long long terms = st_terms(n_hits, 0, 1);
+                const int headroom = st_headroom(terms);
                 std::printf("%s%d.%d.%lld.%d", first ? "" : ";", b, n_hits, terms, headroom);
                 first = false;
                 max_headroom = std::max(max_headroom, headroom);

@@ -9,8 +9,9 @@ per-pixel gradient of ``W.pair_consist_grad`` -- one fp32 rounding of ``coeffici
 2^-23 relative per term, summed in float64 -- so 1e-6 of the sample's largest gradient (a tenth of the rule's absolute term,
 some eight times 2^-23) bounds it with room for cancellation between a vertex's pixels.
 
-Headroom.  tests/host/launch_plan_cases.cpp (``scatter``) restates how ``unit_scatter_tiles_kernel`` hands an image's covered
-tiles to workgroups and the ``terms`` / ``headroom`` lines in front of its second pass, on csrc/launch_plan.hpp's own plan.
+Headroom.  tests/host/launch_plan_cases.cpp (``scatter``) calls the functions of csrc/launch_plan.hpp with which
+``unit_scatter_tiles_kernel`` hands an image's covered tiles to workgroups and forms ``terms`` / ``headroom`` in front of its
+second pass (``st_parts``, ``st_second_q``, ``st_used``, ``st_share``, ``st_terms``, ``st_headroom``), on that header's own plan.
 Fed with the oracle's coverage it proves that X1 (raster 132) reaches headroom 1 and X2 (raster 196) headroom 2 in every
 workgroup, for both seeds, that the next smaller rasters the fused path accepts (128, 192) reach one less even when every tile
 is covered, and that NO case of tests/pair_mesh_cases.py, tests/pair_border_cases.py nor the 1 x 480 shape of
