@@ -35,6 +35,8 @@ COLOR_OP_NONE, COLOR_OP_BRIGHTNESS, COLOR_OP_SATURATION, COLOR_OP_HUE, COLOR_OP_
 JPEG_MAGIC, JPEG_HEADER_BYTES = 0x314A524D, 576  # MR_JPEG_*: a packed frame of mr_jpeg_entropy_decode
 # MR_PNG_*: a packed frame of datasets/pngdecode.py; the rows of a band and the largest side of mr_png_unfilter
 PNG_MAGIC, PNG_HEADER_BYTES, PNG_BAND_ROWS, PNG_MAX_SIDE = 0x3150524D, 64, 64, 10752
+EVAL_MAX_JOBS, EVAL_PER_POINT, EVAL_PER_SAMPLE_SUM, EVAL_POINTS, EVAL_MAX_POINTS = 8, 0, 1, 2, 4096  # MR_EVAL_*: the jobs of mr_eval_feed
+EVAL_MAX_THRESHOLDS = 1024  # mr_eval_measures
 MANO_POSE_PCA, MANO_POSE_AXISANG = 0, 1  # MR_MANO_POSE_*: the pose form of mr_mano_forward_full / mr_mano_backward_full
 # (image, mask) pairs the fused pair kernels are instantiated for
 FUSED_BATCH_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.uint8), (torch.bfloat16, torch.float32))
@@ -82,6 +84,11 @@ SIGNATURES = {
     "mr_mano_adapt_workspace_floats": (_I, [_I, _I]),
     "mr_mano_adapt_forward": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "mr_mano_adapt_backward": (_I, [_P, _P, _I] + [_P] * 5 + [_I, _I, _I, _P]),
+    # the training metrics (csrc/eval_metrics.hip): additions to ABI 9
+    "mr_eval_job_layout": (_I, [_P, _I]),
+    "mr_eval_feed": (_I, [_P, _I, _I, _P]),
+    "mr_eval_measures_workspace_floats": (_I, [_I, _I, _I]),
+    "mr_eval_measures": (_I, [_P, _I, _I, _P, _I] + [_P] * 5 + [_P]),
     "mr_warp_forward": (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_warp_backward": (_I, [_P] * 5 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_occlusion_mask": (_I, [_P] * 4 + [_L, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),

@@ -22,6 +22,17 @@ PATH_KEYS = {
     "objfaces": BaseQueries.OBJFACES,
     "objverts3d": BaseQueries.OBJVERTS3D,
     "handverts3d": BaseQueries.HANDVERTS3D,
+    # what netscripts/evaluate.py reads (evaluate.py:33-98 of the reference): ground truth in the dataset's own frame, the
+    # same after the augmentation ("_trans") and the augmentation's affine
+    "joints3d": BaseQueries.JOINTS3D,
+    "joints2d": BaseQueries.JOINTS2D,
+    "objcorners2d": BaseQueries.OBJCORNERS2D,
+    "objverts2d": BaseQueries.OBJVERTS2D,
+    "joints3d_trans": TransQueries.JOINTS3D,
+    "joints2d_trans": TransQueries.JOINTS2D,
+    "objcorners2d_trans": TransQueries.OBJCORNERS2D,
+    "objverts2d_trans": TransQueries.OBJVERTS2D,
+    "affinetrans": TransQueries.AFFINETRANS,
 }
 
 

@@ -1,7 +1,8 @@
 """Training loop over alternating data / consist batches -- counterpart of the hot loop of
-meshreg/netscripts/epochpassconsist.py:56-68 (metric meters, evaluators and figure dumps are
-out of scope).  Loss is accumulated over ``loader_nb`` consecutive batches, then ONE
-``zero_grad / backward / step``: that is the "iteration" of the headline metric.
+meshreg/netscripts/epochpassconsist.py:56-68 (figure dumps are out of scope; the metric meters
+and evaluators of :34-51 / :69-84 are ``netscripts.evaluate.TrainMetrics``, passed as ``metrics``).
+Loss is accumulated over ``loader_nb`` consecutive batches, then ONE ``zero_grad / backward /
+step``: that is the "iteration" of the headline metric.
 """
 import os
 
@@ -41,7 +42,7 @@ def raise_pending_nan(optimizer):
             raise ValueError("Loss became nan! (the step's parameter update was skipped on the device)")
 
 
-def train_step(batches, premodel, optimizer, check_nan=True, reducer=None):
+def train_step(batches, premodel, optimizer, check_nan=True, reducer=None, metrics=None):
     """One optimiser step over `loader_nb = len(batches)` batches (epochpassconsist.py:57-68).  With
     ``check_nan`` a NaN loss never reaches the parameters or the optimiser state, as in the reference (:61-63),
     and raises ``ValueError``.  The reference reads the loss on the host before ``backward`` -- a pipeline drain
@@ -59,7 +60,9 @@ def train_step(batches, premodel, optimizer, check_nan=True, reducer=None):
     all-reduces are issued from inside ``backward`` and joined before the optimiser reads the gradients.  The NaN
     flag is then GLOBAL: it rides through the last bucket's all-reduce, so a NaN loss on any rank skips the update
     and raises on every rank in the same step (the replicas stay identical and no rank is left waiting in a
-    collective)."""
+    collective).
+    ``metrics``: a ``netscripts.evaluate.TrainMetrics``, fed after each batch's forward from detached tensors (one launch
+    per fed frame, no host read); None changes nothing."""
     if check_nan:
         raise_pending_nan(optimizer)
     losses, logs = [], {}
@@ -69,6 +72,8 @@ def train_step(batches, premodel, optimizer, check_nan=True, reducer=None):
         for batch in batches:
             loss, all_losses, _results, _pair_results = premodel.forward(batch)
             losses.append(loss.flatten())
+            if metrics is not None:
+                metrics.feed(batch, all_losses, _results)
             # (detached: a log entry that kept its grad_fn would keep this step's autograd graph -- and the parameters'
             # AccumulateGrad nodes, bound to the stream they were created on -- alive in the caller's hands)
             logs.update({k: (v.detach() if torch.is_tensor(v) else v) for k, v in all_losses.items() if v is not None})
@@ -114,13 +119,14 @@ def train_step(batches, premodel, optimizer, check_nan=True, reducer=None):
     return loss.detach(), logs
 
 
-def epoch_pass(loader, premodel, optimizer, loader_nb=2, check_nan=True, reducer=None):
-    """loader yields {"data": [sample, ...], "supervision": "data" | "consist"} dicts."""
+def epoch_pass(loader, premodel, optimizer, loader_nb=2, check_nan=True, reducer=None, metrics=None):
+    """loader yields {"data": [sample, ...], "supervision": "data" | "consist"} dicts.  ``metrics``: see ``train_step``; read
+    it out with ``metrics.save_dict(prefix)`` after the pass."""
     pending, history = [], []
     for batch in loader:
         pending.append(batch)
         if len(pending) == loader_nb:
-            loss, _ = train_step(pending, premodel, optimizer, check_nan=check_nan, reducer=reducer)
+            loss, _ = train_step(pending, premodel, optimizer, check_nan=check_nan, reducer=reducer, metrics=metrics)
             history.append(loss)
             pending = []
     if check_nan:

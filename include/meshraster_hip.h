@@ -508,6 +508,78 @@ MR_API int mr_mano_adapt_backward(const float* verts, const float* weight, int c
                                   int num_verts, int num_joints, mr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * 2b. Training metrics (meshreg/netscripts/evaluate.py, libyana's EvalUtil)
+ * ---------------------------------------------------------------------------------- */
+/* Additions to ABI 9.  mr_eval_feed: the distances one fed frame contributes to its evaluators and
+ * meters, ONE launch for up to MR_EVAL_MAX_JOBS jobs (grid (sample, job), the jobs by value in the
+ * kernel's argument block).  All tensors fp32 and dense.  A job:
+ *   pred[B,K,dims], target[B,K,dims], dims in {2, 3} (a third component of 0 for dims 2)
+ *   affine[B,3,3] or NULL (dims 2 only).  With a = affine[b] row-major, one fp32 operation per operator:
+ *     c00 = a4 a8 - a5 a7   c01 = a2 a7 - a1 a8   c02 = a1 a5 - a2 a4
+ *     c10 = a5 a6 - a3 a8   c11 = a0 a8 - a2 a6   c12 = a2 a3 - a0 a5   c20 = a3 a7 - a4 a6
+ *     det = (a0 c00 + a1 c10) + a2 c20              i_rc = c_rc / det   (IEEE division)
+ *     recover_back(x, y) = ((i00 x + i01 y) + i02, (i10 x + i11 y) + i12)
+ *   applied to every point of pred, or of target when affine_target != 0 (the sanity figure).
+ *   center in {-1, 0..K-1}: cp = pred point `center`, ct = target point `center` (after
+ *   recover_back; zeros for -1).
+ *   d_r = (p_r - cp_r) - (t_r - ct_r)       dist = sqrtf((d0 d0 + d1 d1) + d2 d2)
+ *   mode MR_EVAL_PER_POINT: out[b,k] = dist (K <= 4096).
+ *   mode MR_EVAL_PER_SAMPLE_SUM: out[b] = sum_k dist, any K: thread t of 256 adds k = t, t + 256, ...
+ *   in order, the 64 lanes of a wave meet in a butterfly (xor 32, 16, .. 1), the four waves are added
+ *   in order.
+ *   mode MR_EVAL_POINTS: out[b,k,0..dims) = p - cp, the pred side as it enters the distance
+ *   (recover_back as a function); target is not read and may be NULL, any K.
+ *   `out` points at the row this feed starts at: the host knows every B it has fed, so the device
+ *   keeps no cursor and uses no atomics.
+ * Two calls give the same bits; a sample's rows do not depend on its batch; a singular affine or a NaN
+ * input gives non-finite distances in that sample's rows only.  B == 0 or num_jobs == 0: MR_OK, nothing
+ * launched.  MR_ERR_BADARG before any launch: num_jobs outside 0..8, B < 0, jobs NULL, and per job a
+ * NULL or misaligned pred / target (MR_EVAL_POINTS: target may be NULL) / out, a misaligned affine, dims outside {2, 3}, K < 1, center
+ * outside -1..K-1, an affine with dims 3, an unknown mode, a per-point K > 4096.
+ * mr_eval_job_layout writes sizeof(MrEvalJob) and the offset of every field in declaration order
+ * into out[0..n) and returns how many values there are (11). */
+#define MR_EVAL_MAX_JOBS 8
+#define MR_EVAL_PER_POINT 0
+#define MR_EVAL_PER_SAMPLE_SUM 1
+#define MR_EVAL_POINTS 2
+typedef struct MrEvalJob {
+    const float* pred;
+    const float* target;
+    const float* affine;
+    float* out;
+    int num_points;
+    int dims;
+    int center;
+    int mode;
+    int affine_target;
+    int reserved;
+} MrEvalJob;
+MR_API int mr_eval_job_layout(int* out, int n);
+MR_API int mr_eval_feed(const MrEvalJob* jobs, int num_jobs, int batch_size, mr_stream_t stream);
+
+/* mr_eval_measures: the read-out of one evaluator's log[rows, num_kp] (fp32 distances, row-major)
+ * against thresholds[num_thresholds] (fp32, non-decreasing), without moving the log.  Per keypoint k:
+ *   sums[k]            fp64 sum of the column over ALL rows (NaN / inf rows make it NaN / inf, as
+ *                      numpy's mean would be): thread t of 1024 adds rows t, t + 1024, ... in order,
+ *                      the lanes of a wave meet in a butterfly, the sixteen waves are added in order
+ *   pck_counts[k, j]   the number of rows with d <= thresholds[j] (fp32 comparison against the array
+ *                      itself); NaN and inf rows count in no bin
+ *   mid[k, 0..1]       the elements (rows - 1) / 2 and rows / 2 of the sorted column, NaN sorted last
+ *                      as np.sort does (equal for an odd count): a radix select on the bit patterns
+ *   nonfinite[k]       the number of NaN or inf rows
+ * Launch shape: one workgroup of 1024 threads per keypoint.  The integers and mid are exact and depend
+ * on no launch shape; the fp64 sum's order is the one stated.  work: mr_eval_measures_workspace_floats
+ * (rows, num_kp, num_thresholds) floats (rows * num_kp: each column made contiguous); an int, like
+ * mr_mano_adapt_workspace_floats, and MR_ERR_BADARG for rows < 0, num_kp < 1, num_thresholds < 0 or a
+ * count beyond INT_MAX.  rows == 0: MR_OK, outputs untouched.  A NULL or misaligned pointer (sums: 8
+ * bytes, the others 4; thresholds and pck_counts may be NULL when num_thresholds == 0):
+ * MR_ERR_BADARG.  num_thresholds > 1024: MR_ERR_NOTIMPL.  All of it before any launch. */
+MR_API int mr_eval_measures_workspace_floats(int rows, int num_kp, int num_thresholds);
+MR_API int mr_eval_measures(const float* log, int rows, int num_kp, const float* thresholds,
+                            int num_thresholds, double* sums, unsigned* pck_counts, float* mid,
+                            unsigned* nonfinite, float* work, mr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * 3. Warping (meshreg/warping/imgflowarp.py)
  * ---------------------------------------------------------------------------------- */
 
