@@ -35,6 +35,7 @@ COLOR_OP_NONE, COLOR_OP_BRIGHTNESS, COLOR_OP_SATURATION, COLOR_OP_HUE, COLOR_OP_
 JPEG_MAGIC, JPEG_HEADER_BYTES = 0x314A524D, 576  # MR_JPEG_*: a packed frame of mr_jpeg_entropy_decode
 # MR_PNG_*: a packed frame of datasets/pngdecode.py; the rows of a band and the largest side of mr_png_unfilter
 PNG_MAGIC, PNG_HEADER_BYTES, PNG_BAND_ROWS, PNG_MAX_SIDE = 0x3150524D, 64, 64, 10752
+RESIZE_MAX_TAPS, RESIZE_PLAN_INTS = 33, 8  # MR_RESIZE_*: the tap cap and the plan's length of mr_frames_resize_*
 EVAL_MAX_JOBS, EVAL_PER_POINT, EVAL_PER_SAMPLE_SUM, EVAL_POINTS, EVAL_MAX_POINTS = 8, 0, 1, 2, 4096  # MR_EVAL_*: the jobs of mr_eval_feed
 EVAL_MAX_THRESHOLDS = 1024  # mr_eval_measures
 MANO_POSE_PCA, MANO_POSE_AXISANG = 0, 1  # MR_MANO_POSE_*: the pose form of mr_mano_forward_full / mr_mano_backward_full
@@ -139,6 +140,12 @@ SIGNATURES = {
     "mr_png_packed_bytes": (_L, [_I] * 3),
     "mr_png_unfilter_workspace_bytes": (_L, [_I] * 4),
     "mr_png_unfilter": (_I, [_P] + [_I] * 4 + [_P, _P, _P]),
+    # Pillow's BILINEAR resize (csrc/frame_resize.hip, csrc/resize_plan.hpp): additions to ABI 9
+    "mr_frames_resize_taps": (_I, [_I, _I]),
+    "mr_frames_resize_tables": (_I, [_I, _I, _P, _P]),
+    "mr_frames_resize_plan": (_I, [_I] * 4 + [_P]),
+    "mr_frames_resize_workspace_bytes": (_I, [_I] * 5),
+    "mr_frames_resize": (_I, [_P, _I, _I, _I, _P, _I, _I] + [_P] * 6),
     "mr_bn_act_forward": (_I, [_P] * 6 + [_F, _I, _I, _I, _P, _I, _I, _I, _P]),
     "mr_bn_act_backward_workspace_bytes": (_L, [_I, _I]),
     "mr_bn_act_backward": (_I, [_P] * 8 + [_F, _I, _I, _I] + [_P] * 5 + [_L, _I, _I, _I, _P]),

@@ -66,6 +66,76 @@ def frames_to_batch(frames, affinetrans, inp_res, flip=None, mean=(0.5, 0.5, 0.5
     return image, mask
 
 
+BILINEAR = 2  # Pillow's Image.BILINEAR: the one resampling filter ``resize`` offers
+_RESIZE_TABLES = {}  # (Ws, Hs, W, H, device type, device index) -> the four device tables of that geometry
+
+
+def resize_tables(in_size, out_size):
+    """Pillow's coefficient tables of one axis (``mr_frames_resize_tables``; needs no device): (bounds int32 [out_size, 2] --
+    per output index the first source index and the count of its taps --, coeffs int32 [out_size, taps], 22-bit fixed point,
+    zero from the count on).  ValueError for a side below 1, NotImplementedError beyond 10752 pixels or a reduction by more
+    than 16."""
+    in_size, out_size = int(in_size), int(out_size)
+    lib = _lib.load()
+    taps = lib.mr_frames_resize_taps(in_size, out_size)
+    if taps == -2:
+        raise NotImplementedError(f"resize {in_size} -> {out_size}: sides run to {_lib.PNG_MAX_SIDE} pixels and a reduction to a "
+                                  f"factor of 16 ({_lib.RESIZE_MAX_TAPS} taps)")
+    if taps < 0:
+        raise ValueError(f"resize {in_size} -> {out_size}: a side is below 1")
+    bounds, coeffs = np.empty((out_size, 2), np.int32), np.empty((out_size, taps), np.int32)
+    rc = lib.mr_frames_resize_tables(in_size, out_size, bounds.ctypes.data, coeffs.ctypes.data)
+    if rc != taps:
+        raise RuntimeError(f"mr_frames_resize_tables failed: {rc}")
+    return bounds, coeffs
+
+
+def _device_resize_tables(Ws, Hs, W, H, dev):
+    dev = torch.device(dev)
+    index = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (Ws, Hs, W, H, dev.type, index)  # (values only: a tensor or a device object never is a key)
+    tabs = _RESIZE_TABLES.get(key)
+    if tabs is None:
+        host = resize_tables(Ws, W) + resize_tables(Hs, H)
+        tabs = _RESIZE_TABLES[key] = tuple(torch.from_numpy(t).to(dev) for t in host)
+    return tabs
+
+
+def resize(frames, size, resample=BILINEAR):
+    """Pillow's ``Image.resize(size, Image.BILINEAR)`` of a batch of decoded frames on the GPU, byte for byte
+    (``mr_frames_resize``): one launch whatever N, on the caller's stream; not differentiable.
+
+    Args:
+        frames: uint8 CUDA tensor [N, Hs, Ws, 3]
+        size: (W, H) of the result.  Sides run from 1 to 10752 pixels; enlargements of any factor, reductions up to a factor
+            of 16 per axis -- beyond that NotImplementedError, from the sizes alone.
+        resample: ``BILINEAR`` (Pillow's code 2) -- anything else is NotImplementedError; ``box`` and ``reducing_gap`` are
+            not offered
+
+    Returns:
+        uint8 CUDA tensor [N, H, W, 3], a new tensor (a copy where the size is the frames' own).  The geometry's coefficient
+        tables are built once per (Ws, Hs, W, H, device), uploaded and kept.
+    """
+    if resample != BILINEAR:
+        raise NotImplementedError(f"resize: only BILINEAR (Pillow's filter code {BILINEAR}) is implemented, got {resample!r}")
+    _lib.check_cuda(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError("frames must be uint8 [N, Hs, Ws, 3]")
+    W, H = int(size[0]), int(size[1])
+    N, Hs, Ws, _ = frames.shape
+    if min(W, H, Ws, Hs) < 1:
+        raise ValueError(f"resize {Ws} x {Hs} -> {W} x {H}: a side is below 1")
+    frames = frames.detach()
+    if (W, H) == (Ws, Hs):
+        return frames.clone(memory_format=torch.contiguous_format)
+    tabs = _device_resize_tables(Ws, Hs, W, H, frames.device)  # (refuses an unsupported geometry also where N = 0)
+    frames = frames.contiguous()
+    out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=frames.device)
+    _lib.call("mr_frames_resize", _lib.ptr(frames), N, Ws, Hs, _lib.ptr(out), W, H, *[_lib.ptr(t) for t in tabs], None,
+              _lib.stream_ptr(frames.device))
+    return out
+
+
 def color_augment(frames, plans, flip=None):
     """Gaussian blur + colour jitter of a batch of decoded frames on the GPU, byte for byte what ``coloraugm``'s host path
     (Pillow) gives for the same draws.

@@ -27,7 +27,12 @@ transform (flip, rotation, centre) as one ``hand_info`` row (``manogt.pack_hand_
 ``assemble_batch`` evaluates the layer for all frames of the step in one GPU call (``manogt.hand_verts_batch``).
 ``hand_cam_rot`` (3x3, only with ``hand_geometry="device"``): the rotation the dataset's ``get_hand_verts3d`` applies after the
 translation (ho3dv2.py:347: ``cam_extr[:3, :3]``); None for a dataset that applies none (fhbhands.py:355-359, which HAS a
-``cam_extr`` and does not use it for the hand).  It is the caller's statement about the dataset: no attribute is read."""
+``cam_extr`` and does not use it for the hand).  It is the caller's statement about the dataset: no attribute is read.
+``frame_size`` ((W, H), or None): the frame size the pose dataset's centre, scale, intrinsics and 2-D annotations refer to
+(fhbhands.py:110-130 reads quarter-size copies and scales its annotations by ``reduce_factor``).  Files of another size are
+resized to it with Pillow's BILINEAR ``Image.resize`` in front of the colour path: by ``get_sample`` on the host, or
+(``decode="device"``) by ``assemble_batch`` on the GPU between the decode and ``color_augment`` (``frames.resize``, byte for byte
+the same) -- the sample then carries ``resize_to``.  Files of that size, and None, change nothing."""
 import random
 import traceback
 
@@ -56,7 +61,7 @@ class HandObjSet(Dataset):
                  split="train", scale_jittering=0.3, center_jittering=0.2, train=True, hue=0.15, saturation=0.5,
                  contrast=0.5, brightness=0.5, blur_radius=0.5, spacing=2, queries=DEFAULT_QUERIES, sides="both",
                  block_rot=False, sample_nb=None, has_dist2strong=False, color_fn="reference", decode="host",
-                 hand_geometry="host", hand_cam_rot=None):
+                 hand_geometry="host", hand_cam_rot=None, frame_size=None):
         if hand_geometry not in ("host", "device"):
             raise ValueError(f"hand_geometry must be 'host' or 'device', got {hand_geometry!r}")
         if hand_geometry == "device" and not hasattr(pose_dataset, "get_hand_info"):
@@ -77,6 +82,11 @@ class HandObjSet(Dataset):
             if not hasattr(pose_dataset, "get_image_bytes"):
                 raise ValueError("decode=\"device\" needs a pose_dataset with get_image_bytes(idx) (the JPEG or PNG file's bytes)")
         self.decode = decode
+        if frame_size is not None:
+            if len(tuple(frame_size)) != 2 or min(int(v) for v in frame_size) < 1:
+                raise ValueError(f"frame_size must be (W, H) with sides of at least 1, got {frame_size!r}")
+            frame_size = (int(frame_size[0]), int(frame_size[1]))
+        self.frame_size = frame_size
         self.pose_dataset = pose_dataset
         self.center_idx, self.inp_res = center_idx, tuple(inp_res)
         self.normalize_img, self.sides = normalize_img, sides
@@ -125,9 +135,18 @@ class HandObjSet(Dataset):
                 data = ds.get_image_bytes(idx)
                 codec = framecodec.codec_for(data)
                 frame, packed = None, codec.host_stage(data)
-                width = codec.packed_info(packed)["width"]  # (the file's own, as its headers give it: no second parse)
+                info = codec.packed_info(packed)  # (the file's own size, as its headers give it: no second parse)
+                width = info["width"]
+                if self.frame_size is not None and (width, info["height"]) != self.frame_size:
+                    # the packed frame travels as it is; assemble_batch resizes after the decode
+                    sample["resize_to"] = np.array(self.frame_size, dtype=np.int32)
+                    width = self.frame_size[0]
             else:
                 frame = np.asarray(ds.get_image(idx))
+                if self.frame_size is not None and (frame.shape[1], frame.shape[0]) != self.frame_size:
+                    from PIL import Image
+
+                    frame = np.asarray(Image.fromarray(frame).resize(self.frame_size, Image.BILINEAR))
                 width = frame.shape[1]
             if flip:
                 center = np.array(center).copy()
@@ -283,7 +302,7 @@ def _hand_verts(dicts, outs, device, mano_layer):
 
 def _images(dicts, outs, frame_keys, device, inp_res, **to_batch):
     """The dicts' frames (under one of ``frame_keys``: decoded, or packed by one codec) -> ``image`` / ``jittermask`` in
-    ``outs``: decode, then ``color_augment`` where planned, then one ``frames_to_batch(..., **to_batch)``."""
+    ``outs``: decode, then ``resize`` where the dicts carry ``resize_to``, then ``color_augment`` where planned, then one ``frames_to_batch(..., **to_batch)``."""
     def packed_codec():
         for codec in framecodec.CODECS:
             n = sum(codec.key in d for d in dicts)
@@ -294,7 +313,20 @@ def _images(dicts, outs, frame_keys, device, inp_res, **to_batch):
                 return codec
         return None
 
+    def resize_target():
+        n = sum("resize_to" in d for d in dicts)
+        if n and n != len(dicts):
+            raise ValueError(f"resize_to in {n} of {len(dicts)} frame dicts: a batch mixes samples of "
+                             "HandObjSet(frame_size=...) whose files need a resize with samples whose files do not")
+        if not n:
+            return None
+        sizes = np.concatenate([np.asarray(d["resize_to"]).reshape(-1, 2) for d in dicts], 0)
+        if np.any(sizes != sizes[:1]):
+            raise ValueError("resize_to: the batch's frames are to be resized to different sizes (one frame size per batch)")
+        return int(sizes[0, 0]), int(sizes[0, 1])
+
     codec = packed_codec()
+    resize_to = resize_target()  # (both checks before anything is uploaded)
     key = "frame" if codec is None else codec.key
     rows = [torch.as_tensor(d[key]) for d in dicts]
     if codec is not None:
@@ -304,6 +336,8 @@ def _images(dicts, outs, frame_keys, device, inp_res, **to_batch):
             raise ValueError(f"{key}: the batch's packed frames differ in size (one frame geometry per batch)")
     frames, split = _stack_rows(rows)
     frames = frames.to(device, non_blocking=True) if codec is None else framecodec.decode_packed(codec, frames, device)
+    if resize_to is not None:
+        frames = frames_mod.resize(frames, resize_to)
     affines = np.concatenate([np.asarray(d["affinetrans"]) for d in dicts], 0)
     flips = np.concatenate([np.asarray(d["flip"]).reshape(-1) for d in dicts], 0)
     planned = sum("color_plan" in d for d in dicts)
@@ -326,14 +360,15 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
     ``color_plan`` (``HandObjSet(color_fn="device")``).  Dicts with ``frame_jpeg`` instead of ``frame``
     (``HandObjSet(decode="device")``, all of a batch or none): the packed frames are stacked, uploaded in one copy and
     reconstructed by ``jpegdecode.reconstruct`` first; dicts with ``frame_png`` likewise, through ``pngdecode.unfilter``.  A batch
-    holds one of the three.  ``image_dtype`` / ``mask_dtype``: the batch's element
+    holds one of the three.  Dicts with ``resize_to`` (``HandObjSet(decode="device", frame_size=...)`` on files of another size, all
+    of a batch or none): the decoded frames go through ``frames.resize`` before the colour augmentation.  ``image_dtype`` / ``mask_dtype``: the batch's element
     types as ``frames_to_batch`` takes them (``torch.bfloat16`` / ``torch.uint8``: the compact batch).
     Dicts with ``hand_info`` (``HandObjSet(hand_geometry="device")``, all of a batch or none) need ``mano_layer``, the
     datasets' ``SynthManoLayer``: the rows are stacked and ``manogt.hand_verts_batch`` runs once; its result is each dict's
     ``handverts3d``."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
     frame_keys = ("frame",) + tuple(codec.key for codec in framecodec.CODECS)
-    consumed = frame_keys + ("affinetrans", "flip", "color_plan", "hand_info")
+    consumed = frame_keys + ("affinetrans", "flip", "color_plan", "hand_info", "resize_to")
     out = [{k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in d.items() if k not in consumed}
            for d in dicts]
     _hand_verts(dicts, out, device, mano_layer)

@@ -15,7 +15,7 @@ class SynthPoseDataset:
     has_dist2strong = False
 
     def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",), jpeg_quality=None, jpeg_subsampling=2,
-                 png_compress_level=None, mano_layer=None):
+                 png_compress_level=None, mano_layer=None, file_scale=1):
         """2 * num_pairs frames: frame 2k and 2k + 1 are the two time steps of scene k.
         jpeg_quality (None: frames are arrays, as ever): the frames exist as JPEG files' bytes, encoded by Pillow at this
         quality and ``jpeg_subsampling`` (0 / 1 / 2: 4:4:4 / 4:2:2 / 4:2:0) -- ``get_image_bytes(idx)`` returns them (the
@@ -26,9 +26,16 @@ class SynthPoseDataset:
         build it (``use_pca=False, flat_hand_mean=True, center_idx=None``, fhbhands.py:103-108).  Every frame then has a MANO
         annotation (fullpose [48], trans [3], shape [10]) drawn from a generator seeded with ``seed``: ``get_hand_info(idx)``
         returns it (the reference's accessor, fhbhands.py:367-370) and ``get_hand_verts3d(idx)`` evaluates the layer on it
-        (``manogt.hand_verts_host``, fhbhands.py:355-359).  Everything else is untouched."""
+        (``manogt.hand_verts_host``, fhbhands.py:355-359).  Everything else is untouched.
+        file_scale (1: as ever; an integer k above 1): the frames -- arrays, JPEG or PNG files -- are k times ``frame_size``
+        a side, while the intrinsics, the boxes and every other annotation stay in ``frame_size`` coordinates: FPHAB as
+        downloaded (1920 x 1080 files, annotations the reference scales by ``reduce_factor = 1 / 4``, fhbhands.py:110-130),
+        for ``HandObjSet(frame_size=...)``."""
         if jpeg_quality is not None and png_compress_level is not None:
             raise ValueError("jpeg_quality and png_compress_level: the frames are files of one format")
+        if int(file_scale) != file_scale or file_scale < 1:
+            raise ValueError(f"file_scale must be an integer of at least 1, got {file_scale!r}")
+        self.file_scale = int(file_scale)
         self.frame_size = tuple(frame_size)  # (W, H)
         W, H = self.frame_size
         scene = synth.random_scene(num_pairs, seed=seed, image_size=256)
@@ -43,7 +50,7 @@ class SynthPoseDataset:
                 K[1, 2] += (H - 256) / 2
                 self.K.append(K)
         self.obj_faces = scene["obj_faces"]
-        self.frames = rng.integers(0, 256, (2 * num_pairs, H, W, 3), dtype=np.uint8)
+        self.frames = rng.integers(0, 256, (2 * num_pairs, H * self.file_scale, W * self.file_scale, 3), dtype=np.uint8)
         self.sides = [sides[i % len(sides)] for i in range(2 * num_pairs)]
         self.files = None  # the frames as files' bytes, where a format is chosen
         save = None

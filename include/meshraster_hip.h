@@ -1124,6 +1124,44 @@ MR_API int64_t mr_png_unfilter_workspace_bytes(int num_frames, int width, int he
 MR_API int mr_png_unfilter(const unsigned char* packed, int num_frames, int width, int height, int channels,
                            unsigned char* frames_out, void* workspace, mr_stream_t stream);
 
+/* ---- frame resize: Pillow's Image.resize(size, Image.BILINEAR) for RGB frames ----------------
+ * frames_in uint8 [num_frames, src_h, src_w, 3] -> frames_out uint8 [num_frames, dst_h, dst_w, 3], byte for byte what
+ * Pillow's ImagingResample gives: two separable passes (the horizontal one first) over 22-bit fixed-point coefficients
+ * with an 8-bit intermediate image; a pass is acc = 2^21 + sum p[lo + x] * k[x] in 32-bit integers and
+ * clamp(acc >> 22, 0, 255).  An axis that keeps its size runs as its identity table (one weight of 2^22).
+ *
+ * HOST, no device needed (csrc/resize_plan.hpp):
+ * mr_frames_resize_taps(in_size, out_size): taps per output pixel of one axis, 2 ceil(max(in / out, 1)) + 1.
+ * mr_frames_resize_tables(in_size, out_size, bounds, coeffs): fills bounds[2 out_size] -- per output index the first
+ *   source index lo and the count n of its taps -- and coeffs[out_size * taps], zero from n on; returns taps.
+ * mr_frames_resize_plan(src_w, src_h, dst_w, dst_h, plan): plan[MR_RESIZE_PLAN_INTS] = tile width, tile height (output
+ *   pixels a workgroup owns), intermediate rows a tile holds, LDS bytes of a workgroup (at most 65536), tiles across, tiles
+ *   down, source columns a tile holds, source rows staged in LDS at a time.  A pure function of the four sizes; MR_OK or
+ *   the refusal below.
+ * All three: a side below 1 (or a NULL table / plan): MR_ERR_BADARG.  A side above MR_PNG_MAX_SIDE, or a reduction by
+ * more than 16 (more than MR_RESIZE_MAX_TAPS = 33 taps): MR_ERR_NOTIMPL.  Enlargements of any factor are supported.
+ *
+ * DEVICE, mr_frames_resize: ONE launch whatever num_frames.  A workgroup owns a tile of the output: it stages the source
+ * rows the tile's taps span in LDS (a few at a time), runs the horizontal pass from them into intermediate rows in LDS, then
+ * the vertical pass from those, then stores the tile; the intermediate image never reaches global memory.  bounds_x / coeffs_x / bounds_y / coeffs_y: the tables of
+ * mr_frames_resize_tables(src_w, dst_w, ...) and (src_h, dst_h, ...) in DEVICE memory, 4-byte aligned.  The kernel clamps
+ * every source index it forms from them to the frame: tables of another geometry give wrong pixels, never a read outside
+ * frames_in.  frames_out is 4-byte aligned (rows are stored as aligned dwords where dst_w is a multiple of 4, as bytes
+ * elsewhere); frames_in needs no alignment (16-byte aligned, it is read 16 bytes a lane).  Integer arithmetic only, no atomics.
+ * workspace: mr_frames_resize_workspace_bytes(num_frames, src_w, src_h, dst_w, dst_h) bytes = 0 (NULL is accepted; an
+ * int, as mr_mano_adapt_workspace_floats; MR_ERR_BADARG / MR_ERR_NOTIMPL for what mr_frames_resize refuses).
+ * num_frames == 0: MR_OK, nothing is touched.  MR_ERR_BADARG: num_frames < 0, a side below 1, NULL or misaligned
+ * pointers.  MR_ERR_NOTIMPL: what mr_frames_resize_plan refuses.  All of it before the launch. */
+#define MR_RESIZE_MAX_TAPS 33
+#define MR_RESIZE_PLAN_INTS 8
+MR_API int mr_frames_resize_taps(int in_size, int out_size);
+MR_API int mr_frames_resize_tables(int in_size, int out_size, int* bounds, int* coeffs);
+MR_API int mr_frames_resize_plan(int src_w, int src_h, int dst_w, int dst_h, int* plan);
+MR_API int mr_frames_resize_workspace_bytes(int num_frames, int src_w, int src_h, int dst_w, int dst_h);
+MR_API int mr_frames_resize(const unsigned char* frames_in, int num_frames, int src_w, int src_h,
+                            unsigned char* frames_out, int dst_w, int dst_h, const int* bounds_x, const int* coeffs_x,
+                            const int* bounds_y, const int* coeffs_y, void* workspace, mr_stream_t stream);
+
 /* ---- trainer side: BatchNorm with frozen statistics + residual add + ReLU -----------------
  * The reference trains with --freeze_batchnorm (trainmeshwarp.py:205-206, 237-240): every BatchNorm2d of the
  * ResNet-18 trunk runs in eval mode with trainable affine parameters, followed by ReLU, by "+ identity, ReLU"
