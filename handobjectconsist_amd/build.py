@@ -6,9 +6,10 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["raster_fwd.hip", "raster_bwd.hip", "warp.hip", "vertex_stage.hip", "mano_lbs.hip", "meshreg_post.hip",
-           "frame_batch.hip", "frame_color.hip", "frame_jpeg.hip", "frame_png.hip", "frozen_bn.hip", "stem_pool.hip", "stem_wrw.hip",
-           "pair_step.hip", "mano_adapt.hip", "eval_metrics.hip", "frame_resize.hip"]
+# the one list of library sources: the host-side recorder (tests/golden/make_golden_launch_sequences.py) links all of them
+SOURCES = ["raster_fwd.hip", "raster_bwd.hip", "raster_bwd_vc.hip", "warp.hip", "warp_tiles.hip", "vertex_stage.hip", "mano_lbs.hip",
+           "meshreg_post.hip", "frame_batch.hip", "frame_color.hip", "frame_jpeg.hip", "frame_png.hip", "frozen_bn.hip", "stem_pool.hip",
+           "stem_wrw.hip", "pair_step.hip", "mano_adapt.hip", "eval_metrics.hip", "frame_resize.hip", "library.hip"]
 LIB_PATH = os.path.join(_HERE, "libmeshraster_hip.so")
 # -ffp-contract=off: parity-critical fp32 expressions must round operation by operation
 # exactly like the CPU oracle (SURVEY 7 "bit-faithful coverage").

@@ -442,7 +442,7 @@ inline BackwardPlan plan_render_backward(const BackwardRequest& r) {
     return p;
 }
 
-// ---- the vertex-colour backward and the tile scatter (raster_bwd.hip) -----------------------------------------------------
+// ---- the vertex-colour backward and the tile scatter (raster_bwd_vc.hip) --------------------------------------------------
 struct ScatterVCPlan {
     int status;
     bool scatter;       // pixel-parallel scatter when the per-image colour table fits LDS (MR_FLAG_FORCE_GATHER: the gather)
@@ -548,7 +548,7 @@ MR_PLAN_HD inline int st_headroom(long long terms) {
 // ... and the binary point of the terms: bm = the float bits of the workgroup's largest |gradient|
 MR_PLAN_HD inline int st_shift(int headroom, unsigned bm) { return ST_FIX_BITS - headroom - ((int)(bm >> 23) - 126); }
 
-// ---- the listed pair-loss forward (warp.hip: launch_flow_pair_forward) -----------------------------------------------------
+// ---- the listed pair-loss forward (warp_tiles.hip: launch_flow_pair_forward) -----------------------------------------------
 // the form -- records / unit gradient / loss only --, the criterion and the batch's element types are chosen once per launch
 struct PairFwdPlan {
     enum Form { LOSS_ONLY, UNIT_GRAD, RECORDS } form;

@@ -60,6 +60,17 @@ struct Face {
     float inv[9];
 };
 
+// map accessors: IMG = image orientation (vertically flipped, NCHW rgb), else raster NHWC
+template <bool IMG>
+__device__ __forceinline__ int64_t idx1(int b, int yi, int xi, int is) {
+    return IMG ? ((int64_t)b * is + (is - 1 - yi)) * is + xi : ((int64_t)b * is + yi) * is + xi;
+}
+template <bool IMG>
+__device__ __forceinline__ int64_t idx3(int b, int yi, int xi, int c, int is) {
+    return IMG ? (((int64_t)b * 3 + c) * is + (is - 1 - yi)) * is + xi
+               : (((int64_t)b * is + yi) * is + xi) * 3 + c;
+}
+
 __device__ __forceinline__ bool backfacing(const float* f) {
     return (f[7] - f[1]) * (f[3] - f[0]) < (f[4] - f[1]) * (f[6] - f[0]);
 }
@@ -465,7 +476,7 @@ __device__ __forceinline__ void rodrigues_bwd(const float* r, const float* gR, f
 
 // Covered-tile lists of the 2B stack images of a frame pair (round 5, ABI 7): mr_flow_pair_forward_grad_tiles' finalize
 // launch compacts the coverage words it reads anyway, mr_flow_pair_backward_unit_tiles hands out its workgroups over them in
-// proportion to the images' covered tiles (raster_bwd.hip, scatter_tiles_body WORK).  Layout of the buffer:
+// proportion to the images' covered tiles (raster_bwd_vc.hip, scatter_tiles_body WORK).  Layout of the buffer:
 //   int n_cov[2B] (padded to 256 bytes) | uint16 cov[2B][tiles per image]  (ids of the image's covered tiles, ascending)
 struct ScatterWork {
     int* n_cov;
@@ -503,7 +514,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblocks) {
 }
 
 // Header of the tile list of a render launch (one per call, in the render's workspace; raster_fwd.hip builds it, the
-// listed warp kernels of warp.hip walk it too).  Entries are uint4 {global tile id = image * tiles per image + tile (raster
+// listed warp kernels of warp_tiles.hip walk it too).  Entries are uint4 {global tile id = image * tiles per image + tile (raster
 // orientation, row-major), offset and count of the bin's records, length of the image's large list}.
 struct TileList {
     unsigned n_heavy;  // tiles with at least HEAVY_RECS candidate records, all images: dispatched FIRST; entries [0, n_heavy)

@@ -25,7 +25,7 @@ struct FlowRenderArgs {
 };
 int launch_flow_render(const FlowRenderArgs& a, hipStream_t s);
 
-// mr_flow_pair_forward_grad_tiles' arguments (warp.hip: occlusion + flow epilogue + pair loss over the render's tile list, then
+// mr_flow_pair_forward_grad_tiles' arguments (warp_tiles.hip: occlusion + flow epilogue + pair loss over the render's tile list, then
 // the finalize launch).  The optional group:
 //   unit_grad, unit_grad_max, loss_sum, scatter_work   without unit_grad: the loss-only form, mr_flow_pair_forward_tiles
 //   mean_out, mean_of   the mean over the batch: mean_out[0] = the mean of loss_bwd + loss_fwd (mean_of = 0) or of loss_fwd
@@ -48,7 +48,7 @@ struct FlowPairFwdArgs {
 };
 int launch_flow_pair_forward(const FlowPairFwdArgs& a, hipStream_t s);
 
-// mr_flow_pair_backward_unit_tiles' arguments (raster_bwd.hip), plus the two extra incoming gradients of mr_pair_step_backward:
+// mr_flow_pair_backward_unit_tiles' arguments (raster_bwd_vc.hip), plus the two extra incoming gradients of mr_pair_step_backward:
 // of loss_bwd + loss_fwd and of the batch mean (ScatterTilesParams::gl_sum / gl_mean; mean_of as in the forward)
 struct UnitScatterArgs {
     const int32_t* face_index_map; const uint32_t* tile_hit; const float* weight_map; const int32_t* vertex_id_map;

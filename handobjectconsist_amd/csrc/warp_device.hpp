@@ -1,6 +1,7 @@
 // warp_device.hpp -- device functions of the photometric-warp kernels that more than one translation unit needs
-// (warp.hip: the warp / occlusion / pair-loss kernels; raster_bwd.hip: the fused pair-loss + raster backward of the
-// training path).  grid_sample semantics restated (torch, zeros padding, align_corners=False):
+// (warp.hip and warp_tiles.hip: the warp / occlusion / pair-loss kernels, dense and over the render's tile list;
+// raster_bwd_vc.hip: the fused pair-loss + raster backward of the training path).  grid_sample semantics restated (torch,
+// zeros padding, align_corners=False):
 //   vx = 2 (x + u) / max(W - 1, 1) - 1 ;  ix = ((vx + 1) W - 1) / 2
 #pragma once
 
@@ -656,8 +657,24 @@ __device__ __forceinline__ unsigned abs_bits_max(float2 g) {
     return max(__float_as_uint(g.x) & 0x7fffffffu, __float_as_uint(g.y) & 0x7fffffffu);
 }
 
+// block-wide sums of four values with ONE barrier: wave butterflies, 4 x 4 partials in LDS,
+// every thread adds the four wave partials in wave order (fixed order: deterministic)
+__device__ __forceinline__ void block_sum4(float* v, float (*red)[4]) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] += __shfl_xor(v[k], off);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 4; k++) red[wave][k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
+}
+
 // ---------------------------------------------------------------------------------------
-// listed launches: a workgroup's tile of the stacked render's tile list (see warp.hip, "Listed launches")
+// listed launches: a workgroup's tile of the stacked render's tile list (see warp_tiles.hip, "Listed launches")
 // ---------------------------------------------------------------------------------------
 struct ListArgs {
     const TileList* tlist;

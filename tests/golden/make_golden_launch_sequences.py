@@ -1,7 +1,7 @@
-"""Generate tests/golden/launch_sequences.json: what every launcher of raster_fwd.hip, raster_bwd.hip, warp.hip, pair_step.hip
-and vertex_stage.hip asks of the HIP runtime -- kernel, grid, block, dynamic LDS bytes and a hash of the explicit arguments of
+"""Generate tests/golden/launch_sequences.json: what every launcher of raster_fwd.hip, raster_bwd.hip, raster_bwd_vc.hip, warp.hip,
+warp_tiles.hip, pair_step.hip and vertex_stage.hip asks of the HIP runtime -- kernel, grid, block, dynamic LDS bytes and a hash of the explicit arguments of
 each launch, every memset, stream-ordered allocation and attribute call, in order -- over the table of cases in
-tests/host/launch_record_main.cpp.  No device is involved: the five sources are compiled with the library's flags plus
+tests/host/launch_record_main.cpp.  No device is involved: the seven sources are compiled with the library's flags plus
 ``--cuda-host-only`` and linked with tests/host/hip_recorder.cpp, a stand-in for the runtime that writes the calls down.
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_launch_sequences.py [output path [source hash]]
@@ -9,9 +9,9 @@ tests/host/launch_record_main.cpp.  No device is involved: the five sources are 
 The file is a record of the launchers as they were BEFORE their decisions moved into csrc/launch_plan.hpp, with one host-side
 change on top.  Seven parameter blocks were list-initialised, which left their padding bytes -- kernel-argument bytes like any
 other -- to the stack, so that the hashes of their launches differed from run to run or from build to build: PairParams and
-PairBwdParams (warp.hip), the two PixelMapParams of mr_backward_pixel_map and mr_render_backward, and the GatherVCParams of
-mr_render_vc_backward (inside its ScatterVCParams), mr_render_flow_backward, mr_flow_pair_backward_tiles_crit and
-launch_unit_scatter_tiles (raster_bwd.hip).  In the recorded tree they are value-initialised and then filled, exactly as in the
+PairBwdParams (warp.hip), the two PixelMapParams of mr_backward_pixel_map and mr_render_backward (raster_bwd.hip), and the
+GatherVCParams of mr_render_vc_backward (inside its ScatterVCParams), mr_render_flow_backward, mr_flow_pair_backward_tiles_crit
+and launch_unit_scatter_tiles (raster_bwd_vc.hip).  In the recorded tree they are value-initialised and then filled, exactly as in the
 tree this file came with; nothing else differs from the parent commit, and against the untouched parent only the argument
 hashes of those launches differ.  The ``build.source_hash()`` of the recorded tree is stored with the file.
 
@@ -22,7 +22,7 @@ runner from this file.  (Recorded that way since: the pair step's "bwd-only" cas
 one incoming gradient -- `R -1` before launch_unit_scatter_tiles accepted it, the scatter and the vertex launch after; no other
 line moved.)
 
-The driver links the other nine sources too (UNRECORDED_SOURCES), for its cases that are run and not recorded
+The driver links every other source of build.SOURCES too (unrecorded_sources()), for its cases that are run and not recorded
 (``--unrecorded``; with ``--stream HEX`` every case hands that stream over and the recorder reports calls on any other:
 tests/test_stream_record_host.py).  Neither option changes a line of the recorded table.
 
@@ -46,11 +46,7 @@ if ROOT not in sys.path:
 PATH = os.path.join(HERE, "launch_sequences.json")
 HOST = os.path.join(ROOT, "tests", "host")
 CACHE = os.path.join(HOST, "build")  # git-ignored
-SOURCES = ["raster_fwd.hip", "raster_bwd.hip", "warp.hip", "pair_step.hip", "vertex_stage.hip"]
-# linked as well, host-only like the five, for the cases that are run but not recorded (launch_record --unrecorded: every
-# entry point on the caller's stream, tests/test_stream_record_host.py); their launch geometry is in no golden file
-UNRECORDED_SOURCES = ["mano_lbs.hip", "meshreg_post.hip", "frozen_bn.hip", "stem_pool.hip", "stem_wrw.hip", "frame_batch.hip",
-                      "frame_color.hip", "frame_jpeg.hip", "frame_png.hip"]
+SOURCES = ["raster_fwd.hip", "raster_bwd.hip", "raster_bwd_vc.hip", "warp.hip", "warp_tiles.hip", "pair_step.hip", "vertex_stage.hip"]
 RUNS = {"cus256": ["--cus", "256"], "cus64": ["--cus", "64"]}
 SOURCE_TABLES = {}  # source -> its kernel argument table, filled by build_driver
 
@@ -88,6 +84,17 @@ def parse_kernel_args(asm_text):
     return out
 
 
+def unrecorded_sources():
+    """Every other source of the library (build.SOURCES is the one list of them), linked as well, host-only like the recorded
+    ones, for the cases that are run but not recorded (launch_record --unrecorded: every entry point on the caller's stream,
+    tests/test_stream_record_host.py); their launch geometry is in no golden file.  Computed, so that a source added to the
+    build is never outside the recorder's checks."""
+    from handobjectconsist_amd import build
+
+    assert set(SOURCES) <= set(build.SOURCES), "a recorded source the library is not built from"
+    return [src for src in build.SOURCES if src not in SOURCES]
+
+
 def build_driver(verbose=False):
     """-> (driver executable, kernel argument table); compiles what the cache under tests/host/build/ does not hold."""
     from handobjectconsist_amd import build
@@ -99,7 +106,7 @@ def build_driver(verbose=False):
             hh.update(fh.read())
     procs, objs, tables = [], [], []
     tmp = ".%d.tmp" % os.getpid()  # (written under a name of this process, then renamed: concurrent builders do not collide)
-    for src in SOURCES + UNRECORDED_SOURCES:
+    for src in SOURCES + unrecorded_sources():
         with open(os.path.join(build.CSRC, src), "rb") as fh:
             key = hashlib.sha256(" ".join(build.COMPILE_FLAGS).encode() + hh.digest() + fh.read()).hexdigest()[:16]
         stem = os.path.join(CACHE, "%s.%s" % (os.path.splitext(src)[0], key))

@@ -13,7 +13,7 @@
 
 using namespace mr;
 
-// `launch_plan_cases scatter`: the pair step's backward scatter (unit_scatter_tiles_kernel, raster_bwd.hip) at given counts of
+// `launch_plan_cases scatter`: the pair step's backward scatter (unit_scatter_tiles_kernel, raster_bwd_vc.hip) at given counts of
 // covered 32 x 8 tiles per image, on a device of 256 compute units: how many workgroups every image gets and, for every
 // workgroup, the `terms` and `headroom` the kernel computes.  tests/test_pair_upstream_cases_host.py feeds it the oracle's
 // coverage.

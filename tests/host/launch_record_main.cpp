@@ -5,7 +5,7 @@
 //
 // --stream: the value every case passes as its mr_stream_t (NULL without it), announced to the recorder, which then reports
 // every call on another stream; nothing else of the output changes.  --unrecorded: the recorded table in full, then the
-// cases no golden file holds (every other entry point of all fourteen sources), a self-test of the stream check, and the
+// cases no golden file holds (every other entry point of every source the library is built from), a self-test of the stream check, and the
 // kernels no case launched.  --kernel-names: the table's kernels under the names the L lines show.
 //
 // Pointers are made up (argument k of a call sits at k << 40, nothing is ever dereferenced), so the argument hashes are
@@ -632,7 +632,7 @@ void pair_forward_cases() {
 // every runtime call they make is on that stream, and that between them and the recorded table every kernel is launched.
 void unrecorded_cases() {
     const float E5 = 1e-5f;
-    // the nine sources the recorded table does not touch
+    // the sources the recorded table does not touch
     for (int full = 0; full < 2; full++)
         for (int center : {-1, 9, 17}) {
             if (!full && center == 17) continue;
@@ -750,7 +750,47 @@ void unrecorded_cases() {
         end(mr_png_unfilter(P<unsigned char>(1), 3, 61, 45, ch, P<unsigned char>(2), nullptr, g_stream));
     }
 
-    // the entry points of the five recorded sources that the recorded table never calls
+    for (int center : {-1, 9}) {
+        begin("unrecorded mano_adapt_forward center%d", center);
+        end(mr_mano_adapt_forward(P(1), P(2), center, P(3), P(4), 3, 778, 21, g_stream));
+        for (int which = 0; which < 3; which++) {  // both incoming gradients and the weight's; g_verts alone; g_joints alone
+            begin("unrecorded mano_adapt_backward center%d which%d", center, which);
+            end(mr_mano_adapt_backward(P(1), P(2), center, which != 2 ? P(5) : nullptr, which != 1 ? P(6) : nullptr, P(7), P(8),
+                                       which == 0 ? P(9) : nullptr, 3, 778, 21, g_stream));
+        }
+    }
+    {
+        // (the jobs are a host array, read before the call returns)
+        auto job = [](int k, int mode, int dims, bool affine, int center) {
+            MrEvalJob j{};
+            j.pred = P(4 * k + 1); j.target = mode == MR_EVAL_POINTS ? nullptr : P(4 * k + 2); j.affine = affine ? P(4 * k + 3) : nullptr;
+            j.out = P(4 * k + 4); j.num_points = mode == MR_EVAL_PER_SAMPLE_SUM ? 5000 : 21; j.dims = dims; j.center = center; j.mode = mode;
+            j.affine_target = affine && mode == MR_EVAL_PER_SAMPLE_SUM;
+            return j;
+        };
+        for (int mode : {MR_EVAL_PER_POINT, MR_EVAL_PER_SAMPLE_SUM, MR_EVAL_POINTS})
+            for (int affine = 0; affine < 2; affine++) {
+                const MrEvalJob one = job(0, mode, affine ? 2 : 3, affine != 0, affine ? -1 : 0);
+                begin("unrecorded eval_feed mode%d affine%d", mode, affine);
+                end(mr_eval_feed(&one, 1, 3, g_stream));
+            }
+        MrEvalJob eight[MR_EVAL_MAX_JOBS];
+        for (int k = 0; k < MR_EVAL_MAX_JOBS; k++) eight[k] = job(k, k % 3, k & 1 ? 2 : 3, (k & 3) == 1, k % 3 == 0 ? 9 : -1);
+        begin("unrecorded eval_feed jobs%d", MR_EVAL_MAX_JOBS);
+        end(mr_eval_feed(eight, MR_EVAL_MAX_JOBS, 64, g_stream));
+    }
+    for (int nt : {0, 20}) {
+        begin("unrecorded eval_measures thresholds%d", nt);
+        end(mr_eval_measures(P(1), 1000, 21, nt ? P(2) : nullptr, nt, P<double>(3), nt ? P<unsigned>(4) : nullptr, P(5), P<unsigned>(6), P(7), g_stream));
+    }
+    // the horizontal taps of the five instantiations: 3 (an enlargement), 5, 7, 9 (reductions up to 2, 3, 4), any count (by 5)
+    for (int dst_w : {1280, 480, 256, 160, 128}) {
+        begin("unrecorded frames_resize 640x480 to %dx%d taps%d", dst_w, dst_w * 3 / 4, mr_frames_resize_taps(640, dst_w));
+        end(mr_frames_resize(P<unsigned char>(1), 3, 640, 480, P<unsigned char>(2), dst_w, dst_w * 3 / 4, P<int>(3), P<int>(4), P<int>(5), P<int>(6), nullptr,
+                             g_stream));
+    }
+
+    // the entry points of the seven recorded sources that the recorded table never calls
     for (int mode = 0; mode < 2; mode++) {
         begin("unrecorded warp_forward mode%d", mode);
         end(mr_warp_forward(P(1), P(2), P(3), P(4), 2, 3, 60, 44, 1.0f, mode, g_stream));

@@ -294,7 +294,7 @@ _WITH_WORKSPACE = _FLOW_FWD + _CONSIST[:2] + _CONSIST_TILES[:2]
 
 # (entry points, overrides of _VALID -- None = NULL --, expected return)
 _VALIDATION_TABLE = [
-    # ---- tile scatter backward (raster_bwd.hip) ----
+    # ---- tile scatter backward (raster_bwd_vc.hip) ----
     (_SCATTER, dict(batch_size=-1), -1),
     (_SCATTER, dict(num_verts=-1), -1),
     (_SCATTER, dict(num_faces=-1), -1),
@@ -370,7 +370,7 @@ _VALIDATION_TABLE = [
     (_CRIT, dict(criterion=-1), -1),
     (_CRIT, dict(criterion=2, batch_size=0, list_capacity=0), -1),
     (_CRIT, dict(criterion=1, batch_size=0, list_capacity=0), 0),
-    # ---- flow-pair forward over the tile list (warp.hip) ----
+    # ---- flow-pair forward over the tile list (warp_tiles.hip) ----
     (_FLOW_FWD, dict(mask_flow1=None), -1),
     (_FLOW_FWD, dict(mask_flow2=None), -1),
     (_FLOW_FWD, dict(flow12=None), -1),
@@ -393,7 +393,7 @@ _VALIDATION_TABLE = [
     (_FLOW_FWD[2:], dict(unit_grad=None), -1),
     (_FLOW_FWD[2:], dict(unit_grad_max=None), -1),
     (_FLOW_FWD[2:], dict(unit_grad=None, batch_size=0, list_capacity=0), -1),
-    # ---- what the pair-loss launchers share (warp.hip) ----
+    # ---- what the pair-loss launchers share (warp.hip, warp_tiles.hip) ----
     (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(image_ref=None), -1),
     (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(image=None), -1),
     (_FLOW_FWD + _CONSIST + _CONSIST_TILES, dict(jitter_ref=None), -1),

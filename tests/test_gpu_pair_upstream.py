@@ -7,7 +7,7 @@ unchanged: guarded inputs, poisoned outputs, the float64 oracle element by eleme
 largest |ref| of the same sample and leaf -- a rule relative to the sample, so it holds at any coefficient in fp32's normal
 range.  Specs and cases: tests/pair_upstream_cases.py; their exactness and the headroom proofs: tests/test_pair_upstream_cases_host.py.
 
-What the backward does with the upstream (raster_bwd.hip: st_unit_scalars and st_unit_coef, the coefficient phase of
+What the backward does with the upstream (raster_bwd_vc.hip: st_unit_scalars and st_unit_coef, the coefficient phase of
 scatter_tiles_body; the shift: launch_plan.hpp's st_headroom and st_shift): one coefficient per image,
 (gl_dir + gl_sum + gl_mean / B) / count from the arrays present; a zero coefficient returns early; the fixed point's shift is
 taken from the exponent of fl(unit_max x coefficient); a non-finite product switches the workgroup to fp32 global atomics; the
