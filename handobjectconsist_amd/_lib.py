@@ -90,6 +90,9 @@ SIGNATURES = {
     "mr_eval_feed": (_I, [_P, _I, _I, _P]),
     "mr_eval_measures_workspace_floats": (_I, [_I, _I, _I]),
     "mr_eval_measures": (_I, [_P, _I, _I, _P, _I] + [_P] * 5 + [_P]),
+    # ground-truth object meshes from a resident model bank (csrc/obj_gt.hip): additions to ABI 9
+    "mr_obj_bank_build": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "mr_obj_gt_batch": (_I, [_P] * 5 + [_I, _I, _I, _P, _I, _L, _L, _P, _P, _L, _P, _L, _P, _P, _P]),
     "mr_warp_forward": (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_warp_backward": (_I, [_P] * 5 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_occlusion_mask": (_I, [_P] * 4 + [_L, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),

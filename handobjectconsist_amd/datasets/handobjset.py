@@ -32,7 +32,12 @@ translation (ho3dv2.py:347: ``cam_extr[:3, :3]``); None for a dataset that appli
 (fhbhands.py:110-130 reads quarter-size copies and scales its annotations by ``reduce_factor``).  Files of another size are
 resized to it with Pillow's BILINEAR ``Image.resize`` in front of the colour path: by ``get_sample`` on the host, or
 (``decode="device"``) by ``assemble_batch`` on the GPU between the decode and ``color_augment`` (``frames.resize``, byte for byte
-the same) -- the sample then carries ``resize_to``.  Files of that size, and None, change nothing."""
+the same) -- the sample then carries ``resize_to``.  Files of that size, and None, change nothing.
+``obj_geometry="device"`` (needs ``pose_dataset.get_obj_info(idx) -> (model id, pose [3,4])``): the sample carries the frame's
+model id, its placement ``[A | b]`` and the same small transform as one ``obj_info`` row (``objgt.pack_obj_info``) instead of
+``objverts3d`` / ``objfaces`` / ``objcanverts`` / ``objcantrans`` / ``objcanscale`` (the row remembers which of the three object queries were asked for: the batch gets the keys
+the host path would have given it); ``assemble_batch(obj_bank=...)`` gathers them
+from the device-resident model bank for all frames of the step in one GPU call (``objgt.obj_geometry_batch``)."""
 import random
 import traceback
 
@@ -61,7 +66,12 @@ class HandObjSet(Dataset):
                  split="train", scale_jittering=0.3, center_jittering=0.2, train=True, hue=0.15, saturation=0.5,
                  contrast=0.5, brightness=0.5, blur_radius=0.5, spacing=2, queries=DEFAULT_QUERIES, sides="both",
                  block_rot=False, sample_nb=None, has_dist2strong=False, color_fn="reference", decode="host",
-                 hand_geometry="host", hand_cam_rot=None, frame_size=None):
+                 hand_geometry="host", hand_cam_rot=None, frame_size=None, obj_geometry="host"):
+        if obj_geometry not in ("host", "device"):
+            raise ValueError(f"obj_geometry must be 'host' or 'device', got {obj_geometry!r}")
+        if obj_geometry == "device" and not hasattr(pose_dataset, "get_obj_info"):
+            raise ValueError("obj_geometry=\"device\" needs a pose_dataset with get_obj_info(idx) (model id, pose [3,4])")
+        self.obj_geometry = obj_geometry
         if hand_geometry not in ("host", "device"):
             raise ValueError(f"hand_geometry must be 'host' or 'device', got {hand_geometry!r}")
         if hand_geometry == "device" and not hasattr(pose_dataset, "get_hand_info"):
@@ -221,8 +231,18 @@ class HandObjSet(Dataset):
                     sample["hand_info"] = manogt.pack_hand_info(pose, trans, shape, flip=flip, rot_mat=rot_mat, center3d=center3d,
                                                                 cam_rot=self.hand_cam_rot)
                     continue
+                if key == "objverts3d" and self.obj_geometry == "device":
+                    continue
                 pts = rotated(mirrored(getattr(ds, getter)(idx)))
                 sample[key] = (pts - center3d if center3d is not None else pts).astype(np.float32)
+        if self.obj_geometry == "device":
+            if any(k in q for k in ("objverts3d", "objfaces", "objcanverts")):
+                # the model's id and placement travel; the meshes are gathered on the GPU by assemble_batch (same mirror, rotation, centre)
+                from handobjectconsist_amd.datasets import objgt
+
+                model, pose34 = ds.get_obj_info(idx)
+                sample["obj_info"] = objgt.pack_obj_info(model, pose34, flip=flip, rot_mat=rot_mat, center3d=center3d, queries=q)
+            return sample
         if "objfaces" in q:
             sample["objfaces"] = np.asarray(ds.get_obj_faces(idx))
         if "objcanverts" in q:
@@ -300,6 +320,36 @@ def _hand_verts(dicts, outs, device, mano_layer):
         o["handverts3d"] = v
 
 
+def _obj_rows(dicts, obj_bank):
+    """The dicts' ``obj_info`` rows, checked (all dicts or none, collated, a bank, ids inside it) before anything is uploaded:
+    None, or the arguments of ``objgt.obj_geometry_batch``."""
+    with_info = sum("obj_info" in d for d in dicts)
+    if not with_info:
+        return None
+    if with_info != len(dicts):
+        raise ValueError(f"obj_info in {with_info} of {len(dicts)} dicts: a batch mixes samples of "
+                         "HandObjSet(obj_geometry=\"device\") with samples that carry their meshes")
+    if obj_bank is None:
+        raise ValueError("obj_info needs assemble_batch(obj_bank=...): the bank of the dataset's models")
+    from handobjectconsist_amd.datasets import objgt
+
+    rows = [np.asarray(d["obj_info"], np.float32) for d in dicts]
+    if any(r.ndim != 2 for r in rows):
+        raise ValueError("obj_info must be collated: [frames, values] per dict, not one sample's row")
+    args = objgt.unpack_obj_info(np.concatenate(rows, 0))
+    obj_bank.check_ids(args["model"])
+    return dict(args, groups=[len(r) for r in rows])
+
+
+def _obj_meshes(args, outs, device, obj_bank):
+    """-> ``objverts3d`` / ``objcanverts`` / ``objfaces`` / ``objcantrans`` / ``objcanscale`` in ``outs``, through one
+    ``objgt.obj_geometry_batch`` call; each dict padded to its own longest model."""
+    from handobjectconsist_amd.datasets import objgt
+
+    for o, res in zip(outs, objgt.obj_geometry_batch(obj_bank, device=device, **args)):
+        o.update(res)
+
+
 def _images(dicts, outs, frame_keys, device, inp_res, **to_batch):
     """The dicts' frames (under one of ``frame_keys``: decoded, or packed by one codec) -> ``image`` / ``jittermask`` in
     ``outs``: decode, then ``resize`` where the dicts carry ``resize_to``, then ``color_augment`` where planned, then one ``frames_to_batch(..., **to_batch)``."""
@@ -353,7 +403,7 @@ def _images(dicts, outs, frame_keys, device, inp_res, **to_batch):
 
 
 def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
-                   image_dtype=torch.float32, mask_dtype=torch.float32, mano_layer=None):
+                   image_dtype=torch.float32, mask_dtype=torch.float32, mano_layer=None, obj_bank=None):
     """Collated batch (one frame's dict, or a list of them from ``seq_extend_collate``) -> device-resident
     tensors with ``image`` / ``jittermask`` built by the GPU from ``frame`` / ``affinetrans`` / ``flip``.
     All frames of the step go through ONE ``frames_to_batch`` launch -- after ``frames.color_augment`` where the dicts carry
@@ -365,13 +415,20 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
     types as ``frames_to_batch`` takes them (``torch.bfloat16`` / ``torch.uint8``: the compact batch).
     Dicts with ``hand_info`` (``HandObjSet(hand_geometry="device")``, all of a batch or none) need ``mano_layer``, the
     datasets' ``SynthManoLayer``: the rows are stacked and ``manogt.hand_verts_batch`` runs once; its result is each dict's
-    ``handverts3d``."""
+    ``handverts3d``.
+    Dicts with ``obj_info`` (``HandObjSet(obj_geometry="device")``, all of a batch or none) need ``obj_bank``, the
+    ``objgt.ObjectBank`` of the dataset's models: one ``objgt.obj_geometry_batch`` call over all frames of the step gives each dict
+    its ``objverts3d`` / ``objcanverts`` / ``objfaces`` (int64) / ``objcantrans`` / ``objcanscale``, padded cyclically to the dict's own
+    longest model.  A mixed batch, a missing bank and an id outside the bank raise ValueError before anything is uploaded."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
     frame_keys = ("frame",) + tuple(codec.key for codec in framecodec.CODECS)
-    consumed = frame_keys + ("affinetrans", "flip", "color_plan", "hand_info", "resize_to")
+    consumed = frame_keys + ("affinetrans", "flip", "color_plan", "hand_info", "resize_to", "obj_info")
+    obj_args = _obj_rows(dicts, obj_bank)  # (refusals before the first upload)
     out = [{k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in d.items() if k not in consumed}
            for d in dicts]
     _hand_verts(dicts, out, device, mano_layer)
+    if obj_args is not None:
+        _obj_meshes(obj_args, out, device, obj_bank)
     with_frames = [i for i, d in enumerate(dicts) if any(k in d for k in frame_keys)]
     if with_frames:
         m, s = (mean, std) if normalize_img else ((0.5, 0.5, 0.5), (1.0, 1.0, 1.0))

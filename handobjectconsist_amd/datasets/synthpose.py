@@ -11,11 +11,34 @@ from handobjectconsist_amd.datasets import framecodec
 from handobjectconsist_amd.utils import synth
 
 
+def procedural_models(count, seed=0):
+    """``count`` closed meshes of different sizes: ellipsoids of a few centimetres, model j a (4 + 3 j) x (6 + 5 j) latitude /
+    longitude grid -- 20, 68, 146, ... vertices, twice as many faces less four -- outward-facing, float32 / int32."""
+    rng = np.random.default_rng([seed, 35])
+    models = []
+    for j in range(int(count)):
+        lat, lon = 4 + 3 * j, 6 + 5 * j
+        radii = rng.uniform(0.03, 0.06, 3)
+        th = np.pi * np.arange(1, lat) / lat
+        ph = 2 * np.pi * np.arange(lon) / lon
+        ring = np.stack([np.outer(np.sin(th), np.cos(ph)), np.outer(np.sin(th), np.sin(ph)), np.outer(np.cos(th), np.ones(lon))], -1)
+        verts = np.concatenate([[[0, 0, 1.0]], ring.reshape(-1, 3), [[0, 0, -1.0]]]) * radii
+        at = lambda i, k: 1 + i * lon + k % lon
+        south = 1 + (lat - 1) * lon
+        faces = [[0, at(0, k), at(0, k + 1)] for k in range(lon)]
+        for i in range(lat - 2):
+            for k in range(lon):
+                faces += [[at(i, k), at(i + 1, k), at(i + 1, k + 1)], [at(i, k), at(i + 1, k + 1), at(i, k + 1)]]
+        faces += [[south, at(lat - 2, k + 1), at(lat - 2, k)] for k in range(lon)]
+        models.append((verts.astype(np.float32), np.array(faces, np.int32)))
+    return models
+
+
 class SynthPoseDataset:
     has_dist2strong = False
 
     def __init__(self, num_pairs=4, frame_size=(640, 480), seed=0, sides=("right",), jpeg_quality=None, jpeg_subsampling=2,
-                 png_compress_level=None, mano_layer=None, file_scale=1):
+                 png_compress_level=None, mano_layer=None, file_scale=1, obj_models=None):
         """2 * num_pairs frames: frame 2k and 2k + 1 are the two time steps of scene k.
         jpeg_quality (None: frames are arrays, as ever): the frames exist as JPEG files' bytes, encoded by Pillow at this
         quality and ``jpeg_subsampling`` (0 / 1 / 2: 4:4:4 / 4:2:2 / 4:2:0) -- ``get_image_bytes(idx)`` returns them (the
@@ -30,7 +53,13 @@ class SynthPoseDataset:
         file_scale (1: as ever; an integer k above 1): the frames -- arrays, JPEG or PNG files -- are k times ``frame_size``
         a side, while the intrinsics, the boxes and every other annotation stay in ``frame_size`` coordinates: FPHAB as
         downloaded (1920 x 1080 files, annotations the reference scales by ``reduce_factor = 1 / 4``, fhbhands.py:110-130),
-        for ``HandObjSet(frame_size=...)``."""
+        for ``HandObjSet(frame_size=...)``.
+        obj_models (None: the object is the scene's, as ever): a list of (verts [V,3], faces [F,3]) models, or a count k of
+        procedural ones of different sizes (``procedural_models``).  They form ``self.obj_bank`` (``objgt.ObjectBank``); every
+        scene then has a model id and each of its two frames a rigid placement [A | b] near the scene's object (float64), drawn
+        from a generator seeded with ``seed``: ``get_obj_info(idx)`` returns them (the accessor ``HandObjSet(obj_geometry="device")`` needs), and
+        ``get_obj_verts_trans`` / ``get_obj_faces`` / ``get_obj_verts_can`` evaluate the same annotation through the bank's host
+        functions.  Everything else is untouched."""
         if jpeg_quality is not None and png_compress_level is not None:
             raise ValueError("jpeg_quality and png_compress_level: the frames are files of one format")
         if int(file_scale) != file_scale or file_scale < 1:
@@ -82,6 +111,25 @@ class SynthPoseDataset:
                 self.mano_infos.append({"fullpose": fullpose.astype(np.float32), "trans": trans.astype(np.float32),
                                         "shape": (mrng.standard_normal(10) * 0.5).astype(np.float32)})
 
+        self.obj_bank, self.obj_infos = None, None
+        if obj_models is not None:
+            from handobjectconsist_amd.datasets import objgt
+
+            models = procedural_models(obj_models, seed) if isinstance(obj_models, (int, np.integer)) else obj_models
+            self.obj_bank = objgt.ObjectBank(models)
+            orng = np.random.default_rng([seed, 34])  # (a generator of its own: the frames above do not move)
+            self.obj_infos = []
+            for k in range(2 * num_pairs):
+                if k % 2 == 0:  # the two time steps of a scene show one model, turned a little further
+                    model, turn = int(orng.integers(len(self.obj_bank))), orng.standard_normal(3) * 0.7
+                w = turn + orng.standard_normal(3) * 0.05  # axis-angle -> rotation (Rodrigues, float64)
+                t = np.linalg.norm(w)
+                K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / t
+                R = np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * K.dot(K)
+                # the placement: where the scene's object is (in front of the camera, metres)
+                b = self.obj[k].mean(0) + orng.standard_normal(3) * 0.01
+                self.obj_infos.append((model, np.concatenate([R, b[:, None]], 1)))
+
     def __len__(self):
         return len(self.frames)
 
@@ -128,13 +176,24 @@ class SynthPoseDataset:
         info = self.mano_infos[idx]
         return info["fullpose"], info["trans"], info["shape"]
 
+    def get_obj_info(self, idx):
+        if self.obj_infos is None:
+            raise RuntimeError("SynthPoseDataset(obj_models=None) holds no model ids")
+        return self.obj_infos[idx]
+
     def get_obj_verts_trans(self, idx):
+        if self.obj_bank is not None:
+            return self.obj_bank.verts_trans(*self.obj_infos[idx])
         return self.obj[idx].copy()
 
     def get_obj_faces(self, idx):
+        if self.obj_bank is not None:
+            return self.obj_bank.faces[self.obj_infos[idx][0]]
         return self.obj_faces
 
     def get_obj_verts_can(self, idx):
+        if self.obj_bank is not None:
+            return self.obj_bank.canonical(self.obj_infos[idx][0])
         return (self.obj[idx] - self.can_trans) / self.can_scale, self.can_trans, self.can_scale
 
     def get_dist_idx(self, idx, dist=1):

@@ -580,6 +580,61 @@ MR_API int mr_eval_measures(const float* log, int rows, int num_kp, const float*
                             unsigned* nonfinite, float* work, mr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * 2c. Ground-truth object meshes from a resident model bank
+ * ---------------------------------------------------------------------------------- */
+/* Additions to ABI 9.  The bank: the models of a dataset concatenated in device memory,
+ *   verts[total_verts,3] fp32, faces[total_faces,3] int32 (model-local indices),
+ *   table[M,4] int32: first vertex, vertices, first face, faces of each model.
+ * mr_obj_bank_build, one launch, one workgroup per model:
+ *   box[M,6]  = min x y z, max x y z over the model's vertices (zeros ordered -0 < +0)
+ *   centre[M,3] = (min + max) * 0.5f      canverts[total_verts,3] = v - centre
+ * -- libyana's center_vert_bbox(verts, scale=False), each step one IEEE fp32 operation: numpy's
+ * float32 bits.  A one-vertex model is legal; vertices are finite (the caller's check).  A table row
+ * that leaves the bank (device data) is skipped: nothing of that model is written.
+ * num_models == 0: MR_OK, nothing launched.  num_models < 0, total_verts < 0, total_verts == 0
+ * with models, a NULL or misaligned pointer: MR_ERR_BADARG before any launch.
+ *
+ * mr_obj_gt_batch, one launch for the N frames of a step, whatever collated dict they belong to.
+ * frames[N] on the device, one record per frame (32 words): */
+typedef struct MrObjFrame {
+    int32_t model;        /* clamped to [0, M) */
+    int32_t padded_verts; /* rows of this frame in objverts3d / objcanverts */
+    int32_t padded_faces; /* rows of this frame in objfaces */
+    int32_t flip;         /* != 0: objcanverts' x negated (objverts3d's mirror is folded into rot) */
+    int32_t vert_offset;  /* first row of the frame in objverts3d / objcanverts; ascending over frames */
+    int32_t face_offset;  /* first row of the frame in objfaces; ascending over frames */
+    int32_t reserved[2];
+    float pose[12];       /* [A | b] row-major 3x4: the dataset's placement of the model */
+    float rot[9];         /* augmentation rotation x mirror, row-major */
+    float center3d[3];    /* subtracted last; zeros where nothing is centred */
+} MrObjFrame;
+/* For slot s of frame f, n / nF the model's own vertex / face counts FROM THE TABLE:
+ *   y = A v[s mod n] + b,  y_i = ((A_i0 v_0 + A_i1 v_1) + A_i2 v_2) + b_i
+ *   objverts3d[vert_offset + s, r]  = ((R_r0 y_0 + R_r1 y_1) + R_r2 y_2) - center3d[r]
+ *   objcanverts[vert_offset + s, :] = canverts[s mod n], x negated where flip
+ *   objfaces[face_offset + s, :]    = (int64_t) faces[s mod nF]
+ *   objcantrans[f, :] = centre[model],  objcanscale[f] = 1
+ * Cyclic repetition is the reference's padding rule (collate.py:15-36).  vert_rows / face_rows: the
+ * rows of all frames together (the launch is sized by them); vert_capacity / face_capacity: the rows
+ * the output buffers hold.  A workgroup owns 256 consecutive rows: one lane per row computes it into LDS,
+ * then one lane per output element stores it, at an index formed from the workgroup and lane ids alone:
+ * nothing read from device memory becomes an output index; model ids and table rows are clamped to the bank, a
+ * slot outside its frame's padded length is left unwritten.  No atomics, no workspace.
+ * N == 0 (with no rows): MR_OK, nothing launched.  MR_ERR_BADARG before any launch: a negative
+ * count, rows beyond their capacity or beyond INT_MAX - 256, rows without frames, frames without a bank
+ * (M, total_verts or total_faces < 1), a NULL or misaligned pointer (objfaces: 8 bytes). */
+MR_API int mr_obj_bank_build(const float* verts, const int32_t* table, int num_models,
+                             int total_verts, float* box, float* centre, float* canverts,
+                             mr_stream_t stream);
+MR_API int mr_obj_gt_batch(const float* verts, const float* canverts, const float* centre,
+                           const int32_t* faces, const int32_t* table, int num_models,
+                           int total_verts, int total_faces, const MrObjFrame* frames,
+                           int num_frames, int64_t vert_rows, int64_t face_rows, float* objverts3d,
+                           float* objcanverts, int64_t vert_capacity, int64_t* objfaces,
+                           int64_t face_capacity, float* objcantrans, float* objcanscale,
+                           mr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * 3. Warping (meshreg/warping/imgflowarp.py)
  * ---------------------------------------------------------------------------------- */
 

@@ -22,7 +22,7 @@ for hdr in sorted(f for f in os.listdir(B.CSRC) if f.endswith((".hpp", ".h"))) +
     with open(os.path.join(B.CSRC, hdr), "rb") as fh:
         hh.update(fh.read())
 objs = []
-for s in B.SOURCES:
+for s in B.ALL_SOURCES:
     path = os.path.join(B.CSRC, s)
     cached = B._object_for(s, hh.digest())
     if s != src and os.path.exists(cached):  # (the library's own object of an unchanged source)
