@@ -38,6 +38,7 @@ PNG_MAGIC, PNG_HEADER_BYTES, PNG_BAND_ROWS, PNG_MAX_SIDE = 0x3150524D, 64, 64, 1
 RESIZE_MAX_TAPS, RESIZE_PLAN_INTS = 33, 8  # MR_RESIZE_*: the tap cap and the plan's length of mr_frames_resize_*
 EVAL_MAX_JOBS, EVAL_PER_POINT, EVAL_PER_SAMPLE_SUM, EVAL_POINTS, EVAL_MAX_POINTS = 8, 0, 1, 2, 4096  # MR_EVAL_*: the jobs of mr_eval_feed
 EVAL_MAX_THRESHOLDS = 1024  # mr_eval_measures
+GT2D_BANK, GT2D_POINTS3D, GT2D_POINTS2D = 0, 1, 2  # MR_GT2D_*: where a record of mr_gt2d_batch takes its points from
 MANO_POSE_PCA, MANO_POSE_AXISANG = 0, 1  # MR_MANO_POSE_*: the pose form of mr_mano_forward_full / mr_mano_backward_full
 # (image, mask) pairs the fused pair kernels are instantiated for
 FUSED_BATCH_DTYPES = ((torch.float32, torch.float32), (torch.bfloat16, torch.uint8), (torch.bfloat16, torch.float32))
@@ -93,6 +94,8 @@ SIGNATURES = {
     # ground-truth object meshes from a resident model bank (csrc/obj_gt.hip): additions to ABI 9
     "mr_obj_bank_build": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "mr_obj_gt_batch": (_I, [_P] * 5 + [_I, _I, _I, _P, _I, _L, _L, _P, _P, _L, _P, _L, _P, _P, _P]),
+    # 2-D ground truth from resident geometry (csrc/gt2d/gt2d.hip): an addition to ABI 9
+    "mr_gt2d_batch": (_I, [_P, _P, _I, _I, _P, _L, _P, _L, _P, _I, _L, _P, _P, _L, _P]),
     "mr_warp_forward": (_I, [_P] * 4 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_warp_backward": (_I, [_P] * 5 + [_I, _I, _I, _I, _F, _I, _P]),
     "mr_occlusion_mask": (_I, [_P] * 4 + [_L, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),

@@ -17,6 +17,12 @@ SOURCES = ["raster_fwd.hip", "raster_bwd.hip", "raster_bwd_vc.hip", "warp.hip", 
 # tests/test_stream_record_host.py.  The library is built from both lists, which together are every .hip file of csrc/.
 OWN_DRIVER_SOURCES = ["obj_gt.hip"]
 ALL_SOURCES = SOURCES + OWN_DRIVER_SOURCES
+# ... and the sources that came after it, each again with a recorder driver of its own: gt2d/gt2d.hip with
+# tests/host/gt2d_record_main.cpp (tests/test_gt2d_record_host.py).  tests/test_objgt_record_host.py holds OWN_DRIVER_SOURCES to
+# the one file it drives and the two lists above to every .hip file directly under csrc/, and is an existing test file too: a
+# later source with its own driver lives in a subdirectory of csrc/ (compiled with csrc/ on the include path) and is listed here.
+NESTED_SOURCES = ["gt2d/gt2d.hip"]
+LIBRARY_SOURCES = ALL_SOURCES + NESTED_SOURCES  # what the library is built from
 LIB_PATH = os.path.join(_HERE, "libmeshraster_hip.so")
 # -ffp-contract=off: parity-critical fp32 expressions must round operation by operation
 # exactly like the CPU oracle (SURVEY 7 "bit-faithful coverage").
@@ -40,7 +46,7 @@ def source_hash():
     """sha256 over the compiler flags and every file the library is built from (content, not mtimes:
     a fresh checkout or a gpurun snapshot resets mtimes)."""
     h = hashlib.sha256(" ".join(HIPCC_FLAGS).encode())
-    deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC))
+    deps = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)) + [os.path.join(CSRC, f) for f in NESTED_SOURCES]
     deps.append(os.path.join(_HERE, "..", "include", "meshraster_hip.h"))
     for d in deps:
         if os.path.isfile(d):
@@ -64,7 +70,7 @@ COMPILE_FLAGS = [f for f in HIPCC_FLAGS if f != "-shared"]
 def _object_for(src, headers_hash):
     with open(os.path.join(CSRC, src), "rb") as fh:
         key = hashlib.sha256(" ".join(COMPILE_FLAGS).encode() + headers_hash + fh.read()).hexdigest()[:16]
-    return os.path.join(OBJ_DIR, f"{os.path.splitext(src)[0]}.{key}.o")
+    return os.path.join(OBJ_DIR, f"{os.path.splitext(os.path.basename(src))[0]}.{key}.o")
 
 
 def build_library(force=False, verbose=False):
@@ -80,12 +86,12 @@ def build_library(force=False, verbose=False):
     for hdr in sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))) + [os.path.join("..", "..", "include", "meshraster_hip.h")]:
         with open(os.path.join(CSRC, hdr), "rb") as fh:
             hh.update(fh.read())
-    objs = [_object_for(src, hh.digest()) for src in ALL_SOURCES]
+    objs = [_object_for(src, hh.digest()) for src in LIBRARY_SOURCES]
     procs = []
-    for src, obj in zip(ALL_SOURCES, objs):
+    for src, obj in zip(LIBRARY_SOURCES, objs):
         if os.path.exists(obj):
             continue
-        cmd = [_hipcc()] + COMPILE_FLAGS + ["-c", "-o", obj + ".tmp.o", os.path.join(CSRC, src)]
+        cmd = [_hipcc()] + COMPILE_FLAGS + (["-I", CSRC] if src in NESTED_SOURCES else []) + ["-c", "-o", obj + ".tmp.o", os.path.join(CSRC, src)]
         if verbose:
             print(" ".join(cmd))
         procs.append((obj, cmd, subprocess.Popen(cmd)))
@@ -105,7 +111,7 @@ def build_library(force=False, verbose=False):
     with open(STAMP_PATH, "w") as fh:
         fh.write(source_hash() + "\n")
     if verbose:
-        print("libmeshraster_hip.so: compiled %d of %d sources (source hash %s)" % (len(procs), len(ALL_SOURCES), source_hash()[:12]))
+        print("libmeshraster_hip.so: compiled %d of %d sources (source hash %s)" % (len(procs), len(LIBRARY_SOURCES), source_hash()[:12]))
     return LIB_PATH
 
 

@@ -37,7 +37,16 @@ the same) -- the sample then carries ``resize_to``.  Files of that size, and Non
 model id, its placement ``[A | b]`` and the same small transform as one ``obj_info`` row (``objgt.pack_obj_info``) instead of
 ``objverts3d`` / ``objfaces`` / ``objcanverts`` / ``objcantrans`` / ``objcanscale`` (the row remembers which of the three object queries were asked for: the batch gets the keys
 the host path would have given it); ``assemble_batch(obj_bank=...)`` gathers them
-from the device-resident model bank for all frames of the step in one GPU call (``objgt.obj_geometry_batch``)."""
+from the device-resident model bank for all frames of the step in one GPU call (``objgt.obj_geometry_batch``).
+The 2-D queries (none of them a default): ``affinetrans`` (TransQueries.AFFINETRANS), ``joints2d`` / ``objverts2d`` / ``handverts2d``
+(BaseQueries: ``pose_dataset.get_joints2d`` / ``get_objverts2d`` / ``get_hand_verts2d``, x mirrored as ``W - x`` where the hand is
+flipped, W the frame's width) and the same with ``_trans`` (TransQueries: through ``affinetrans``), handobjset.py:160-225.  They
+need ``frame`` among the queries: the affine and W are the frame's.  ``points2d="device"``: the sample carries one ``gt2d_info`` row
+(``gt2d.pack_gt2d_info``: the dataset's intrinsics, flip, W, the affine, the queried keys) and the annotated joints' base pixels
+(``gt2d_joints``) instead; ``assemble_batch`` projects, mirrors and crops the resident meshes for all frames of the step in one GPU
+call (``gt2d.points2d_batch``).  ``objverts2d`` then needs ``obj_geometry="device"`` and one of its three queries (the
+``obj_info`` row carries the model and the placement), ``handverts2d`` needs ``hand_geometry="device"`` and ``handverts3d`` (the
+``hand_info`` row carries the annotation)."""
 import random
 import traceback
 
@@ -52,6 +61,9 @@ from handobjectconsist_amd.datasets import frames as frames_mod
 from handobjectconsist_amd.datasets import handutils
 
 DEFAULT_QUERIES = ("frame", "camintr", "joints3d", "handverts3d", "objverts3d", "objfaces", "objcanverts", "side")
+# the 2-D ground truth: kind -> the pose dataset's accessor (handobjset.py:160-225's order)
+POINTS2D_GETTERS = (("joints2d", "get_joints2d"), ("objverts2d", "get_objverts2d"), ("handverts2d", "get_hand_verts2d"))
+POINTS2D_KEYS = tuple(k + s for k, _ in POINTS2D_GETTERS for s in ("", "_trans"))
 
 
 def flip_hand_side(target_side, hand_side):
@@ -66,7 +78,7 @@ class HandObjSet(Dataset):
                  split="train", scale_jittering=0.3, center_jittering=0.2, train=True, hue=0.15, saturation=0.5,
                  contrast=0.5, brightness=0.5, blur_radius=0.5, spacing=2, queries=DEFAULT_QUERIES, sides="both",
                  block_rot=False, sample_nb=None, has_dist2strong=False, color_fn="reference", decode="host",
-                 hand_geometry="host", hand_cam_rot=None, frame_size=None, obj_geometry="host"):
+                 hand_geometry="host", hand_cam_rot=None, frame_size=None, obj_geometry="host", points2d="host"):
         if obj_geometry not in ("host", "device"):
             raise ValueError(f"obj_geometry must be 'host' or 'device', got {obj_geometry!r}")
         if obj_geometry == "device" and not hasattr(pose_dataset, "get_obj_info"):
@@ -106,6 +118,23 @@ class HandObjSet(Dataset):
         self.max_rot, self.block_rot = max_rot, block_rot
         self.train, self.scale_jittering, self.center_jittering = train, scale_jittering, center_jittering
         self.queries = tuple(queries)
+        if points2d not in ("host", "device"):
+            raise ValueError(f"points2d must be 'host' or 'device', got {points2d!r}")
+        self.points2d = points2d
+        for kind, getter in POINTS2D_GETTERS:
+            if kind not in self.queries and kind + "_trans" not in self.queries:
+                continue
+            if "frame" not in self.queries:
+                raise ValueError(f"{kind}: the 2-D queries need \"frame\" among the queries (the crop affine and the mirror's width are the frame's)")
+            if points2d == "host" or kind == "joints2d":
+                if not hasattr(pose_dataset, getter):
+                    raise ValueError(f"the query {kind!r} needs a pose_dataset with {getter}(idx)")
+            elif kind == "objverts2d" and (obj_geometry != "device" or not any(k in self.queries for k in ("objverts3d", "objfaces", "objcanverts"))):
+                raise ValueError("points2d=\"device\": objverts2d needs obj_geometry=\"device\" and one of objverts3d / objfaces / objcanverts among "
+                                 "the queries (their obj_info row carries the model and the placement)")
+            elif kind == "handverts2d" and (hand_geometry != "device" or "handverts3d" not in self.queries):
+                raise ValueError("points2d=\"device\": handverts2d needs hand_geometry=\"device\" and handverts3d among the queries (its hand_info "
+                                 "row carries the annotation)")
         self.has_dist2strong = has_dist2strong
         if color_fn == "reference":  # the reference's own augmentation (handobjset.py:339-358)
             from handobjectconsist_amd.datasets import coloraugm
@@ -197,6 +226,28 @@ class HandObjSet(Dataset):
             else:
                 sample["frame"] = np.ascontiguousarray(frame)
             sample["flip"] = bool(flip)
+        want2d = [(kind, getter) for kind, getter in POINTS2D_GETTERS if kind in q or kind + "_trans" in q]
+        if want2d and not want_img:
+            raise ValueError("the 2-D queries need \"frame\" among the queries")
+        if want2d and self.points2d == "device":
+            # the intrinsics, the mirror and the affine travel; the meshes are projected on the GPU by assemble_batch
+            from handobjectconsist_amd.datasets import gt2d
+
+            sample["gt2d_info"] = gt2d.pack_gt2d_info(ds.get_camintr(idx), flip, width, affinetrans, q)
+        for kind, getter in want2d:
+            if self.points2d == "device" and kind != "joints2d":
+                continue
+            pts = getattr(ds, getter)(idx)
+            if flip:
+                pts = pts.copy()
+                pts[:, 0] = width - pts[:, 0]
+            if self.points2d == "device":
+                sample["gt2d_joints"] = pts.astype(np.float32)  # (the annotated joints: base pixels, mirrored already)
+                continue
+            if kind in q:
+                sample[kind] = pts.astype(np.float32)
+            if kind + "_trans" in q:
+                sample[kind + "_trans"] = np.array(handutils.transform_coords(pts, affinetrans)).astype(np.float32)
         if "camintr" in q:
             camintr = ds.get_camintr(idx)
             # the rotation is applied to the 3-D annotations: only the crop multiplies the intrinsics (:180-183)
@@ -350,6 +401,50 @@ def _obj_meshes(args, outs, device, obj_bank):
         o.update(res)
 
 
+def _gt2d_rows(dicts, obj_args, mano_layer):
+    """The dicts' ``gt2d_info`` rows, checked (all dicts or none, collated, the rows of the kinds they ask for present) before
+    anything is uploaded: None, or the arguments of ``gt2d.points2d_batch`` less the hand's vertices."""
+    with_info = sum("gt2d_info" in d for d in dicts)
+    if not with_info:
+        return None
+    if with_info != len(dicts):
+        raise ValueError(f"gt2d_info in {with_info} of {len(dicts)} dicts: a batch mixes samples of "
+                         "HandObjSet(points2d=\"device\") with samples that carry their 2-D points")
+    from handobjectconsist_amd.datasets import gt2d
+
+    rows = [np.asarray(d["gt2d_info"], np.float32) for d in dicts]
+    if any(r.ndim != 2 for r in rows):
+        raise ValueError("gt2d_info must be collated: [frames, values] per dict, not one sample's row")
+    args = gt2d.unpack_gt2d_info(np.concatenate(rows, 0))
+    keys = args.pop("keys")
+    args.update(groups=[len(r) for r in rows], keys=keys, points2d_mirrored=True)
+    if any(k.startswith("objverts2d") for k in keys):
+        if obj_args is None:
+            raise ValueError("gt2d_info asks for objverts2d: the dicts need obj_info (HandObjSet(obj_geometry=\"device\"))")
+        args.update(model=obj_args["model"], pose=obj_args["pose"])
+    if any(k.startswith("handverts2d") for k in keys):
+        if any("hand_info" not in d for d in dicts) or mano_layer is None:
+            raise ValueError("gt2d_info asks for handverts2d: the dicts need hand_info (HandObjSet(hand_geometry=\"device\")) and "
+                             "assemble_batch(mano_layer=...)")
+    if any(k.startswith("joints2d") for k in keys):
+        if any("gt2d_joints" not in d for d in dicts):
+            raise ValueError("gt2d_info asks for joints2d: the dicts need gt2d_joints")
+        args["points2d"] = np.concatenate([np.asarray(d["gt2d_joints"], np.float32) for d in dicts], 0)
+    return args
+
+
+def _points2d(args, dicts, outs, device, mano_layer, obj_bank):
+    """-> the queried ``joints2d`` / ``objverts2d`` / ``handverts2d`` and their ``_trans`` in ``outs``, through one
+    ``gt2d.points2d_batch`` call; the hand's camera-frame vertices from one more ``forward_full`` call (``gt2d.hand_cam_verts``)."""
+    from handobjectconsist_amd.datasets import gt2d, manogt
+
+    if any(k.startswith("handverts2d") for k in args["keys"]):
+        hand = manogt.unpack_hand_info(np.concatenate([np.asarray(d["hand_info"], np.float32) for d in dicts], 0))
+        args = dict(args, points3d=gt2d.hand_cam_verts(mano_layer, hand["fullpose"], hand["shape"], hand["trans"], hand["cam_rot"], device=device))
+    for o, res in zip(outs, gt2d.points2d_batch(bank=obj_bank if "model" in args else None, device=device, **args)):
+        o.update(res)
+
+
 def _images(dicts, outs, frame_keys, device, inp_res, **to_batch):
     """The dicts' frames (under one of ``frame_keys``: decoded, or packed by one codec) -> ``image`` / ``jittermask`` in
     ``outs``: decode, then ``resize`` where the dicts carry ``resize_to``, then ``color_augment`` where planned, then one ``frames_to_batch(..., **to_batch)``."""
@@ -419,16 +514,26 @@ def assemble_batch(batch, device, inp_res, normalize_img=False, mean=(0.485, 0.4
     Dicts with ``obj_info`` (``HandObjSet(obj_geometry="device")``, all of a batch or none) need ``obj_bank``, the
     ``objgt.ObjectBank`` of the dataset's models: one ``objgt.obj_geometry_batch`` call over all frames of the step gives each dict
     its ``objverts3d`` / ``objcanverts`` / ``objfaces`` (int64) / ``objcantrans`` / ``objcanscale``, padded cyclically to the dict's own
-    longest model.  A mixed batch, a missing bank and an id outside the bank raise ValueError before anything is uploaded."""
+    longest model.  A mixed batch, a missing bank and an id outside the bank raise ValueError before anything is uploaded.
+    Dicts with ``gt2d_info`` (``HandObjSet(points2d="device")``, all of a batch or none): after the hand and object calls, one
+    ``gt2d.points2d_batch`` call over all frames of the step gives each dict the 2-D keys its samples were queried for --
+    ``joints2d`` / ``objverts2d`` / ``handverts2d`` and their ``_trans``, float32 [frames, points, 2], ``objverts2d`` padded as
+    ``objverts3d`` is.  A dict with 2-D ground truth, from either path, keeps its ``affinetrans`` (the metrics read it)."""
     dicts = batch if isinstance(batch, (list, tuple)) else [batch]
     frame_keys = ("frame",) + tuple(codec.key for codec in framecodec.CODECS)
-    consumed = frame_keys + ("affinetrans", "flip", "color_plan", "hand_info", "resize_to", "obj_info")
+    consumed = frame_keys + ("affinetrans", "flip", "color_plan", "hand_info", "resize_to", "obj_info", "gt2d_info", "gt2d_joints")
     obj_args = _obj_rows(dicts, obj_bank)  # (refusals before the first upload)
+    gt2d_args = _gt2d_rows(dicts, obj_args, mano_layer)
     out = [{k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in d.items() if k not in consumed}
            for d in dicts]
     _hand_verts(dicts, out, device, mano_layer)
     if obj_args is not None:
         _obj_meshes(obj_args, out, device, obj_bank)
+    if gt2d_args is not None:
+        _points2d(gt2d_args, dicts, out, device, mano_layer, obj_bank)
+    for d, o in zip(dicts, out):
+        if "affinetrans" in d and ("gt2d_info" in d or any(k in d for k in POINTS2D_KEYS)):
+            o["affinetrans"] = torch.as_tensor(d["affinetrans"]).to(device, non_blocking=True)
     with_frames = [i for i, d in enumerate(dicts) if any(k in d for k in frame_keys)]
     if with_frames:
         m, s = (mean, std) if normalize_img else ((0.5, 0.5, 0.5), (1.0, 1.0, 1.0))

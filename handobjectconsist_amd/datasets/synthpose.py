@@ -196,6 +196,21 @@ class SynthPoseDataset:
             return self.obj_bank.canonical(self.obj_infos[idx][0])
         return (self.obj[idx] - self.can_trans) / self.can_scale, self.can_trans, self.can_scale
 
+    # the 2-D annotations, in ho3dv2.py's form (:309-312, 350-354, 454-458): ``project`` on the accessor's own 3-D points
+    @staticmethod
+    def project(points3d, cam_intr):
+        hom_2d = np.array(cam_intr).dot(np.asarray(points3d).transpose()).transpose()
+        return (hom_2d / hom_2d[:, 2:])[:, :2].astype(np.float32)
+
+    def get_joints2d(self, idx):
+        return self.project(self.get_joints3d(idx), self.get_camintr(idx))
+
+    def get_objverts2d(self, idx):
+        return self.project(self.get_obj_verts_trans(idx), self.get_camintr(idx))
+
+    def get_hand_verts2d(self, idx):
+        return self.project(self.get_hand_verts3d(idx), self.get_camintr(idx))
+
     def get_dist_idx(self, idx, dist=1):
         """Closest annotated frame `dist` steps ahead (> 0) or behind (< 0) inside the same scene."""
         other = idx ^ 1 if dist != 0 else idx

@@ -11,6 +11,11 @@ import numpy as np
 import torch
 
 
+# the per-mesh entries a trainer pads (trainmeshwarp.py's ``extend_queries``, as plain strings): the 2-D object points repeat
+# with the 3-D ones, so that row k of ``objverts2d`` stays the projection of row k of ``objverts3d``
+EXTEND_QUERIES = ("objverts3d", "objfaces", "objcanverts", "objverts2d", "objverts2d_trans")
+
+
 def pad_cyclic(array, length):
     """Rows of `array` repeated cyclically up to `length` rows."""
     array = np.asarray(array)

@@ -635,6 +635,49 @@ MR_API int mr_obj_gt_batch(const float* verts, const float* canverts, const floa
                            mr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * 2d. 2-D ground truth from resident geometry
+ * ---------------------------------------------------------------------------------- */
+/* An addition to ABI 9.  mr_gt2d_batch, one launch for a step: the projected, mirrored and cropped
+ * points of all frames of all collated dicts -- object vertices, hand vertices, joints -- as two flat
+ * [rows,2] fp32 arrays.  records[N] on the device, one per (frame, kind of point), 36 words: */
+#define MR_GT2D_BANK 0     /* vertex (slot mod n) of bank model `model` (n from the table), p = A v + b */
+#define MR_GT2D_POINTS3D 1 /* row src_first + (slot mod count) of points3d: a camera-frame point */
+#define MR_GT2D_POINTS2D 2 /* row src_first + (slot mod count) of points2d: a base pixel, not projected */
+typedef struct MrGt2dRecord {
+    int32_t mode;        /* MR_GT2D_* (anything else is taken as POINTS3D) */
+    int32_t row_offset;  /* first row of the record in base / trans; ascending over records */
+    int32_t padded;      /* rows of the record: its points repeated cyclically up to this many */
+    int32_t count;       /* points of the record's own (POINTS3D / POINTS2D; BANK reads the table) */
+    int32_t flip;        /* != 0: x = width - x */
+    int32_t model;       /* BANK: clamped to [0, M) */
+    int32_t src_first;   /* POINTS3D / POINTS2D: first row of the record's block, clamped to the array */
+    int32_t reserved;
+    float K[9];          /* the dataset's intrinsics, row-major */
+    float width;         /* W of the mirror */
+    float affine[6];     /* rows 0 and 1 of affinetrans */
+    float pose[12];      /* BANK: [A | b] row-major 3x4, as in MrObjFrame */
+} MrGt2dRecord;
+/* For slot s of a record, in fp32 with one rounding per operator:
+ *   BANK       p_i = ((A_i0 v_0 + A_i1 v_1) + A_i2 v_2) + b_i   (mr_obj_gt_batch's y, bit for bit)
+ *   hom_r = (K_r0 p_0 + K_r1 p_1) + K_r2 p_2,   x = hom_0 / hom_2,   y = hom_1 / hom_2
+ *   x = width - x where flip                                   base[row_offset + s, :]  = (x, y)
+ * and in fp64 on the fp32 values, rounded once:
+ *   t_r = (M_r0 x + M_r1 y) + M_r2                             trans[row_offset + s, :] = (t_0, t_1)
+ * hom_2 == 0 yields IEEE's inf / NaN in that row alone.  A workgroup owns 256 consecutive rows: one lane
+ * per row computes it into LDS, then one lane per output element stores it, at an index formed from the
+ * workgroup and lane ids alone; model ids, table rows and blocks of the dense arrays are clamped to their
+ * buffers; a slot outside its record's padded length, and a record whose source array is absent, is left
+ * unwritten.  The bank (verts, table: mr_obj_bank_build's inputs) may be absent (num_models == 0), so
+ * may either dense array (rows3d / rows2d == 0).  No atomics, no workspace, no allocation.
+ * N == 0 or rows == 0 (N == 0 with rows is refused): MR_OK, nothing launched.  MR_ERR_BADARG before any
+ * launch: a negative count, rows beyond capacity or beyond INT_MAX - 256, a bank without vertices, a NULL
+ * pointer of something counted, a misaligned pointer. */
+MR_API int mr_gt2d_batch(const float* verts, const int32_t* table, int num_models, int total_verts,
+                         const float* points3d, int64_t rows3d, const float* points2d, int64_t rows2d,
+                         const MrGt2dRecord* records, int num_records, int64_t rows, float* base,
+                         float* trans, int64_t capacity, mr_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * 3. Warping (meshreg/warping/imgflowarp.py)
  * ---------------------------------------------------------------------------------- */
 

@@ -22,7 +22,7 @@ for hdr in sorted(f for f in os.listdir(B.CSRC) if f.endswith((".hpp", ".h"))) +
     with open(os.path.join(B.CSRC, hdr), "rb") as fh:
         hh.update(fh.read())
 objs = []
-for s in B.ALL_SOURCES:
+for s in B.LIBRARY_SOURCES:
     path = os.path.join(B.CSRC, s)
     cached = B._object_for(s, hh.digest())
     if s != src and os.path.exists(cached):  # (the library's own object of an unchanged source)
@@ -31,9 +31,9 @@ for s in B.ALL_SOURCES:
     if s == src:
         text = open(repl).read() if os.path.isfile(repl) else subprocess.run(
             ["git", "-C", ROOT, "show", f"{repl}:handobjectconsist_amd/csrc/{s}"], capture_output=True, text=True, check=True).stdout
-        path = os.path.join(tmp, s)
+        path = os.path.join(tmp, os.path.basename(s))
         open(path, "w").write(text)
-    obj = os.path.join(tmp, s + ".o")
+    obj = os.path.join(tmp, os.path.basename(s) + ".o")
     subprocess.check_call([B._hipcc()] + B.COMPILE_FLAGS + ["-I", B.CSRC, "-c", "-o", obj, path])
     objs.append(obj)
 out = os.path.join(out_dir, f"lib_{name}.so")
